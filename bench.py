@@ -20,7 +20,9 @@ Plumbing switches for the test-suite / one-GPU rehearsals of the N > 1 path (nev
 (collectives over gloo instead of RCCL: several ranks can then share ONE GPU), --device cpu (the product's CPU formulation, eager),
 --nrr (neural rendering resolution, 128 = BASELINE).
 
-Extra legs on rank 0 at N == 1 (all outside the timed region):
+A plain run sets up, captures the step's graph, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR)
+and prints the line.  --full adds, outside the timed region: the check of the captured graph against the eager call, and on rank 0
+at N == 1 the extra legs below (--no-extra / --no-roofline / --no-cpu-baseline leave some of them out):
   sustained    -- the same step repeated until the GPU has been busy for >= 2 s (an external sampler can see it)
   roofline     -- per-launch HIP-event timing of the dominant kernel family over extra eager frames
   cpu_baseline -- the CPU oracle (restatement of the reference's pure-PyTorch op path) timed on the host cores on a bounded
@@ -55,6 +57,7 @@ PMC_FILE = next((p for p in (os.path.join(REPO, 'profiles', f'r{r:02d}_pmc_frame
                 os.path.join(REPO, 'profiles', 'r05_pmc_frame_hbm_traffic.json'))      # newest committed PMC collection
 DEV = torch.device('cuda')      # set by setup_distributed
 DIST = False                    # a process group is up (N > 1, or --force-dist at N = 1): steps end in the all-gather, timing brackets in barriers
+DUMP_BYTES = 64 << 20           # --dump-outputs: bytes written in all
 
 
 def sync():
@@ -71,6 +74,11 @@ def parse():
     ap.add_argument('--workload', default='reenact', choices=['reenact', 'drive'])
     ap.add_argument('--frames-per-rank', type=int, default=0, help='frames per rank per step (default: 1 at N = 1, 8 at N > 1)')
     ap.add_argument('--gather', default='f32', choices=['f32', 'u8'], help='dtype of the all-gathered frames (N > 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also check the captured graph against the eager call and run the extra legs (sustained, variants, roofline, CPU baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last step returned as DIR/<name>.npy (float32, float64 kept; '
+                         f'{DUMP_BYTES >> 20} MB in all: an array over its share is a fixed seeded sample of its flattened elements)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip the variant legs (f32_mfma_only, sr_fp16, drive_loop, batch8, encoder)')
@@ -159,7 +167,8 @@ class Workload:
 
 
 def make_step(gen, wl, graphed, gather_dtype):
-    """Returns step(k): render this rank's frames of step k and (N > 1) all-gather the frames of the step."""
+    """Returns step(k): render this rank's frames of step k and (N > 1) all-gather the frames of the step.  step.last holds what the
+    step's caller receives: the synthesis outputs (N = 1) or the gathered frames of the step (N > 1)."""
     from invertavatar_amd.output import to_uint8_hwc
     world, per = wl.world, wl.per_rank
     if DIST:
@@ -172,9 +181,43 @@ def make_step(gen, wl, graphed, gather_dtype):
         img = out['image']
         if DIST:
             part = to_uint8_hwc(img) if gather_dtype == 'u8' else img.contiguous()
-            return all_gather_frames(gathered, part)
+            step.last = {'image': all_gather_frames(gathered, part)}
+            return step.last['image']
+        step.last = out
         return img
     return step
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every tensor of `outputs` as <path>/<name>.npy (nested names joined by '.'), float32 (float64 stays float64).
+    At most DUMP_BYTES in all: the arrays are taken smallest first, and one larger than its even share of what is left is replaced by
+    a fixed seeded sample of its flattened elements (1-D, the same indices on every run with the same arguments)."""
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            flat[name] = v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk(f'{name}.{k}' if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f'{name}.{i}', x)
+    walk('', outputs)
+    os.makedirs(path, exist_ok=True)
+    left, names = DUMP_BYTES, sorted(flat, key=lambda n: flat[n].numel())
+    for i, name in enumerate(names):
+        t = flat[name].detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dtype == torch.float64 else 4
+        share = left // (len(names) - i)
+        if t.numel() * item > share:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), share // item))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, f'{name}.npy'), a)
+        left -= a.nbytes
 
 
 def timed(step, steps, warmup, world):
@@ -197,11 +240,14 @@ def timed(step, steps, warmup, world):
     return dt
 
 
-def capture(gen, wl, batch, **kw):
-    """hipGraph of one synthesis call at this batch size, validated against the eager call (same bits expected)."""
+def capture(gen, wl, batch, validate=True, **kw):
+    """hipGraph of one synthesis call at this batch size (captured here, outside the timed steps), validated against the eager call
+    (same bits expected) when `validate`."""
     from invertavatar_amd.graphed import GraphedSynthesis
     graphed = GraphedSynthesis(gen, batch=batch, neural_rendering_resolution=NRR, with_ray_dist=wl.world > 1, **kw)
     img_g = wl.replay(graphed, 0)['image'].clone()
+    if not validate:
+        return graphed, 'hipGraph replay (not checked against eager: --full checks it)'
     err = (img_g - wl.eager(gen, 0)['image']).abs().max().item()
     if not err <= 1e-5:
         raise RuntimeError(f'graph replay differs from eager by {err}')
@@ -567,26 +613,30 @@ def drive_main(args, rank, world):
         def eager(s):
             return gen.synthesis_withTexture(ws8, tex8, wl.cams[s], {'uvcoords_image': wl.uvs[s]}, static_feats=sta8, neural_rendering_resolution=NRR,
                                              noise_mode='const', evaluation=True, jitter=wl.jits[s],
-                                             ray_dist=wl.frame_dists[s] if per > 1 else None)['image']
+                                             ray_dist=wl.frame_dists[s] if per > 1 else None)
         graphed, launch = None, 'eager'
         if DEV.type == 'cuda' and not args.eager:
             try:
                 graphed = GraphedDrive(gen, ws, tex, sta, batch=per, neural_rendering_resolution=NRR, ray_dist_elems=per if per > 1 else 0)
                 img_g = graphed(wl.cams[0], wl.uvs[0], wl.jits[0], wl.frame_dists[0] if per > 1 else None)['image'].clone()
-                err = (img_g - eager(0)).abs().max().item()
-                if not err <= 1e-5:
-                    raise RuntimeError(f'graph replay differs from eager by {err}')
-                launch = 'hipGraph replay (validated against eager: max |d| = %.1e)' % err
+                launch = 'hipGraph replay (not checked against eager: --full checks it)'
+                if args.full:
+                    err = (img_g - eager(0)['image']).abs().max().item()
+                    if not err <= 1e-5:
+                        raise RuntimeError(f'graph replay differs from eager by {err}')
+                    launch = 'hipGraph replay (validated against eager: max |d| = %.1e)' % err
             except Exception as exc:   # noqa: BLE001
                 graphed, launch = None, f'eager (graph capture unavailable: {exc})'
 
         def step(k):
             s = k % wl.n_sets
-            img = graphed(wl.cams[s], wl.uvs[s], wl.jits[s], wl.frame_dists[s] if per > 1 else None)['image'] if graphed is not None else eager(s)
+            step.last = graphed(wl.cams[s], wl.uvs[s], wl.jits[s], wl.frame_dists[s] if per > 1 else None) if graphed is not None else eager(s)
             if DIST:
-                return all_gather_frames(gathered, img.contiguous())
-            return img
+                step.last = {'image': all_gather_frames(gathered, step.last['image'].contiguous())}
+            return step.last['image']
         dt = timed(step, args.steps, args.warmup, world)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step.last)
     fps = world * per * args.steps / dt
     out = {'metric': 'frames/sec (512^2 out, 128^2 neural render)', 'value': round(fps, 3), 'unit': 'frames/s',
            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
@@ -645,11 +695,13 @@ def main():
         graphed, launch_mode = None, 'eager'
         if not args.eager and DEV.type == 'cuda':
             try:
-                graphed, launch_mode = capture(gen, wl, per)
+                graphed, launch_mode = capture(gen, wl, per, validate=args.full)
             except Exception as exc:   # noqa: BLE001  fall back to eager launches, and say so in the JSON line
                 graphed, launch_mode = None, f'eager (graph capture unavailable: {exc})'
         step = make_step(gen, wl, graphed, args.gather)
         dt = timed(step, args.steps, args.warmup, world)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step.last)
         cfg = 'configs[1]: reenact_avatar_next3d single-seed render, 1 frame per synthesis call' if per == 1 and world == 1 else \
               f'configs[3]: batched reenactment, batch {per * world} = {per} frames per rank per step, frame-sharded'
         result = {
@@ -669,7 +721,7 @@ def main():
             result['config']['rehearsal'] = f'backend {args.dist_backend}, device {args.device}: plumbing run, not a measurement'
         if DIST and world == 1:
             result['config']['force_dist'] = f'process group up at world size 1 (backend {torch.distributed.get_backend()}): every timed step ends in all_gather_into_tensor'
-        if rank == 0 and world == 1 and per == 1 and DEV.type == 'cuda' and not DIST:
+        if args.full and rank == 0 and world == 1 and per == 1 and DEV.type == 'cuda' and not DIST:
             # keep the GPU busy for >= 2 s with the same step (the timed K steps alone can be shorter than a sampler's period)
             n, t_s = 0, time.perf_counter()
             while time.perf_counter() - t_s < 2.0:

@@ -8,7 +8,7 @@ reference imports but the container lacks are stubbed: ``
 ``torchvision`` (unused on the path) and ``cv2`` (only ``floodFill`` is reached; stubbed with
 scipy.ndimage connected-component labelling, 4-connectivity).
 
-Usage:  python tests/golden/make_golden.py [--only ops,camera,renderer,eg3d,small,extra,full,names,encoder]
+Usage:  python tests/golden/make_golden.py [--only ops,camera,renderer,eg3d,small,extra,full,names,encoder,dataset]
 """
 import argparse
 import contextlib
@@ -666,6 +666,35 @@ def gen_encoder_new():
     print(f'encoder_new_state_names.txt: {len(lines)} tensors')
 
 
+def gen_dataset():
+    """Every item the reference's ImageFolderDataset returns for the directory tests/test_dataset_cpu.py writes (RGBA frames), in the
+    three reader configurations of test_equal_to_the_reference_reader, flattened by that test's _flatten."""
+    import importlib
+    import pathlib
+    import tempfile
+    import PIL.Image
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import test_dataset_cpu as T
+    sys.modules['cv2'].imread = lambda p, flag=1: np.asarray(PIL.Image.open(p).convert('L'))   # imread(path, 0) of a 1-channel PNG
+    ref_mod = importlib.import_module('training_avatar_texture.dataset_new')
+    out, cwd = {}, os.getcwd()
+    with tempfile.TemporaryDirectory() as d:
+        path, names, _, _ = T._write_dataset(pathlib.Path(d), rgba=True)
+        os.chdir(d)              # the UV face mask is read relative to the working directory
+        try:
+            for c, extra in enumerate(T.READER_CONFIGS):
+                ref = ref_mod.ImageFolderDataset(**T._kwargs(path, **extra))
+                out[f'{c}/len'] = np.int64(len(ref))
+                out[f'{c}/label_shape'], out[f'{c}/image_shape'] = np.array(str(list(ref.label_shape))), np.array(str(list(ref.image_shape)))   # (may hold None)
+                for i in range(len(ref)):
+                    T._flatten(out, f'{c}/item{i}', ref[i])
+                    T._flatten(out, f'{c}/by_name{i}', ref.get_by_name(names[i]))
+        finally:
+            os.chdir(cwd)
+    np.savez_compressed(os.path.join(HERE, 'dataset_reference.npz'), **out)
+    print(f'dataset_reference.npz: {len(out)} arrays')
+
+
 def gen_names():
     """(name, shape, dtype) of every parameter/buffer: the checkpoint-compatibility contract."""
     for width, fname in (('full', 'generator_state_names.txt'), ('small', 'generator_state_names_small.txt')):
@@ -678,7 +707,7 @@ def gen_names():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', default='ops,flr,camera,renderer,eg3d,small,extra,full,bench,sr16,harness,names,encoder,encoder_new')
+    ap.add_argument('--only', default='ops,flr,camera,renderer,eg3d,small,extra,full,bench,sr16,harness,names,encoder,encoder_new,dataset')
     args = ap.parse_args()
     install_stubs()
     sys.path.insert(0, REF)
@@ -699,6 +728,7 @@ def main():
         if 'names' in todo: gen_names()
         if 'encoder' in todo: gen_encoder()
         if 'encoder_new' in todo: gen_encoder_new()
+        if 'dataset' in todo: gen_dataset()
 
 
 if __name__ == '__main__':

@@ -105,7 +105,8 @@ def test_bench_n_gt_1_path_two_ranks_on_one_gpu(workload, extra):
     batch-global / per-frame ray_dist input, the all-gather and the max-over-ranks timing all execute (RCCL itself is the driver's)."""
     from test_bench_cpu import run_bench
     # reenact: plain `python bench.py --gpus 2` (bench.py starts its own ranks); drive: under torch.distributed.run, as the driver's N > 1 command
-    out = run_bench(None if workload == 'reenact' else 29643, '--dist-backend', 'gloo', '--width', 'full', '--steps', '2', '--warmup', '1',
+    # --full: the captured graph is checked against the eager call (a mismatch would fall back to eager launches)
+    out = run_bench(None if workload == 'reenact' else 29643, '--full', '--dist-backend', 'gloo', '--width', 'full', '--steps', '2', '--warmup', '1',
                     '--frames-per-rank', '2', '--workload', workload, *extra, timeout=1500)
     assert out['n_gpus'] == 2 and out['config']['global_batch'] == 4 and out['value'] > 0
     assert out['config']['launch'].startswith('hipGraph replay'), out['config']['launch']
@@ -133,7 +134,7 @@ def test_bench_force_dist_runs_rccl_at_world_size_one(workload, extra):
     """RCCL itself executes on the one-GPU box.  `bench.py --gpus 1 --force-dist` brings up
     init_process_group('nccl', world_size=1, device_id=cuda:0) with HSA_ENABLE_IPC_MODE_LEGACY=0 and ends every timed step in the
     all_gather_into_tensor of the N > 1 path (+ its barriers and the max-over-ranks all-reduce)."""
-    out = _run_bench_one_rank('--force-dist', '--steps', '3', '--warmup', '1', '--frames-per-rank', '2', '--workload', workload, *extra)
+    out = _run_bench_one_rank('--full', '--force-dist', '--steps', '3', '--warmup', '1', '--frames-per-rank', '2', '--workload', workload, *extra)
     assert out['n_gpus'] == 1 and out['value'] > 0 and 'all_gather' in out['config']['collective']
     assert 'nccl' in out['config'].get('force_dist', '') or workload == 'drive'
     assert out['config']['launch'].startswith('hipGraph replay'), out['config']['launch']

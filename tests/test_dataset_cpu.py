@@ -1,10 +1,8 @@
 """`training_avatar_texture.dataset_new.ImageFolderDataset` (the scripts' reader of the on-disk format, eval_seq.py:106-128,204):
-known answers on a dataset written by this test, and -- where /root/reference exists (build container) -- item-by-item equality
-with the reference's class reading the same directory."""
+known answers on a dataset written by this test, and item-by-item equality with what the reference's class returns for the same
+directory (stored under tests/golden/)."""
 import json
 import os
-import sys
-import types
 
 import numpy as np
 import PIL.Image
@@ -80,42 +78,37 @@ def test_known_answers(tmp_path, monkeypatch):
         ds.get_by_name('vidA/none.png')
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/training_avatar_texture'), reason='reference checkout not present (GPU box)')
+READER_CONFIGS = (dict(load_uv=True), dict(load_bg=True), dict(load_uv=True, load_bg=True, resolution=8))
+
+
+def _flatten(out, key, v):
+    """One item of the reader as flat arrays: dicts and tuples by key / position under `key`, strings as 0-d str arrays."""
+    if isinstance(v, dict):
+        for k, x in v.items():
+            _flatten(out, f'{key}/{k}', x)
+    elif isinstance(v, (tuple, list)):
+        for j, x in enumerate(v):
+            _flatten(out, f'{key}/{j}', x)
+    else:
+        out[key] = np.array(v) if isinstance(v, str) else v
+
+
 def test_equal_to_the_reference_reader(tmp_path, monkeypatch):
+    """Item by item, dtype and shape included, equal to what the reference's class returns for the same directory in three reader
+    configurations: tests/golden/dataset_reference.npz (tests/golden/make_golden.py:gen_dataset)."""
     path, names, _, _ = _write_dataset(tmp_path, rgba=True)
     monkeypatch.chdir(tmp_path)
-    cv2 = types.ModuleType('cv2')             # OpenCV is absent here: imread(path, 0) of a single-channel PNG via PIL
-    cv2.imread = lambda p, flag=1: np.asarray(PIL.Image.open(p).convert('L'))
-    saved = {k: sys.modules.get(k) for k in ('cv2', 'dnnlib', 'training_avatar_texture', 'training_avatar_texture.dataset_new')}
-    sys.modules['cv2'] = cv2
-    sys.path.insert(0, '/root/reference')
-    try:
-        for k in ('dnnlib', 'training_avatar_texture', 'training_avatar_texture.dataset_new'):
-            sys.modules.pop(k, None)
-        import importlib
-        ref_mod = importlib.import_module('training_avatar_texture.dataset_new')
-        assert ref_mod.__file__.startswith('/root/reference')
-        for extra in (dict(load_uv=True), dict(load_bg=True), dict(load_uv=True, load_bg=True, resolution=8)):
-            ref = ref_mod.ImageFolderDataset(**_kwargs(path, **extra))
-            own = dataset_new.ImageFolderDataset(**_kwargs(path, **extra))
-            assert len(ref) == len(own) and ref.label_shape == own.label_shape and ref.image_shape == own.image_shape
-
-            def same(a, b):
-                if isinstance(a, dict):
-                    assert a.keys() == b.keys()
-                    return all(same(a[k], b[k]) for k in a)
-                if isinstance(a, str):
-                    return a == b
-                return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
-            for i in range(len(ref)):
-                assert all(same(x, y) for x, y in zip(ref[i], own[i])), (extra, i)
-                assert all(same(x, y) for x, y in zip(ref.get_by_name(names[i]), own.get_by_name(names[i])))
-    finally:
-        sys.path.remove('/root/reference')
-        for k in [k for k in sys.modules if k.split('.')[0] in ('dnnlib', 'training_avatar_texture') and not k.startswith('invertavatar_amd')]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dataset_reference.npz'))
+    for c, extra in enumerate(READER_CONFIGS):
+        own = dataset_new.ImageFolderDataset(**_kwargs(path, **extra))
+        assert len(own) == int(want[f'{c}/len'])
+        assert str(list(own.label_shape)) == str(want[f'{c}/label_shape']) and str(list(own.image_shape)) == str(want[f'{c}/image_shape'])
+        got = {}
+        for i in range(len(own)):
+            _flatten(got, f'{c}/item{i}', own[i])
+            _flatten(got, f'{c}/by_name{i}', own.get_by_name(names[i]))
+        keys = {k for k in want.files if k.startswith(f'{c}/') and k.split('/')[1] not in ('len', 'label_shape', 'image_shape')}
+        assert set(got) == keys, (extra, sorted(set(got) ^ keys))
+        for k in sorted(keys):
+            a, b = want[k], np.asarray(got[k])
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), (extra, k)

@@ -2,10 +2,8 @@
 
 The fixture pickle is written by this test in the reference's byte format -- every persistent object reduced to
 torch_utils.persistence._reconstruct_persistent_obj(meta) with an (empty) module_src -- from a generator of this backend, so no
-reference source travels; when /root/reference is present (build container) a pickle made by the reference's own classes is
-loaded as well."""
+reference source travels."""
 import io
-import os
 import pickle
 import sys
 import types
@@ -87,34 +85,6 @@ def test_unknown_persistent_classes_stay_shells_and_tf_pickles_are_refused():
     data = legacy.load_network_pkl(io.BytesIO(_reference_format_pickle(dict(G=g, D=d))))
     assert isinstance(data['D'], legacy.PickledModule) and data['D'].class_name == 'DualDiscriminator'
     assert torch.equal(legacy.collect_state_dict(data['D'])['x'], torch.ones(3))
-
-
-@pytest.mark.skipif(not os.path.isdir('/root/reference/training_avatar_texture'), reason='needs the reference checkout (build container only)')
-def test_pickle_written_by_the_reference_itself():
-    """The real thing: the reference's TriPlaneGenerator pickled by the reference's persistence (module source embedded),
-    loaded here without executing that source."""
-    import subprocess
-    code = r'''
-import sys, types, pickle, io
-sys.path.insert(0, '/root/reference'); sys.path.insert(0, %r)
-import make_golden as mg
-mg.install_stubs()
-import torch
-from invertavatar_amd import synthetic
-from training_avatar_texture.triplane_v20 import TriPlaneGenerator
-g = TriPlaneGenerator(**synthetic.generator_kwargs('small')).eval().requires_grad_(False)
-synthetic.fill_parameters(g)
-g.neural_rendering_resolution = 64
-sys.stdout.buffer.write(pickle.dumps(dict(G=g, G_ema=g, D=None)))
-''' % os.path.join(os.path.dirname(__file__), 'golden')
-    blob = subprocess.run([sys.executable, '-c', code], capture_output=True, check=True).stdout
-    assert b'module_src' in blob
-    data = legacy.load_network_pkl(io.BytesIO(blob))
-    new = data['G_ema']
-    assert type(new) is TriPlaneGenerator and new.neural_rendering_resolution == 64
-    ref = TriPlaneGenerator(**synthetic.generator_kwargs('small')).eval().requires_grad_(False)
-    synthetic.fill_parameters(ref)
-    assert all(torch.equal(a, b) for a, b in zip(ref.state_dict().values(), new.state_dict().values()))
 
 
 def test_pickle_naming_a_foreign_global_is_refused():

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IA_HIP_ABI_VERSION 7      /* 7 (r06, additive): ia_tokens_split / _t, ia_layernorm_split, ia_dwconv3x3_tokens_split, ia_im2col_split, ia_linear_sx / _splitk / _splitk_plan, ia_matmul_sx, ia_softmax_split, ia_attention_sx / _supported; 6 (r06): ia_render_rays (+ rgb_split, rgb_split_styles, rgb_split_planes), + ia_render_rays_box, ia_ray_limits_box / _parts; 5 (r05; ia_conv2d_mfma_sx_rgb narrowed to n <= 3 fused ToRGB channels, otherwise additive): ia_conv2d_down_sx / _plan, ia_conv3x3_s2_tiny, ia_bn_train_split, ia_convgru_gates_split / _update_split, ia_dwconv3x3_tokens, ia_se_gate_split, ia_upsample_bilinear_add; 4 (r04): + ia_upconv2d_rows_sx / _plan, ia_mouth_edge_blur, ia_split_saturation_poll, ia_conv2d_sx_supported; - ia_conv2d_small; 3 (r03, additive): ia_torgb, ia_upconv2d_fir_sx; 2 (r03): ia_render_rays (+ u_importance), ia_act_split (+ shift), ia_conv2d_mfma_sx (+ prelu_alpha), ia_uv_rasterize (+ binarize_mask) */
+#define IA_HIP_ABI_VERSION 7      /* 7 (additive): ia_query_planes, ia_density_grid, ia_mc_scratch_bytes, ia_mc_count, ia_mc_emit; 7 (r06, additive): ia_tokens_split / _t, ia_layernorm_split, ia_dwconv3x3_tokens_split, ia_im2col_split, ia_linear_sx / _splitk / _splitk_plan, ia_matmul_sx, ia_softmax_split, ia_attention_sx / _supported; 6 (r06): ia_render_rays (+ rgb_split, rgb_split_styles, rgb_split_planes), + ia_render_rays_box, ia_ray_limits_box / _parts; 5 (r05; ia_conv2d_mfma_sx_rgb narrowed to n <= 3 fused ToRGB channels, otherwise additive): ia_conv2d_down_sx / _plan, ia_conv3x3_s2_tiny, ia_bn_train_split, ia_convgru_gates_split / _update_split, ia_dwconv3x3_tokens, ia_se_gate_split, ia_upsample_bilinear_add; 4 (r04): + ia_upconv2d_rows_sx / _plan, ia_mouth_edge_blur, ia_split_saturation_poll, ia_conv2d_sx_supported; - ia_conv2d_small; 3 (r03, additive): ia_torgb, ia_upconv2d_fir_sx; 2 (r03): ia_render_rays (+ u_importance), ia_act_split (+ shift), ia_conv2d_mfma_sx (+ prelu_alpha), ia_uv_rasterize (+ binarize_mask) */
 
 typedef enum ia_status {
     IA_OK = 0,
@@ -767,6 +767,54 @@ int ia_split_saturation_poll(unsigned int* h_flagged, int reset, void* stream);
  *   src, dst, nbytes : HOST arrays of n device pointers / byte counts (any alignment; 16-byte aligned segments move as uint4)
  */
 int ia_stage_inputs(const void* const* src, void* const* dst, const int64_t* nbytes, int n, void* stream);
+
+/*
+ * Avatar geometry (csrc/geometry.hip).  Replaces the point query of TriPlaneGenerator.sample / sample_mixed
+ * (training_avatar_texture/triplane_v20.py:341-402: renderer.run_model = sample_from_planes + OSGDecoder.forward) and the
+ * chunked lattice helpers of inversion/model_utils.py:90-165; marching cubes has no counterpart in the reference.
+ */
+#define IA_GEOM_FLIP_Z 1              /* negate z before the plane projection (ImportanceRenderer.flip_z) */
+
+/*
+ * Decoder output at points.  planes_cl: [B,3,H,W,32] fp32 (the renderer's channels-last planes, as for ia_render_rays_box);
+ * points: [B,M,3]; w0 [64,32], b0 [64], w1 [33,64], b1 [33]: the OSGDecoder's raw FullyConnectedLayer parameters (the library
+ * applies the gains lr_multiplier / sqrt(fan_in) and lr_multiplier).  Per point: flip z (flags & IA_GEOM_FLIP_Z), scale by
+ * 2 / box_warp, bilinear zero-padded align_corners=False gather of the three planes, mean, softplus(threshold 20) hidden layer.
+ *   sigma : [B,M,1] layer-2 row 0
+ *   rgb   : [B,M,32] sigmoid(rows 1..32) * 1.002 - 0.001, or NULL (density only: the colour rows are skipped)
+ * fp32 VALU arithmetic throughout.
+ */
+int ia_query_planes(const float* planes_cl, const float* points, const float* w0, const float* b0, const float* w1, const float* b1,
+                    float lr_multiplier, float box_warp, int flags, int B, int M, int plane_h, int plane_w,
+                    float* sigma, float* rgb, void* stream);
+
+/*
+ * Density on an nx x ny x nz lattice without a coordinate tensor: volume[b,i,j,k] (x slowest, z fastest) is sigma of
+ * ia_query_planes at the point whose coordinate along axis a is, in fp32 with every operation rounded,
+ *     (h_origin[a] - 0.5f * h_cube_length[a]) + idx * (h_cube_length[a] / (n_a - 1)),
+ * i.e. bit for bit ia_query_planes on those points.  Each dimension >= 2, nx * ny * nz < 2^31.
+ *   h_cube_length, h_origin : HOST arrays of 3 floats;  volume : [B,nx,ny,nz] fp32
+ */
+int ia_density_grid(const float* planes_cl, const float* w0, const float* b0, const float* w1, const float* b1,
+                    float lr_multiplier, float box_warp, int flags, int B, int plane_h, int plane_w, int nx, int ny, int nz,
+                    const float* h_cube_length, const float* h_origin, float* volume, void* stream);
+
+/*
+ * Marching cubes of {volume > level} (NaN = outside) on an [nx,ny,nz] fp32 volume, each dimension >= 2, nx * ny * nz < 2^31
+ * (larger volumes: IA_ERR_INVALID_ARG).  Call order:
+ *   1. ia_mc_scratch_bytes -> scratch size (4 bytes per lattice point + 8 bytes per 1024 points);
+ *   2. ia_mc_count(volume, level, scratch, totals): totals = device int[2] = {vertex count, triangle count} (-1: over INT32_MAX);
+ *   3. the caller reads the totals (one host synchronisation) and allocates verts float [V,3] and faces int32 [F,3];
+ *   4. ia_mc_emit with the SAME volume, level and scratch writes them (n_verts / n_faces: the capacities, writes beyond are dropped).
+ * One vertex per lattice edge that crosses the level, ordered by owner point (the lower end, linear index) then axis x < y < z,
+ * at p0 + t * (p1 - p0), t = (level - v0) / (v1 - v0) clamped to [0,1] (NaN -> 0), coordinates h_origin[a] + idx * h_spacing[a]
+ * (fp32, every operation rounded).  Triangles by cell (linear index of the lower corner) then case-table order (csrc/mc_tables.h),
+ * indexed into the shared vertices, wound so that normals point toward decreasing density.  No atomics: bit-reproducible.
+ */
+int ia_mc_scratch_bytes(int nx, int ny, int nz, size_t* h_bytes);
+int ia_mc_count(const float* volume, int nx, int ny, int nz, float level, void* scratch, size_t scratch_bytes, int* totals, void* stream);
+int ia_mc_emit(const float* volume, int nx, int ny, int nz, float level, const float* h_origin, const float* h_spacing,
+               void* scratch, size_t scratch_bytes, float* verts, int64_t n_verts, int* faces, int64_t n_faces, void* stream);
 
 #ifdef __cplusplus
 }

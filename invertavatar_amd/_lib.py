@@ -16,6 +16,7 @@ _lib = None
 
 c_void_p, c_int, c_int64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_f32p = ctypes.POINTER(ctypes.c_float)
 
 ABI_VERSION = 7      # IA_HIP_ABI_VERSION of include/ia_hip.h
 
@@ -95,6 +96,12 @@ _SIGNATURES = {
     'ia_stage_inputs': [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), _i64p, c_int, c_void_p],
     'ia_ray_sampler': [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     'ia_styles_demod': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    'ia_query_planes': [c_void_p] * 6 + [c_float, c_float] + [c_int] * 5 + [c_void_p] * 3,
+    'ia_density_grid': [c_void_p] * 5 + [c_float, c_float] + [c_int] * 7 + [_f32p, _f32p, c_void_p, c_void_p],
+    'ia_mc_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_mc_count': [c_void_p, c_int, c_int, c_int, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_mc_emit': [c_void_p, c_int, c_int, c_int, c_float, _f32p, _f32p, c_void_p, ctypes.c_size_t, c_void_p, c_int64, c_void_p, c_int64,
+                   c_void_p],
 }
 
 

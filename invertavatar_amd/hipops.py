@@ -1289,3 +1289,89 @@ def se_gate(v, shortcut, w1, w2):
                                     _p(out), b, c, r, h, w, _lib.stream_ptr(v.device))
     _lib.check(st, 'ia_se_gate')
     return out
+
+
+# ------------------------------------------------------------------ avatar geometry (csrc/geometry.hip)
+
+def _decoder_checked(w0, b0, w1, b1):
+    for name, t in (('w0', w0), ('b0', b0), ('w1', w1), ('b1', b1)):
+        _f32c(t, name)
+    if tuple(w0.shape) != (64, 32) or b0.numel() != 64 or tuple(w1.shape) != (33, 64) or b1.numel() != 33:
+        raise RuntimeError('decoder weights must be the OSGDecoder shapes w0 [64,32], b0 [64], w1 [33,64], b1 [33]')
+
+
+def _planes_checked(planes_cl):
+    _f32c(planes_cl, 'planes')
+    if planes_cl.dim() != 5 or planes_cl.shape[1] != 3 or planes_cl.shape[4] != 32:
+        raise RuntimeError(f'planes must be [B,3,H,W,32] channels-last, got {tuple(planes_cl.shape)}')
+    return planes_cl.shape[0], planes_cl.shape[2], planes_cl.shape[3]
+
+
+def query_planes(planes_cl, points, w0, b0, w1, b1, lr_multiplier=1.0, box_warp=1.0, flip_z=False, rgb=True):
+    """Decoder output at points (see ia_query_planes): planes [B,3,H,W,32], points [B,M,3] -> (sigma [B,M,1], rgb [B,M,32] or None)."""
+    b, ph, pw = _planes_checked(planes_cl)
+    _decoder_checked(w0, b0, w1, b1)
+    _f32c(points, 'points')
+    if points.dim() != 3 or points.shape[0] != b or points.shape[2] != 3:
+        raise RuntimeError(f'points must be [B={b},M,3], got {tuple(points.shape)}')
+    m = points.shape[1]
+    dev = planes_cl.device
+    sigma = torch.empty(b, m, 1, device=dev)
+    col = torch.empty(b, m, 32, device=dev) if rgb else None
+    flops = b * m * 2.0 * (32 * 64 + 64 * (33 if rgb else 1))
+    traffic = 4.0 * b * m * (3 + 1 + (32 if rgb else 0)) + 4.0 * planes_cl.numel()
+    with torch.cuda.device(dev), _Timed('query_planes', flops, traffic, f'M={m}'):
+        st = _lib.load().ia_query_planes(_p(planes_cl), _p(points), _p(w0), _p(b0), _p(w1), _p(b1), float(lr_multiplier), float(box_warp),
+                                         1 if flip_z else 0, b, m, ph, pw, _p(sigma), _p(col), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_query_planes')
+    return sigma, col
+
+
+def _f3(v):
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
+def density_grid(planes_cl, w0, b0, w1, b1, res, cube_length, origin, lr_multiplier=1.0, box_warp=1.0, flip_z=False):
+    """Density on the nx x ny x nz lattice of `cube_length` / `origin` (per-axis triples): [B,nx,ny,nz] (see ia_density_grid)."""
+    b, ph, pw = _planes_checked(planes_cl)
+    _decoder_checked(w0, b0, w1, b1)
+    nx, ny, nz = (int(r) for r in res)
+    dev = planes_cl.device
+    vol = torch.empty(b, nx, ny, nz, device=dev)
+    n = b * nx * ny * nz
+    with torch.cuda.device(dev), _Timed('density_grid', n * 2.0 * (32 * 64 + 64), 4.0 * (n + planes_cl.numel()), f'{nx}x{ny}x{nz}'):
+        st = _lib.load().ia_density_grid(_p(planes_cl), _p(w0), _p(b0), _p(w1), _p(b1), float(lr_multiplier), float(box_warp),
+                                         1 if flip_z else 0, b, ph, pw, nx, ny, nz, _f3(cube_length), _f3(origin), _p(vol),
+                                         _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_density_grid')
+    return vol
+
+
+def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
+    """Mesh of {volume > level} (see ia_mc_count / ia_mc_emit): volume [nx,ny,nz] -> (verts float32 [V,3], faces int32 [F,3]).
+    One host synchronisation (the two totals)."""
+    _f32c(volume, 'volume')
+    if volume.dim() != 3:
+        raise RuntimeError(f'volume must be [nx,ny,nz], got {tuple(volume.shape)}')
+    nx, ny, nz = volume.shape
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_mc_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_mc_scratch_bytes')
+    dev = volume.device
+    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    stream = _lib.stream_ptr(dev)
+    with torch.cuda.device(dev):
+        with _Timed('mc_count', 0.0, 4.0 * volume.numel() + nbytes.value, f'{nx}x{ny}x{nz}'):
+            st = lib.ia_mc_count(_p(volume), nx, ny, nz, float(level), _p(scratch), nbytes.value, _p(totals), stream)
+        _lib.check(st, 'ia_mc_count')
+        n_verts, n_faces = (int(v) for v in totals.cpu())
+        if n_verts < 0 or n_faces < 0:
+            raise RuntimeError(f'marching_cubes: more than 2^31 - 1 vertices or triangles in a {nx}x{ny}x{nz} volume')
+        verts = torch.empty(n_verts, 3, device=dev)
+        faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+        with _Timed('mc_emit', 0.0, 4.0 * volume.numel() + nbytes.value + 12.0 * (n_verts + n_faces), f'{nx}x{ny}x{nz}'):
+            st = lib.ia_mc_emit(_p(volume), nx, ny, nz, float(level), _f3(origin), _f3(spacing), _p(scratch), nbytes.value,
+                                _p(verts), n_verts, _p(faces), n_faces, stream)
+        _lib.check(st, 'ia_mc_emit')
+    return verts, faces

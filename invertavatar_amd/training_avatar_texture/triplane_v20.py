@@ -526,6 +526,37 @@ class TriPlaneGenerator(torch.nn.Module):
                      **synthesis_kwargs):
         return self._query(ws, coordinates, directions, mesh_condition, update_emas, synthesis_kwargs)
 
+    def query_points(self, ws, coordinates, mesh_condition, **synthesis_kwargs):
+        """What ``sample_mixed`` returns ({'rgb' [B,M,32], 'sigma' [B,M,1]}) without ray directions (the decoder ignores them).  Device
+        tensors: the planes, then ONE ``ia_query_planes`` launch (gather + decoder, fp32) instead of grid_sample + two linear layers."""
+        from .. import geometry
+        planes = geometry.generator_planes(self, ws, mesh_condition, **synthesis_kwargs)
+        return geometry.query_planes(planes, self.decoder, coordinates, self.rendering_kwargs['box_warp'], rgb=True)
+
+    @torch.no_grad()
+    def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
+                         **synthesis_kwargs):
+        """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
+        ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
+        as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
+        'colors' uint8 [V,3] (the decoder's rgb[:3] at the vertices).  ``level`` = 10 is the EG3D-family shape threshold: a knob, not a
+        constant of the model.  The planes are computed once per call; device tensors stay on the device throughout."""
+        from .. import geometry
+        box_warp = self.rendering_kwargs['box_warp']
+        length = box_warp if cube_length is None else cube_length
+        planes = geometry.generator_planes(self, ws, mesh_condition, **synthesis_kwargs)
+        volume = geometry.density_volume(planes, self.decoder, resolution, length, origin, box_warp)
+        res, ls, org = geometry._res3(resolution), geometry._vec3(length), geometry._vec3(origin)
+        axes = [geometry.lattice_axis(n, ls[a], org[a]) for a, n in enumerate(res)]
+        out = []
+        for b in range(volume.shape[0]):
+            verts, faces = geometry.marching_cubes(volume[b], level, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
+            item = {'volume': volume[b], 'verts': verts, 'faces': faces}
+            if with_colors:
+                item['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, verts, box_warp)
+            out.append(item)
+        return out
+
     def forward(self, z, c, v, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None, update_emas=False,
                 cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)

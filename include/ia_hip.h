@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IA_HIP_ABI_VERSION 7      /* 7 (additive): ia_query_planes, ia_density_grid, ia_mc_scratch_bytes, ia_mc_count, ia_mc_emit; 7 (r06, additive): ia_tokens_split / _t, ia_layernorm_split, ia_dwconv3x3_tokens_split, ia_im2col_split, ia_linear_sx / _splitk / _splitk_plan, ia_matmul_sx, ia_softmax_split, ia_attention_sx / _supported; 6 (r06): ia_render_rays (+ rgb_split, rgb_split_styles, rgb_split_planes), + ia_render_rays_box, ia_ray_limits_box / _parts; 5 (r05; ia_conv2d_mfma_sx_rgb narrowed to n <= 3 fused ToRGB channels, otherwise additive): ia_conv2d_down_sx / _plan, ia_conv3x3_s2_tiny, ia_bn_train_split, ia_convgru_gates_split / _update_split, ia_dwconv3x3_tokens, ia_se_gate_split, ia_upsample_bilinear_add; 4 (r04): + ia_upconv2d_rows_sx / _plan, ia_mouth_edge_blur, ia_split_saturation_poll, ia_conv2d_sx_supported; - ia_conv2d_small; 3 (r03, additive): ia_torgb, ia_upconv2d_fir_sx; 2 (r03): ia_render_rays (+ u_importance), ia_act_split (+ shift), ia_conv2d_mfma_sx (+ prelu_alpha), ia_uv_rasterize (+ binarize_mask) */
+#define IA_HIP_ABI_VERSION 7      /* 7 (additive): ia_raycast_scratch_bytes, ia_volume_bricks, ia_raycast_volume, ia_volume_gradient; 7 (additive): ia_query_planes, ia_density_grid, ia_mc_scratch_bytes, ia_mc_count, ia_mc_emit; 7 (r06, additive): ia_tokens_split / _t, ia_layernorm_split, ia_dwconv3x3_tokens_split, ia_im2col_split, ia_linear_sx / _splitk / _splitk_plan, ia_matmul_sx, ia_softmax_split, ia_attention_sx / _supported; 6 (r06): ia_render_rays (+ rgb_split, rgb_split_styles, rgb_split_planes), + ia_render_rays_box, ia_ray_limits_box / _parts; 5 (r05; ia_conv2d_mfma_sx_rgb narrowed to n <= 3 fused ToRGB channels, otherwise additive): ia_conv2d_down_sx / _plan, ia_conv3x3_s2_tiny, ia_bn_train_split, ia_convgru_gates_split / _update_split, ia_dwconv3x3_tokens, ia_se_gate_split, ia_upsample_bilinear_add; 4 (r04): + ia_upconv2d_rows_sx / _plan, ia_mouth_edge_blur, ia_split_saturation_poll, ia_conv2d_sx_supported; - ia_conv2d_small; 3 (r03, additive): ia_torgb, ia_upconv2d_fir_sx; 2 (r03): ia_render_rays (+ u_importance), ia_act_split (+ shift), ia_conv2d_mfma_sx (+ prelu_alpha), ia_uv_rasterize (+ binarize_mask) */
 
 typedef enum ia_status {
     IA_OK = 0,
@@ -815,6 +815,47 @@ int ia_mc_scratch_bytes(int nx, int ny, int nz, size_t* h_bytes);
 int ia_mc_count(const float* volume, int nx, int ny, int nz, float level, void* scratch, size_t scratch_bytes, int* totals, void* stream);
 int ia_mc_emit(const float* volume, int nx, int ny, int nz, float level, const float* h_origin, const float* h_spacing,
                void* scratch, size_t scratch_bytes, float* verts, int64_t n_verts, int* faces, int64_t n_faces, void* stream);
+
+/*
+ * Isosurface ray casting over the same volumes (csrc/raycast.hip; no counterpart in the reference).  The lattice and inside rule are
+ * those of marching cubes: point (i,j,k) of an [nx,ny,nz] fp32 volume (x slowest) sits at h_lo[a] + idx * h_step[a]; a point is
+ * inside iff v > level (NaN: outside); between points the field is the trilinear interpolant.  Each dimension >= 2, nx*ny*nz < 2^31.
+ *
+ * ia_raycast_scratch_bytes -> size of the brick grid: a float2 {min, max} per brick of 8 x 8 x 8 cells (neighbouring bricks share
+ * their boundary points; NaN ignored; an all-NaN brick holds {+inf, -inf}), ceil((n-1)/8) bricks per axis, z fastest.
+ * ia_volume_bricks writes it.  It depends on the volume only: reuse it for any level and any number of views.
+ */
+#define IA_RAYCAST_DENSE 1            /* flags bit 0: walk every cell (no brick skipping; bricks may be NULL).  Results are bit-equal. */
+
+int ia_raycast_scratch_bytes(int nx, int ny, int nz, size_t* h_bytes);
+int ia_volume_bricks(const float* volume, int nx, int ny, int nz, void* bricks, size_t bricks_bytes, void* stream);
+
+/*
+ * First hit of each ray with {field > level}: rays_o, rays_d [n_rays,3] (device; any camera model), n_rays > 0.
+ *   1. the ray o + t d is clipped to the lattice box [lo, lo + (n-1) step] and to t >= t_min; a ray that misses it (or has a zero
+ *      or non-finite direction) is a miss;
+ *   2. cells are walked in order by a 3-D DDA whose every plane crossing t is computed from the plane index directly;
+ *   3. a brick whose max <= level is skipped whole (exact: the trilinear interpolant is bounded by its corners);
+ *   4. a cell with a NaN corner, or with every corner <= level, has no surface;
+ *   5. within a cell the field along the ray is a cubic in t, split at the roots of its derivative into monotone pieces: the hit is
+ *      the first t where the field is > level (at the clipped start of the ray if it is inside already);
+ *   6. refined by 20 bisection steps on the cubic (bracket < 2e-6 cell); the bracket's midpoint is reported;
+ *   7. normal = -g/|g| (toward decreasing density, as the mesh is wound), 0 if |g| = 0: g = the trilinear interpolation at the hit of
+ *      the central-difference gradients at the cell's corners (one-sided at the border, divided by h_step per axis).
+ *   8. depth [n_rays] = t (the quantity of image_depth for unit directions), normal [n_rays,3], mask uint8 [n_rays]; a miss writes 0.
+ * bricks / bricks_bytes: the grid of ia_volume_bricks for this volume (ignored with IA_RAYCAST_DENSE).  No atomics and no host
+ * synchronisation: the output is a pure function of the inputs, the same with and without skipping and for any batching of rays.
+ */
+int ia_raycast_volume(const float* volume, int nx, int ny, int nz, const float* h_lo, const float* h_step, float level,
+                      const void* bricks, size_t bricks_bytes, const float* rays_o, const float* rays_d, int n_rays, float t_min,
+                      float* depth, float* normal, unsigned char* mask, int flags, void* stream);
+
+/*
+ * The gradient g of step 7 above at arbitrary points [n,3] (clamped into the box) -> grad [n,3]; -g/|g| are the vertex normals of
+ * the marching-cubes mesh of the same volume.  n >= 0.
+ */
+int ia_volume_gradient(const float* volume, int nx, int ny, int nz, const float* h_lo, const float* h_step, const float* points,
+                       int n, float* grad, void* stream);
 
 #ifdef __cplusplus
 }

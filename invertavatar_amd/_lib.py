@@ -102,6 +102,11 @@ _SIGNATURES = {
     'ia_mc_count': [c_void_p, c_int, c_int, c_int, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     'ia_mc_emit': [c_void_p, c_int, c_int, c_int, c_float, _f32p, _f32p, c_void_p, ctypes.c_size_t, c_void_p, c_int64, c_void_p, c_int64,
                    c_void_p],
+    'ia_raycast_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_volume_bricks': [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
+    'ia_raycast_volume': [c_void_p, c_int, c_int, c_int, _f32p, _f32p, c_float, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_float,
+                          c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    'ia_volume_gradient': [c_void_p, c_int, c_int, c_int, _f32p, _f32p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
 

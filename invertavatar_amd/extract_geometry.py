@@ -3,7 +3,10 @@
 For every seed: w = mapping(RandomState(seed).randn) with truncation (as the reenactment script draws it), the tri-planes under one mesh
 condition (the first frame of ``--drive_root`` in the reference's on-disk layout, or a synthetic frame), the density volume on a
 ``--res``^3 lattice over the rendering box, and the marching-cubes mesh of density > ``--level``, written as ``seed%04d.ply`` (binary
-PLY with per-vertex colours); ``--save-volume`` also writes the volume as ``seed%04d.npy``.  Runs on the device when there is one."""
+PLY with per-vertex colours, and with ``--normals`` vertex normals); ``--save-volume`` also writes the volume as ``seed%04d.npy``.
+``--views N --render-res R`` also renders the surface from N cameras of a yaw orbit (``LookAtPoseSampler`` at the rendering kwargs'
+camera radius and pivot) and writes the shaded views as 8-bit PNGs ``seed%04d_view%02d.png`` (``--save-depth``: the depth maps as
+``seed%04d_depth.npy``, [N,R,R]).  Runs on the device when there is one."""
 import argparse
 import os
 
@@ -12,12 +15,23 @@ import torch
 
 from . import geometry, synthetic
 from .reenact_avatar_next3d import FolderDrive, build_generator, parse_range, seed_latents
+from .training_avatar_texture.camera_utils import FOV_to_intrinsics, LookAtPoseSampler
 
 
 def mesh_condition(drive_root=None, device='cpu'):
     """{'uvcoords_image': [1,256,256,3]}: frame 0 of a drive directory, or synthetic frame 0."""
     uv = FolderDrive(drive_root)[0]['vert']['uvcoords_image'] if drive_root else synthetic.uv_conditions([0])
     return {'uvcoords_image': uv.to(device).float()}
+
+
+def orbit_cameras(G, n_views, fov_deg=18.837, device='cpu'):
+    """[n_views, 25] camera labels: a full yaw orbit (starting frontal) at the rendering kwargs' average radius about their pivot."""
+    pivot = torch.tensor(G.rendering_kwargs.get('avg_camera_pivot', [0, 0, 0]), dtype=torch.float32, device=device)
+    radius = G.rendering_kwargs.get('avg_camera_radius', 2.7)
+    intr = FOV_to_intrinsics(fov_deg, device=device).reshape(1, 9)
+    poses = [LookAtPoseSampler.sample(np.pi / 2 + 2 * np.pi * k / n_views, np.pi / 2, pivot, radius=radius, device=device)
+             for k in range(n_views)]
+    return torch.cat([torch.cat([p.reshape(1, 16), intr], 1) for p in poses], 0)
 
 
 def main(argv=None):
@@ -33,6 +47,10 @@ def main(argv=None):
     ap.add_argument('--outdir', required=True)
     ap.add_argument('--save-volume', action='store_true')
     ap.add_argument('--no-colors', action='store_true')
+    ap.add_argument('--normals', action='store_true', help='write vertex normals into the PLY')
+    ap.add_argument('--views', type=int, default=0, help='also render N shaded views of the surface (yaw orbit) as PNGs')
+    ap.add_argument('--render-res', type=int, default=512, help='pixels per side of the rendered views')
+    ap.add_argument('--save-depth', action='store_true', help='with --views: also write the depth maps as .npy')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -41,12 +59,25 @@ def main(argv=None):
     ws, _ = seed_latents(G, args.seeds, args.trunc, args.trunc_cutoff)
     results = []
     for seed, w in zip(args.seeds, ws):
-        out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors, noise_mode='const')[0]
+        out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
+                                 with_normals=args.normals, noise_mode='const')[0]
         path = os.path.join(args.outdir, f'seed{seed:04d}.ply')
-        geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'))
+        geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'), out.get('normals'))
         if args.save_volume:
             np.save(os.path.join(args.outdir, f'seed{seed:04d}.npy'), out['volume'].cpu().numpy())
         print(f'seed {seed}: {out["verts"].shape[0]} vertices, {out["faces"].shape[0]} triangles -> {path}')
+        if args.views > 0:
+            from PIL import Image
+            cams = orbit_cameras(G, args.views, device=args.device)[None]
+            views = G.render_geometry(w.float(), cams, mesh, resolution=args.render_res, volume_resolution=args.res, level=args.level,
+                                      noise_mode='const')
+            shaded = (views['shaded'][0, :, 0].clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
+            for k in range(args.views):
+                Image.fromarray(shaded[k], mode='L').save(os.path.join(args.outdir, f'seed{seed:04d}_view{k:02d}.png'))
+            if args.save_depth:
+                np.save(os.path.join(args.outdir, f'seed{seed:04d}_depth.npy'), views['depth'][0, :, 0].cpu().numpy())
+            out['views'] = views
+            print(f'seed {seed}: {args.views} views at {args.render_res}^2, {int(views["mask"].sum())} surface pixels')
         results.append((path, out))
     return results
 

@@ -11,7 +11,10 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
 - ``marching_cubes``: an indexed, welded, outward-wound triangle mesh of ``{volume > level}``.  Device tensors go to ``ia_mc_count`` +
   ``ia_mc_emit`` (one host read of the two totals in between); CPU tensors and NumPy arrays take a vectorised NumPy restatement of the
   same algorithm (same table, same vertex and triangle order, same fp32 vertex arithmetic).
-- ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy.
+- ``raycast``: first hit of rays with the surface of the trilinear field, with depth and normals.  Device tensors go to
+  ``ia_volume_bricks`` + ``ia_raycast_volume``; CPU tensors and NumPy arrays take a vectorised NumPy restatement (float64) of the same
+  algorithm.  ``volume_normals`` (``ia_volume_gradient``): unit normals at points, e.g. the mesh vertices; ``shade``: headlight Lambert.
+- ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
 axis and in fp32 with every operation rounded on its own, ``lo + i * step`` with ``lo = origin - 0.5 * L`` and ``step = L / (n - 1)``,
@@ -181,6 +184,207 @@ def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0
     return _mc_numpy(volume, level, org, spc)
 
 
+# ------------------------------------------------------------------ ray casting
+
+BRICK = 8               # cells per brick edge (csrc/raycast.hip kBrick)
+BISECT = 20             # bisection steps per hit (csrc/raycast.hip kRcBisect): bracket <= sqrt(3) * 2^-20 < 2e-6 cell
+
+
+def _bricks_numpy(v):
+    """NumPy restatement of ia_volume_bricks: [bx,by,bz,2] float32 {min, max} over 9^3-point bricks (NaN ignored; all NaN: +inf, -inf)."""
+    lo = hi = np.asarray(v, dtype=F32)
+    for a, n in enumerate(lo.shape):
+        starts = np.arange(0, n - 1, BRICK)
+        ends = np.minimum(starts + BRICK, n - 1)                 # the shared boundary plane of each brick
+        lo = np.fmin(np.fmin.reduceat(lo, starts, axis=a), np.take(lo, ends, axis=a))
+        hi = np.fmax(np.fmax.reduceat(hi, starts, axis=a), np.take(hi, ends, axis=a))
+    return np.stack([np.where(np.isnan(lo), np.inf, lo), np.where(np.isnan(hi), -np.inf, hi)], -1).astype(F32)
+
+
+def _point_grad(v, step, idx):
+    """Central-difference gradients [m,3] at lattice points idx [m,3] (one-sided at the border), divided by the step per axis."""
+    n = np.array(v.shape)
+    g = np.empty(idx.shape, dtype=np.float64)
+    for a in range(3):
+        lo_i, hi_i = idx.copy(), idx.copy()
+        lo_i[:, a] = np.maximum(idx[:, a] - 1, 0)
+        hi_i[:, a] = np.minimum(idx[:, a] + 1, n[a] - 1)
+        d = v[hi_i[:, 0], hi_i[:, 1], hi_i[:, 2]] - v[lo_i[:, 0], lo_i[:, 1], lo_i[:, 2]]
+        g[:, a] = d / ((hi_i[:, a] - lo_i[:, a]) * step[a])
+    return g
+
+
+def _cell_grad(v, step, c, u):
+    """Trilinear interpolation at local coordinates u [m,3] of cells c [m,3] of the gradients at the cells' 8 corners."""
+    g = np.zeros(u.shape, dtype=np.float64)
+    for q in range(8):
+        d = np.array([q & 1, (q >> 1) & 1, q >> 2])
+        w = np.prod(np.where(d[None, :] == 1, u, 1.0 - u), axis=1)
+        g += w[:, None] * _point_grad(v, step, c + d[None, :])
+    return g
+
+
+def _unit_neg(g):
+    nrm = np.linalg.norm(g, axis=-1, keepdims=True)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(nrm > 0, -g / nrm, 0.0)
+
+
+def _cubic_first_hit(c0, c1, c2, c3, L):
+    """First s in [0, L] with ((c3 s + c2) s + c1) s + c0 > 0 (c0 already minus the level), or -1: monotone pieces between the roots of
+    the derivative, then BISECT bisection steps on the first piece whose end is inside (csrc/raycast.hip cubic_first_hit)."""
+    f = lambda s: ((c3 * s + c2) * s + c1) * s + c0            # noqa: E731
+    A, B, C = 3.0 * c3, 2.0 * c2, c1
+    r0, r1 = np.full_like(c0, -1.0), np.full_like(c0, -1.0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        lin = (A == 0) & (B != 0)
+        r0 = np.where(lin, -C / np.where(lin, B, 1.0), r0)
+        disc = B * B - 4.0 * A * C
+        quad = (A != 0) & (disc > 0)
+        q = -0.5 * (B + np.copysign(np.sqrt(np.where(quad, disc, 0.0)), B))
+        qa, qb = q / np.where(quad, A, 1.0), np.where(q != 0, C / np.where(q != 0, q, 1.0), -1.0)
+        r0, r1 = np.where(quad, np.minimum(qa, qb), r0), np.where(quad, np.maximum(qa, qb), r1)
+    br = [np.where((r > 0) & (r < L), r, np.nan) for r in (r0, r1)] + [L]
+    s = np.where(c0 > 0, 0.0, -1.0)
+    a = np.zeros_like(c0)
+    for b in br:
+        valid = ~np.isnan(b)
+        take = valid & (s < 0) & (f(np.where(valid, b, 0.0)) > 0)
+        lo, hi = a[take], b[take]
+        cc = [x[take] for x in (c0, c1, c2, c3)]
+        for _ in range(BISECT):
+            mid = 0.5 * (lo + hi)
+            inside = ((cc[3] * mid + cc[2]) * mid + cc[1]) * mid + cc[0] > 0
+            hi, lo = np.where(inside, mid, hi), np.where(inside, lo, mid)
+        s[take] = 0.5 * (lo + hi)
+        a = np.where(valid, b, a)
+    return s
+
+
+def _raycast_numpy(vol, level, lo, step, ro, rd, t_min):
+    """NumPy restatement of ia_raycast_volume (float64 arithmetic; every cell is walked, which the brick skip of the kernel does not
+    change): (depth [R], normal [R,3], mask bool [R])."""
+    v = np.asarray(vol, dtype=F32).astype(np.float64)
+    n = np.array(v.shape)
+    level = float(F32(level))
+    lo, step = np.array(lo, dtype=F32).astype(np.float64), np.array(step, dtype=F32).astype(np.float64)
+    ro, rd = np.asarray(ro, dtype=F32).astype(np.float64).reshape(-1, 3), np.asarray(rd, dtype=F32).astype(np.float64).reshape(-1, 3)
+    R = ro.shape[0]
+    depth, normal, mask = np.zeros(R), np.zeros((R, 3)), np.zeros(R, dtype=bool)
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        O, D = (ro - lo) / step, rd / step
+        ok = np.isfinite(O).all(1) & np.isfinite(D).all(1) & (D != 0).any(1)
+        # 1. clip to the box and to t >= t_min
+        top = (n - 1).astype(np.float64)
+        ta, tb = -O / D, (top - O) / D
+        par = D == 0
+        t0 = np.maximum(float(t_min), np.where(par, -np.inf, np.minimum(ta, tb)).max(1))
+        t1 = np.where(par, np.inf, np.maximum(ta, tb)).min(1)
+        ok &= np.where(par, (O >= 0) & (O <= top), True).all(1) & (t0 <= t1)
+        idx = np.flatnonzero(ok)
+        O, D, t0, t1 = O[idx], D[idx], t0[idx], t1[idx]
+        c = np.clip(np.floor(O + t0[:, None] * D), 0, n - 2).astype(np.int64)
+    tc = t0.copy()
+    sgn = np.where(D > 0, 1, -1)
+    for _ in range(int(n.sum())):
+        if idx.size == 0:
+            break
+        # 2. this cell spans [tc, te]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            tn = np.where(D > 0, (c + 1 - O) / D, np.where(D < 0, (c - O) / D, np.inf))
+        ax = np.argmin(tn, 1)                                         # ties: the lower axis
+        to = tn[np.arange(idx.size), ax]
+        te = np.maximum(np.minimum(to, t1), tc)
+        cv = np.stack([v[c[:, 0] + (q & 1), c[:, 1] + ((q >> 1) & 1), c[:, 2] + (q >> 2)] for q in range(8)], 1)
+        nan = np.isnan(cv).any(1)
+        cand = np.flatnonzero(~nan & (np.where(nan[:, None], -np.inf, cv).max(1) > level))
+        hit = np.zeros(idx.size, dtype=bool)
+        if cand.size:
+            # 4-5. the cubic of the trilinear field along the ray, in s = t - tc
+            w = cv[cand]
+            k1, k2, k3 = w[:, 1] - w[:, 0], w[:, 2] - w[:, 0], w[:, 4] - w[:, 0]
+            k4, k5, k6 = w[:, 3] - w[:, 1] - w[:, 2] + w[:, 0], w[:, 5] - w[:, 1] - w[:, 4] + w[:, 0], w[:, 6] - w[:, 2] - w[:, 4] + w[:, 0]
+            k7 = w[:, 7] - w[:, 3] - w[:, 5] - w[:, 6] + w[:, 1] + w[:, 2] + w[:, 4] - w[:, 0]
+            u = O[cand] + tc[cand, None] * D[cand] - c[cand]
+            bu, bv, bw = D[cand, 0], D[cand, 1], D[cand, 2]
+            u0, v0, w0 = u[:, 0], u[:, 1], u[:, 2]
+            c3 = k7 * bu * bv * bw
+            c2 = k4 * bu * bv + k5 * bu * bw + k6 * bv * bw + k7 * (u0 * bv * bw + v0 * bu * bw + w0 * bu * bv)
+            c1 = (k1 * bu + k2 * bv + k3 * bw + k4 * (u0 * bv + v0 * bu) + k5 * (u0 * bw + w0 * bu) + k6 * (v0 * bw + w0 * bv)
+                  + k7 * (u0 * v0 * bw + u0 * w0 * bv + v0 * w0 * bu))
+            c0 = w[:, 0] + k1 * u0 + k2 * v0 + k3 * w0 + k4 * u0 * v0 + k5 * u0 * w0 + k6 * v0 * w0 + k7 * u0 * v0 * w0 - level
+            s = _cubic_first_hit(c0, c1, c2, c3, te[cand] - tc[cand])
+            h = s >= 0
+            if h.any():
+                hc = cand[h]
+                rays = idx[hc]
+                depth[rays] = tc[hc] + s[h]
+                mask[rays] = True
+                # 7. normal from the interpolated corner gradients
+                normal[rays] = _unit_neg(_cell_grad(v, step, c[hc], u[h] + s[h, None] * D[hc]))
+                hit[hc] = True
+        # step to the next cell; a ray ends at its hit, at the box exit or when it leaves the lattice
+        r = np.arange(idx.size)
+        c[r, ax] += sgn[r, ax]
+        keep = ~hit & (to < t1) & (c[r, ax] >= 0) & (c[r, ax] <= n[ax] - 2)
+        idx, O, D, t1, c, sgn, tc = idx[keep], O[keep], D[keep], t1[keep], c[keep], sgn[keep], te[keep]
+    return depth, normal, mask
+
+
+def _as_out(x, like, dtype=None):
+    """A NumPy result in the container of ``like``: a CPU torch tensor for a tensor, NumPy otherwise."""
+    x = x.astype(dtype or F32)
+    return torch.from_numpy(x) if isinstance(like, torch.Tensor) else x
+
+
+def raycast(volume, level, origin, spacing, rays_o, rays_d, t_min=0.0, skip=True):
+    """First hit of rays [..., 3] with the surface {volume > level} of the trilinear field: {'depth' [...], 'mask' bool [...],
+    'normal' [..., 3]}.  ``origin`` / ``spacing`` are the coordinates of point (0,0,0) and the lattice step per axis (the arguments of
+    ``marching_cubes``).  ``depth`` is the ray parameter t (world distance for unit directions), ``normal`` points toward decreasing
+    density; misses are 0.  Device tensors run on ia_volume_bricks + ia_raycast_volume (``skip``: jump over bricks with max <= level,
+    which changes no result); CPU tensors and NumPy arrays take the NumPy restatement."""
+    org, spc = _vec3(origin), _vec3(spacing)
+    lead = tuple(rays_o.shape[:-1])
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        from . import hipops
+        vol = volume.float().contiguous()
+        bricks = hipops.volume_bricks(vol) if skip else None
+        depth, normal, mask = hipops.raycast_volume(vol, float(level), org, spc, rays_o.float().reshape(-1, 3).contiguous(),
+                                                    rays_d.float().reshape(-1, 3).contiguous(), t_min, bricks)
+        return {'depth': depth.reshape(lead), 'mask': mask.reshape(lead), 'normal': normal.reshape(lead + (3,))}
+    if volume.ndim != 3 or min(volume.shape) < 2:
+        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
+    depth, normal, mask = _raycast_numpy(_np(volume), level, org, spc, _np(rays_o), _np(rays_d), t_min)
+    return {'depth': _as_out(depth.reshape(lead), rays_o), 'mask': _as_out(mask.reshape(lead), rays_o, bool),
+            'normal': _as_out(normal.reshape(lead + (3,)), rays_o)}
+
+
+def volume_normals(volume, verts, origin, spacing):
+    """Unit normals [V,3] at points (the marching-cubes vertices of the same volume): -g/|g| of the interpolated central-difference
+    gradient (0 where g = 0), pointing toward decreasing density as the mesh is wound.  Device tensors run on ia_volume_gradient."""
+    org, spc = _vec3(origin), _vec3(spacing)
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        from . import hipops
+        g = hipops.volume_gradient(volume.float().contiguous(), org, spc, verts.float().reshape(-1, 3).contiguous())
+        nrm = g.norm(dim=-1, keepdim=True)
+        return torch.where(nrm > 0, -g / nrm.clamp_min(1e-30), torch.zeros_like(g))
+    v = np.asarray(_np(volume), dtype=F32).astype(np.float64)
+    n = np.array(v.shape)
+    lo, step = np.array(org, dtype=F32).astype(np.float64), np.array(spc, dtype=F32).astype(np.float64)
+    p = np.asarray(_np(verts), dtype=F32).astype(np.float64).reshape(-1, 3)
+    P = np.fmin(np.fmax((p - lo) / step, 0.0), n - 1)                 # fmax drops a NaN, as fmaxf does
+    c = np.minimum(np.floor(P).astype(np.int64), n - 2)
+    return _as_out(_unit_neg(_cell_grad(v, step, c, P - c)), verts)
+
+
+def shade(normal, rays_d, mask, ambient=0.25):
+    """Headlight Lambert shading in [0, 1]: [..., 1] = mask * (ambient + (1 - ambient) * max(0, n . -d)), d normalised."""
+    normal, rays_d, mask = (torch.as_tensor(x) for x in (normal, rays_d, mask))
+    d = torch.nn.functional.normalize(rays_d.float(), dim=-1)
+    lam = (-(normal.float() * d).sum(-1, keepdim=True)).clamp(0, 1)
+    return (ambient + (1.0 - ambient) * lam) * mask[..., None].float()
+
+
 # ------------------------------------------------------------------ generator-level helpers
 
 def generator_planes(G, ws, mesh_condition, update_emas=False, **synthesis_kwargs):
@@ -205,15 +409,20 @@ def _np(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
 
-def write_ply(path, verts, faces, colors=None):
-    """Binary little-endian PLY: float x, y, z (+ uchar red, green, blue) per vertex, int32 index triples per face."""
+def write_ply(path, verts, faces, colors=None, normals=None):
+    """Binary little-endian PLY: float x, y, z (+ float nx, ny, nz) (+ uchar red, green, blue) per vertex, int32 index triples per face."""
     v = _np(verts).astype('<f4').reshape(-1, 3)
     f = _np(faces).astype('<i4').reshape(-1, 3)
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    if normals is not None:
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
     if colors is not None:
         fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
     vrec = np.empty(v.shape[0], dtype=fields)
     vrec['x'], vrec['y'], vrec['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        nrm = _np(normals).astype('<f4').reshape(-1, 3)
+        vrec['nx'], vrec['ny'], vrec['nz'] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         c = _np(colors).astype(np.uint8).reshape(-1, 3)
         vrec['red'], vrec['green'], vrec['blue'] = c[:, 0], c[:, 1], c[:, 2]
@@ -221,6 +430,8 @@ def write_ply(path, verts, faces, colors=None):
     frec['n'], frec['i'] = 3, f
     head = ['ply', 'format binary_little_endian 1.0', f'element vertex {v.shape[0]}', 'property float x', 'property float y',
             'property float z']
+    if normals is not None:
+        head += ['property float nx', 'property float ny', 'property float nz']
     if colors is not None:
         head += ['property uchar red', 'property uchar green', 'property uchar blue']
     head += [f'element face {f.shape[0]}', 'property list uchar int vertex_indices', 'end_header']
@@ -230,18 +441,23 @@ def write_ply(path, verts, faces, colors=None):
         fh.write(frec.tobytes())
 
 
-def read_ply(path):
-    """Inverse of ``write_ply``: (verts float32 [V,3], faces int64 [F,3], colors uint8 [V,3] or None)."""
+def read_ply(path, with_normals=False):
+    """Inverse of ``write_ply``: (verts float32 [V,3], faces int64 [F,3], colors uint8 [V,3] or None), and with ``with_normals`` a
+    fourth item, normals float32 [V,3] or None."""
     with open(path, 'rb') as fh:
         data = fh.read()
     end = data.index(b'end_header\n') + len(b'end_header\n')
     head = data[:end].decode('ascii').split('\n')
     nv = int(next(h for h in head if h.startswith('element vertex')).split()[-1])
     nf = int(next(h for h in head if h.startswith('element face')).split()[-1])
-    has_col = 'property uchar red' in head
-    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')] + ([('red', 'u1'), ('green', 'u1'), ('blue', 'u1')] if has_col else [])
+    has_col, has_nrm = 'property uchar red' in head, 'property float nx' in head
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')] + ([('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')] if has_nrm else [])
+    fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')] if has_col else []
     vrec = np.frombuffer(data, dtype=fields, count=nv, offset=end)
     frec = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=end + vrec.nbytes)
     verts = np.stack([vrec['x'], vrec['y'], vrec['z']], -1).astype(np.float32)
     cols = np.stack([vrec['red'], vrec['green'], vrec['blue']], -1) if has_col else None
-    return verts, frec['i'].astype(np.int64), cols
+    if not with_normals:
+        return verts, frec['i'].astype(np.int64), cols
+    nrm = np.stack([vrec['nx'], vrec['ny'], vrec['nz']], -1).astype(np.float32) if has_nrm else None
+    return verts, frec['i'].astype(np.int64), cols, nrm

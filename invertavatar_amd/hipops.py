@@ -1375,3 +1375,67 @@ def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0
                                 _p(verts), n_verts, _p(faces), n_faces, stream)
         _lib.check(st, 'ia_mc_emit')
     return verts, faces
+
+
+def _volume_checked(volume):
+    _f32c(volume, 'volume')
+    if volume.dim() != 3:
+        raise RuntimeError(f'volume must be [nx,ny,nz], got {tuple(volume.shape)}')
+    return tuple(int(n) for n in volume.shape)
+
+
+def _rays_checked(t, what, device):
+    _f32c(t, what)
+    if t.dim() != 2 or t.shape[1] != 3 or t.device != device:
+        raise RuntimeError(f'{what} must be [n,3] on {device}, got {tuple(t.shape)} on {t.device}')
+    return t.shape[0]
+
+
+def volume_bricks(volume):
+    """{min, max} per brick of 8^3 cells (see ia_volume_bricks): volume [nx,ny,nz] -> [bx,by,bz,2] float32."""
+    nx, ny, nz = _volume_checked(volume)
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_raycast_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_raycast_scratch_bytes')
+    dev = volume.device
+    bricks = torch.empty((nx + 6) // 8, (ny + 6) // 8, (nz + 6) // 8, 2, device=dev)
+    assert bricks.numel() * 4 == nbytes.value
+    with torch.cuda.device(dev), _Timed('volume_bricks', 0.0, 4.0 * volume.numel(), f'{nx}x{ny}x{nz}'):
+        st = lib.ia_volume_bricks(_p(volume), nx, ny, nz, _p(bricks), nbytes.value, _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_volume_bricks')
+    return bricks
+
+
+def raycast_volume(volume, level, lo, step, rays_o, rays_d, t_min=0.0, bricks=None):
+    """First hit of each ray with {volume > level} (see ia_raycast_volume): rays [n,3] -> (depth [n], normal [n,3], mask bool [n]).
+    With ``bricks`` (from ``volume_bricks``) empty bricks are skipped; without, every cell is walked.  The results are the same."""
+    nx, ny, nz = _volume_checked(volume)
+    dev = volume.device
+    n = _rays_checked(rays_o, 'rays_o', dev)
+    if _rays_checked(rays_d, 'rays_d', dev) != n:
+        raise RuntimeError(f'rays_o and rays_d differ in length: {n} vs {rays_d.shape[0]}')
+    if bricks is not None:
+        _f32c(bricks, 'bricks')
+    depth = torch.empty(n, device=dev)
+    normal = torch.empty(n, 3, device=dev)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return depth, normal, mask.bool()
+    with torch.cuda.device(dev), _Timed('raycast_volume', 0.0, 40.0 * n, f'{nx}x{ny}x{nz} rays={n}'):
+        st = _lib.load().ia_raycast_volume(_p(volume), nx, ny, nz, _f3(lo), _f3(step), float(level), _p(bricks),
+                                           0 if bricks is None else bricks.numel() * 4, _p(rays_o), _p(rays_d), n, float(t_min),
+                                           _p(depth), _p(normal), _p(mask), 1 if bricks is None else 0, _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_raycast_volume')
+    return depth, normal, mask.view(torch.bool)
+
+
+def volume_gradient(volume, lo, step, points):
+    """Interpolated central-difference gradient of the volume at points [n,3] (see ia_volume_gradient) -> [n,3]."""
+    nx, ny, nz = _volume_checked(volume)
+    dev = volume.device
+    n = _rays_checked(points, 'points', dev)
+    grad = torch.empty(n, 3, device=dev)
+    with torch.cuda.device(dev), _Timed('volume_gradient', 0.0, 24.0 * n, f'{nx}x{ny}x{nz} points={n}'):
+        st = _lib.load().ia_volume_gradient(_p(volume), nx, ny, nz, _f3(lo), _f3(step), _p(points), n, _p(grad), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_volume_gradient')
+    return grad

@@ -535,11 +535,12 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         **synthesis_kwargs):
+                         with_normals=False, **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
-        'colors' uint8 [V,3] (the decoder's rgb[:3] at the vertices).  ``level`` = 10 is the EG3D-family shape threshold: a knob, not a
+        'colors' uint8 [V,3] (the decoder's rgb[:3] at the vertices) and, with ``with_normals``, 'normals' float32 [V,3]
+        (``geometry.volume_normals``: unit, toward decreasing density).  ``level`` = 10 is the EG3D-family shape threshold: a knob, not a
         constant of the model.  The planes are computed once per call; device tensors stay on the device throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
@@ -554,7 +555,52 @@ class TriPlaneGenerator(torch.nn.Module):
             item = {'volume': volume[b], 'verts': verts, 'faces': faces}
             if with_colors:
                 item['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, verts, box_warp)
+            if with_normals:
+                item['normals'] = geometry.volume_normals(volume[b], verts, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
             out.append(item)
+        return out
+
+    @torch.no_grad()
+    def render_geometry(self, ws, c, mesh_condition, resolution=512, volume_resolution=256, level=10.0, cube_length=None, with_colors=False,
+                        **synthesis_kwargs):
+        """Surface renders of the avatar's shape from the cameras ``c`` ([B,25] or [B,V,25]): per identity the density volume of
+        ``extract_geometry`` (``volume_resolution``^3 over ``cube_length``, default box_warp) and the first hit of every camera ray
+        (``geometry.raycast``; rays of the generator's ray sampler, so pixels align with ``image_depth`` at the same resolution) with
+        {density > level}, all views of an identity in one launch.  Returns NCHW 'depth' [B(,V),1,H,W] (ray parameter; 0 on a miss),
+        'mask' bool [B(,V),1,H,W], 'normal' [B(,V),3,H,W] (unit, toward decreasing density), 'shaded' [B(,V),1,H,W] (headlight
+        Lambert, ``geometry.shade``) and, with ``with_colors``, 'rgb' [B(,V),3,H,W] (the decoder's rgb[:3] at the hit points, 0 on a
+        miss)."""
+        from .. import geometry
+        single = c.dim() == 2
+        cams = c[:, None] if single else c
+        B, V = cams.shape[:2]
+        if ws.shape[0] != B:
+            raise ValueError(f'ws has batch {ws.shape[0]} but c has {B}')
+        box_warp = self.rendering_kwargs['box_warp']
+        length = box_warp if cube_length is None else cube_length
+        planes = geometry.generator_planes(self, ws, mesh_condition, **synthesis_kwargs)
+        volume = geometry.density_volume(planes, self.decoder, volume_resolution, length, (0, 0, 0), box_warp)
+        res, ls = geometry._res3(volume_resolution), geometry._vec3(length)
+        axes = [geometry.lattice_axis(n, ls[a], 0.0) for a, n in enumerate(res)]
+        lo, step = [float(a[1]) for a in axes], [float(a[2]) for a in axes]
+        cam = cams.reshape(B * V, 25).float()
+        rays_o, rays_d = self.ray_sampler(cam[:, :16].view(-1, 4, 4), cam[:, 16:25].view(-1, 3, 3), resolution)
+        rays_o, rays_d = rays_o.reshape(B, V * resolution * resolution, 3), rays_d.reshape(B, V * resolution * resolution, 3)
+        outs = []
+        for b in range(B):
+            hit = geometry.raycast(volume[b], level, lo, step, rays_o[b], rays_d[b])
+            hit['shaded'] = geometry.shade(hit['normal'], rays_d[b], hit['mask'])
+            if with_colors:
+                pts = (rays_o[b] + hit['depth'][:, None] * rays_d[b])[None]
+                rgb = geometry.query_planes(planes[b:b + 1], self.decoder, pts, box_warp, rgb=True)['rgb'][0, :, :3]
+                hit['rgb'] = rgb * hit['mask'][:, None]
+            outs.append(hit)
+        lead = (B,) if single else (B, V)
+        out = {}
+        for k in outs[0]:
+            x = torch.stack([o[k] for o in outs])
+            x = x.reshape(B * V, resolution, resolution, -1).permute(0, 3, 1, 2)
+            out[k] = x.reshape(lead + x.shape[1:])
         return out
 
     def forward(self, z, c, v, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None, update_emas=False,

@@ -857,6 +857,30 @@ int ia_raycast_volume(const float* volume, int nx, int ny, int nz, const float* 
 int ia_volume_gradient(const float* volume, int nx, int ny, int nz, const float* h_lo, const float* h_step, const float* points,
                        int n, float* grad, void* stream);
 
+/*
+ * Per-frame image metrics (csrc/image_metrics.hip).  Replaces, for evaluation, ssim / msssim of encoder_inversion/criteria/ms_ssim.py
+ * (size_average=False, no `normalize`): 11-tap Gaussian window (sigma 1.5), "valid" correlation, per channel, L = data_range,
+ *     mu1 = G*a, mu2 = G*b, s1 = G*(a*a) - mu1^2, s2 = G*(b*b) - mu2^2, s12 = G*(a*b) - mu1*mu2, C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+ *     cs_map = (2 s12 + C2) / (s1 + s2 + C2),  ssim_map = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs_map,
+ * ssim_k[n], cs_k[n] = their means over (c, y, x) at level k; level k + 1 = 2 x 2 average pool (floor) of level k;
+ * ms_ssim[n] = prod_{k<4} cs_k^w_k * ssim_4^w_4, w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) (a negative mean gives NaN, as in the
+ * reference); mse[n], l1[n] = means of (a-b)^2, |a-b| over all pixels of level 0; psnr = 10 log10(L^2 / mse) (+inf for mse = 0).
+ *   a, b    : IA_IMAGE_F32_NCHW: float [n,c,h,w];  IA_IMAGE_U8_NHWC: uint8 [n,h,w,c], converted on load (values 0..255)
+ *   c in 1..4, levels in 1..5, min(h, w) >> (levels - 1) >= 11 (smaller images are refused; the reference shrinks its window instead)
+ *   scratch : ia_image_metrics_scratch_bytes(n, c, h, w, levels) bytes, 8-byte aligned (host arithmetic only): the tiles' partial sums
+ *             (doubles) and the pooled image pairs of levels 1..levels-1
+ *   out     : float [n, 5 + 2 * levels]: mse, l1, psnr, ssim (= ssim_0), ms_ssim, ssim_0 .. ssim_{levels-1}, cs_0 .. cs_{levels-1}.
+ *             MS-SSIM is defined on five levels only: with levels < 5 the column ms_ssim holds NaN (it is not a copy of ssim).
+ * `levels` launches + one finalising launch whatever n is; no atomics: the same inputs give the same bits, and a frame's results do
+ * not depend on the batch it is part of.  Invalid arguments return IA_ERR_INVALID_ARG before anything is launched.
+ */
+#define IA_IMAGE_F32_NCHW 0
+#define IA_IMAGE_U8_NHWC 1
+
+int ia_image_metrics_scratch_bytes(int n, int c, int h, int w, int levels, size_t* h_bytes);
+int ia_image_metrics(const void* a, const void* b, int layout, int n, int c, int h, int w, float data_range, int levels,
+                     void* scratch, size_t scratch_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -325,12 +325,14 @@ def _drive_graph(net, ws, results, batch, nrr):
 
 
 @torch.no_grad()
-def drive_sequence(net, ws, results, cams, uvcoords, jitter=None, batch=1, gt=None, neural_rendering_resolution=None, graphed=None):
+def drive_sequence(net, ws, results, cams, uvcoords, jitter=None, batch=1, gt=None, neural_rendering_resolution=None, graphed=None, metrics=None):
     """Drive loop (:206-219) over cams [F,25] / uvcoords [F,256,256,3] in calls of `batch` frames (the script uses 1; with
     batch > 1 every frame keeps the depth range of its own call: per-frame `ray_dist`, frame_parallel.per_frame_ray_dist).
     `graphed`: None = the default (DRIVE_GRAPHS: device tensors, batch 1, >= DRIVE_GRAPH_MIN_FRAMES frames -> captured calls, see above),
     True / False force it.  Returns (images [F,3,H,W], mosaics or None): mosaics are the uint8 [gt | rendered] pictures when `gt`
-    [F,3,H,W] is given."""
+    [F,3,H,W] is given.  `metrics`: an image_metrics.ClipMetrics; with `gt`, every call's images are scored against their ground truth
+    right after they are produced (on the device, outside the captured graph, no host synchronisation) -- read them with
+    ``metrics.summary()``.  The images and the return value are the same with and without it."""
     from .frame_parallel import per_frame_ray_dist
     from .reenact_avatar_next3d import _check_split_range
     g = net.generator
@@ -341,6 +343,8 @@ def drive_sequence(net, ws, results, cams, uvcoords, jitter=None, batch=1, gt=No
         if gt is not None:
             for k in range(images.shape[0]):
                 mosaics.append(layout_grid(torch.cat([gt[lo + k:lo + k + 1, :3], images[k:k + 1]], dim=0), grid_w=2, grid_h=1))
+            if metrics is not None:
+                metrics.update(images, gt[lo:lo + images.shape[0], :3])
     _check_split_range(net, start=True)
     use_graphs = graphed if graphed is not None else (DRIVE_GRAPHS and n >= DRIVE_GRAPH_MIN_FRAMES)
     if use_graphs and batch == 1 and cams.is_cuda and not torch.is_grad_enabled():

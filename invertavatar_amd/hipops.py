@@ -1439,3 +1439,32 @@ def volume_gradient(volume, lo, step, points):
         st = _lib.load().ia_volume_gradient(_p(volume), nx, ny, nz, _f3(lo), _f3(step), _p(points), n, _p(grad), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_volume_gradient')
     return grad
+
+
+IMAGE_LAYOUT_F32_NCHW, IMAGE_LAYOUT_U8_NHWC = 0, 1
+
+
+def image_metrics(a, b, data_range, levels=5):
+    """Per-frame mse, l1, psnr, ssim, ms_ssim, ssim_0.., cs_0.. of two image batches (see ia_image_metrics): float32 [N,C,H,W] or
+    uint8 [N,H,W,C] contiguous device tensors of the same shape -> float32 [N, 5 + 2 * levels].  `levels` + 1 launches, no atomics."""
+    if not (a.is_cuda and b.is_cuda and a.device == b.device and a.is_contiguous() and b.is_contiguous()):
+        raise RuntimeError('image_metrics: a and b must be contiguous tensors on the same device')
+    if a.dtype != b.dtype or a.dtype not in (torch.float32, torch.uint8) or a.shape != b.shape or a.dim() != 4:
+        raise RuntimeError(f'image_metrics: float32 [N,C,H,W] or uint8 [N,H,W,C] pairs, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}')
+    if a.dtype == torch.uint8:
+        layout, (n, h, w, c) = IMAGE_LAYOUT_U8_NHWC, a.shape
+    else:
+        layout, (n, c, h, w) = IMAGE_LAYOUT_F32_NCHW, a.shape
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_image_metrics_scratch_bytes(n, c, h, w, int(levels), ctypes.byref(nbytes)), 'ia_image_metrics_scratch_bytes')
+    dev = a.device
+    scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(n, 5 + 2 * int(levels), device=dev)
+    pixels = float(a.numel())
+    with torch.cuda.device(dev), _Timed('image_metrics', 400.0 * pixels, 2.0 * a.element_size() * pixels * (1.0 + 1.0 / 3.0 if levels > 1 else 1.0),
+                                        f'{n}x{c}x{h}x{w} levels={levels}'):
+        st = lib.ia_image_metrics(_p(a), _p(b), layout, n, c, h, w, float(data_range), int(levels), _p(scratch), scratch.numel() * 8,
+                                  _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_image_metrics')
+    return out

@@ -881,6 +881,49 @@ int ia_image_metrics_scratch_bytes(int n, int c, int h, int w, int levels, size_
 int ia_image_metrics(const void* a, const void* b, int layout, int n, int c, int h, int w, float data_range, int levels,
                      void* scratch, size_t scratch_bytes, float* out, void* stream);
 
+/*
+ * Connected components (csrc/components.hip; no counterpart in the reference): which parts of {volume > level} hang together, how
+ * large they are, and a filter that drops the unwanted ones before the volume is meshed or ray-cast.  The lattice and inside rule are
+ * those of marching cubes and ray casting: point (i,j,k) of an [nx,ny,nz] fp32 volume (x slowest) is inside iff v > level (NaN:
+ * outside).  Each dimension >= 2, nx * ny * nz < 2^31 (otherwise IA_ERR_INVALID_ARG).
+ *   connectivity : 26 (indices differ by at most 1 on every axis) or 6 (by exactly 1 on one axis); anything else is refused
+ *   labels       : int32 [nx,ny,nz]; 0 outside; components 1..K numbered in increasing order of their smallest linear index
+ *                  (i * ny + j) * nz + k
+ *   scratch      : ia_components_scratch_bytes bytes (4 per point + 4 per 1024 points), 4-byte aligned; nothing in it survives a call
+ *   count        : device int[1] = K; the caller reads it (one host synchronisation) before it sizes `stats`
+ * Union-find whose roots are smallest indices (8 x 8 x 64 tiles in LDS, then the tile seams with agent-scope integer atomic min on
+ * the parent array, then numbering by a scan): the result does not depend on the order in which the atomics land, so labels are
+ * bit-reproducible.  Every loop is lock-free and strictly descending: no workgroup ever waits for another one.
+ *
+ * ia_component_stats: stats int32 [K,8], row c-1 for label c: point count, smallest linear index, then the inclusive index bounding
+ * box imin, jmin, kmin, imax, jmax, kmax (integer atomic add / min / max: bit-reproducible).  K: the count read above; K < 0 or
+ * K > nx*ny*nz is refused, K = 0 launches nothing, and labels outside 1..K are ignored (never written through).
+ *
+ * ia_volume_keep: out[p] = fill where labels[p] is in 1..K and keep_flags[labels[p]] == 0, else volume[p] (bit copy); points of label
+ * 0 are never modified.  keep_flags: device uint8 [K+1] ([0] ignored); n = number of points; out may alias volume.  fill = level
+ * makes the dropped points outside for marching cubes and ray casting at that level.
+ */
+int ia_components_scratch_bytes(int nx, int ny, int nz, size_t* h_bytes);
+int ia_volume_components(const float* volume, int nx, int ny, int nz, float level, int connectivity, int* labels, void* scratch,
+                         size_t scratch_bytes, int* count, void* stream);
+int ia_component_stats(const int* labels, int nx, int ny, int nz, int K, int* stats, void* stream);
+int ia_volume_keep(const float* volume, const int* labels, int64_t n, const unsigned char* keep_flags, int K, float fill, float* out,
+                   void* stream);
+
+/*
+ * The same labelling for an indexed triangle mesh: vertices a, b are connected if some face contains both.
+ *   faces       : int32 [F,3] (a face with an index outside [0, V) is ignored); 3 F < 2^31
+ *   vert_labels : int32 [V], components 1..K in increasing order of their smallest vertex index; a vertex used by no face is a
+ *                 component of its own
+ *   scratch     : ia_mesh_components_scratch_bytes(V) bytes;  count : device int[1] = K
+ * ia_mesh_component_stats: stats int32 [K,3], row c-1: vertex count, face count (a face belongs to the component of its first
+ * vertex), smallest vertex index.
+ */
+int ia_mesh_components_scratch_bytes(int V, size_t* h_bytes);
+int ia_mesh_components(const int* faces, int64_t F, int V, int* vert_labels, void* scratch, size_t scratch_bytes, int* count,
+                       void* stream);
+int ia_mesh_component_stats(const int* faces, int64_t F, int V, const int* vert_labels, int K, int* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

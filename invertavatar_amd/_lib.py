@@ -109,6 +109,13 @@ _SIGNATURES = {
     'ia_volume_gradient': [c_void_p, c_int, c_int, c_int, _f32p, _f32p, c_void_p, c_int, c_void_p, c_void_p],
     'ia_image_metrics_scratch_bytes': [c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
     'ia_image_metrics': [c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_components_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_volume_components': [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_component_stats': [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    'ia_volume_keep': [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p],
+    'ia_mesh_components_scratch_bytes': [c_int, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_mesh_components': [c_void_p, c_int64, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_mesh_component_stats': [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p],
 }
 
 

@@ -6,7 +6,10 @@ condition (the first frame of ``--drive_root`` in the reference's on-disk layout
 PLY with per-vertex colours, and with ``--normals`` vertex normals); ``--save-volume`` also writes the volume as ``seed%04d.npy``.
 ``--views N --render-res R`` also renders the surface from N cameras of a yaw orbit (``LookAtPoseSampler`` at the rendering kwargs'
 camera radius and pivot) and writes the shaded views as 8-bit PNGs ``seed%04d_view%02d.png`` (``--save-depth``: the depth maps as
-``seed%04d_depth.npy``, [N,R,R]).  Runs on the device when there is one."""
+``seed%04d_depth.npy``, [N,R,R]).  ``--keep largest`` (or ``--keep N``) removes the detached components of {density > level} from the
+volume first, so the PLY, the views and the saved depth show the N largest only; ``--min-voxels M`` also drops kept components of fewer
+than M lattice points; a line per seed reports how many components there were and the sizes of the kept ones.  Runs on the device when
+there is one."""
 import argparse
 import os
 
@@ -34,6 +37,19 @@ def orbit_cameras(G, n_views, fov_deg=18.837, device='cpu'):
     return torch.cat([torch.cat([p.reshape(1, 16), intr], 1) for p in poses], 0)
 
 
+def parse_keep(s):
+    """'largest' or a positive integer (the number of largest components to keep)."""
+    if s == 'largest':
+        return s
+    try:
+        n = int(s)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"--keep takes 'largest' or an integer >= 1, got {s!r}")
+    return n
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Density volumes and meshes of tri-plane avatars')
     ap.add_argument('--seeds', type=parse_range, required=True)
@@ -51,6 +67,8 @@ def main(argv=None):
     ap.add_argument('--views', type=int, default=0, help='also render N shaded views of the surface (yaw orbit) as PNGs')
     ap.add_argument('--render-res', type=int, default=512, help='pixels per side of the rendered views')
     ap.add_argument('--save-depth', action='store_true', help='with --views: also write the depth maps as .npy')
+    ap.add_argument('--keep', type=parse_keep, default=None, help="'largest' or N: keep only the N largest connected components of the shape")
+    ap.add_argument('--min-voxels', type=int, default=0, help='with --keep: also drop kept components of fewer lattice points')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -60,17 +78,21 @@ def main(argv=None):
     results = []
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
-                                 with_normals=args.normals, noise_mode='const')[0]
+                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, noise_mode='const')[0]
         path = os.path.join(args.outdir, f'seed{seed:04d}.ply')
         geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'), out.get('normals'))
         if args.save_volume:
             np.save(os.path.join(args.outdir, f'seed{seed:04d}.npy'), out['volume'].cpu().numpy())
         print(f'seed {seed}: {out["verts"].shape[0]} vertices, {out["faces"].shape[0]} triangles -> {path}')
+        if 'components' in out:
+            info = out['components']
+            sizes = [int(info['stats'][c - 1, 0]) for c in info['kept']]
+            print(f'seed {seed}: {info["count"]} connected components, kept {len(sizes)} of {sizes} lattice points')
         if args.views > 0:
             from PIL import Image
             cams = orbit_cameras(G, args.views, device=args.device)[None]
             views = G.render_geometry(w.float(), cams, mesh, resolution=args.render_res, volume_resolution=args.res, level=args.level,
-                                      noise_mode='const')
+                                      keep=args.keep, min_voxels=args.min_voxels, noise_mode='const')
             shaded = (views['shaded'][0, :, 0].clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
             for k in range(args.views):
                 Image.fromarray(shaded[k], mode='L').save(os.path.join(args.outdir, f'seed{seed:04d}_view{k:02d}.png'))

@@ -14,6 +14,10 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
 - ``raycast``: first hit of rays with the surface of the trilinear field, with depth and normals.  Device tensors go to
   ``ia_volume_bricks`` + ``ia_raycast_volume``; CPU tensors and NumPy arrays take a vectorised NumPy restatement (float64) of the same
   algorithm.  ``volume_normals`` (``ia_volume_gradient``): unit normals at points, e.g. the mesh vertices; ``shade``: headlight Lambert.
+- ``components`` / ``keep_components``: connected components of ``{volume > level}`` (labels, per-component statistics) and the filter
+  that drops floaters before meshing or ray casting; ``mesh_components`` / ``keep_mesh_components``: the same for an indexed mesh.
+  Device tensors go to ``ia_volume_components`` + ``ia_component_stats`` + ``ia_volume_keep`` (``ia_mesh_components`` for meshes); CPU
+  tensors and NumPy arrays take a NumPy union-find restatement of the same definitions.
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
@@ -383,6 +387,206 @@ def shade(normal, rays_d, mask, ambient=0.25):
     d = torch.nn.functional.normalize(rays_d.float(), dim=-1)
     lam = (-(normal.float() * d).sum(-1, keepdim=True)).clamp(0, 1)
     return (ambient + (1.0 - ambient) * lam) * mask[..., None].float()
+
+
+# ------------------------------------------------------------------ connected components
+
+def _forward_offsets(connectivity):
+    """One offset of each pair of opposite neighbour offsets: the lexicographically positive ones."""
+    if connectivity == 6:
+        return [(1, 0, 0), (0, 1, 0), (0, 0, 1)]
+    if connectivity == 26:
+        return [(dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1) if (dx, dy, dz) > (0, 0, 0)]
+    raise ValueError(f'connectivity must be 6 or 26, got {connectivity}')
+
+
+def _roots_numpy(n, a, b):
+    """Union-find over nodes 0..n-1 with the edges (a[e], b[e]): int64 [n], the smallest index of each node's component.  Each round
+    hooks the larger of an edge's two roots under the smaller (parents only decrease, so a root is the minimum of its tree) and then
+    jumps every node to its root; edges inside one tree are dropped; the rounds end when none is left."""
+    parent = np.arange(n, dtype=np.int64)
+    while a.size:
+        ra, rb = parent[a], parent[b]
+        live = ra != rb
+        a, b, ra, rb = a[live], b[live], ra[live], rb[live]
+        if not a.size:
+            break
+        np.minimum.at(parent, np.maximum(ra, rb), np.minimum(ra, rb))
+        while True:
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+    return parent
+
+
+def _components_numpy(v, level, connectivity):
+    """NumPy restatement of ia_volume_components: (labels int32 [nx,ny,nz], K)."""
+    v = np.ascontiguousarray(v, dtype=F32)
+    inside = v > F32(level)                                          # fp32 compare; NaN is outside
+    idx = np.arange(v.size, dtype=np.int64).reshape(v.shape)
+    ea, eb = [], []
+    for off in _forward_offsets(connectivity):
+        s0 = tuple(slice(max(0, -d), n - max(0, d)) for d, n in zip(off, v.shape))
+        s1 = tuple(slice(max(0, d), n - max(0, -d)) for d, n in zip(off, v.shape))
+        both = inside[s0] & inside[s1]
+        ea.append(idx[s0][both])
+        eb.append(idx[s1][both])
+    parent = _roots_numpy(v.size, np.concatenate(ea), np.concatenate(eb))
+    lin = np.flatnonzero(inside)
+    roots = np.unique(parent[lin])                                   # sorted: components in order of their smallest linear index
+    labels = np.zeros(v.size, dtype=np.int32)
+    labels[lin] = np.searchsorted(roots, parent[lin]) + 1
+    return labels.reshape(v.shape), int(roots.size)
+
+
+def _component_stats_numpy(labels, k):
+    """NumPy restatement of ia_component_stats: int32 [K,8]."""
+    labels = np.asarray(labels)
+    stats = np.zeros((k, 8), dtype=np.int32)
+    lin = np.flatnonzero(labels)
+    c = labels.reshape(-1)[lin].astype(np.int64) - 1
+    stats[:, 0] = np.bincount(c, minlength=k)
+    big = np.iinfo(np.int32).max
+    cols = [lin] + list(np.unravel_index(lin, labels.shape))
+    for col, x in enumerate(cols):
+        lo = np.full(k, big, dtype=np.int64)
+        np.minimum.at(lo, c, x)
+        stats[:, 1 + col] = lo
+    for col, x in enumerate(cols[1:]):
+        hi = np.full(k, -1, dtype=np.int64)
+        np.maximum.at(hi, c, x)
+        stats[:, 5 + col] = hi
+    return stats
+
+
+def _check_volume(volume):
+    if volume.ndim != 3 or min(volume.shape) < 2:
+        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
+
+
+def components(volume, level, connectivity=26):
+    """Connected components of ``{volume > level}`` (fp32 compare, NaN outside; neighbours: indices differ by at most 1 on every axis
+    for ``connectivity`` 26, by 1 on exactly one axis for 6): ``(labels, stats)``.  ``labels`` int32 [nx,ny,nz]: 0 outside, components
+    1..K in increasing order of their smallest linear index ``(i*ny + j)*nz + k``.  ``stats`` int32 [K,8], row c-1 for label c: point
+    count, smallest linear index, imin, jmin, kmin, imax, jmax, kmax.  A device tensor runs on ia_volume_components +
+    ia_component_stats (one host synchronisation, for K) and returns device tensors; CPU tensors and NumPy arrays take the NumPy
+    restatement (a union-find written to be checked by reading, not to be fast)."""
+    _forward_offsets(connectivity)
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        from . import hipops
+        labels, k = hipops.volume_components(volume.float().contiguous(), float(level), connectivity)
+        return labels, hipops.component_stats(labels, k)
+    _check_volume(volume)
+    labels, k = _components_numpy(_np(volume), level, connectivity)
+    return _as_out(labels, volume, np.int32), _as_out(_component_stats_numpy(labels, k), volume, np.int32)
+
+
+def select_components(stats, keep='largest', min_voxels=0):
+    """Which labels to keep, from the statistics table (column 0 = size): ``'largest'`` (greatest size; a tie goes to the lowest
+    label), an int n >= 1 (the n largest in that order) or an explicit sequence of labels; ``min_voxels`` then drops those smaller than
+    it.  Returns a list of ints (largest first, or in the order given).  Host code on a [K, *] table."""
+    size = _np(stats)[:, 0].astype(np.int64) if len(stats) else np.zeros(0, dtype=np.int64)
+    k = size.size
+    if isinstance(min_voxels, bool) or int(min_voxels) != min_voxels or min_voxels < 0:
+        raise ValueError(f'min_voxels must be an integer >= 0, got {min_voxels!r}')
+    order = np.lexsort((np.arange(k), -size)) + 1                    # by size descending, then by label
+    if isinstance(keep, str):
+        if keep != 'largest':
+            raise ValueError(f"keep must be 'largest', an int >= 1 or a sequence of labels, got {keep!r}")
+        chosen = order[:1].tolist()
+    elif isinstance(keep, bool) or keep is None:
+        raise ValueError(f"keep must be 'largest', an int >= 1 or a sequence of labels, got {keep!r}")
+    elif isinstance(keep, (int, np.integer)):
+        if keep < 1:
+            raise ValueError(f'keep = {keep}: the number of components to keep must be >= 1')
+        chosen = order[:int(keep)].tolist()
+    else:
+        chosen = []
+        for c in (keep.tolist() if hasattr(keep, 'tolist') else list(keep)):
+            if isinstance(c, bool) or int(c) != c or not 1 <= int(c) <= k:
+                raise ValueError(f'keep: {c!r} is not a label in 1..{k}')
+            chosen.append(int(c))
+        if len(set(chosen)) != len(chosen):
+            raise ValueError(f'keep: labels repeat in {chosen}')
+    return [int(c) for c in chosen if size[c - 1] >= min_voxels]
+
+
+def keep_components(volume, level, keep='largest', min_voxels=0, connectivity=26, fill=None):
+    """Drop floaters: ``(filtered volume, info)``.  The filtered volume equals ``volume`` except at the inside points of components
+    that ``select_components`` does not keep, which become ``fill`` (default: ``level`` rounded to fp32, which is not inside); outside
+    points are never touched, so the kept surface is unchanged.  ``info = {'count': K, 'kept': labels kept, 'stats': [K,8]}``.  With
+    connectivity 26 the mesh of the filtered volume is exactly the kept components' triangles of the original mesh."""
+    labels, stats = components(volume, level, connectivity)
+    kept = select_components(stats, keep, min_voxels)
+    k = int(stats.shape[0])
+    fill = float(F32(level)) if fill is None else float(F32(fill))
+    flags = np.zeros(k + 1, dtype=np.uint8)
+    flags[kept] = 1
+    info = {'count': k, 'kept': kept, 'stats': stats}
+    if isinstance(volume, torch.Tensor) and volume.is_cuda:
+        from . import hipops
+        return hipops.volume_keep(volume.float().contiguous(), labels, torch.from_numpy(flags).to(volume.device), fill), info
+    lab = _np(labels)
+    out = np.array(_np(volume), dtype=F32)
+    out[(lab > 0) & (flags[lab] == 0)] = F32(fill)
+    return _as_out(out, volume), info
+
+
+def _mesh_components_numpy(faces, n_verts):
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= n_verts):
+        raise ValueError(f'faces index vertices outside [0, {n_verts})')
+    parent = _roots_numpy(n_verts, np.concatenate([faces[:, 0], faces[:, 1]]), np.concatenate([faces[:, 1], faces[:, 2]]))
+    roots = np.unique(parent)
+    vl = (np.searchsorted(roots, parent) + 1).astype(np.int32)
+    fl = vl[faces[:, 0]]
+    stats = np.zeros((roots.size, 3), dtype=np.int32)
+    stats[:, 0] = np.bincount(vl.astype(np.int64) - 1, minlength=roots.size)
+    stats[:, 1] = np.bincount(fl.astype(np.int64) - 1, minlength=roots.size)
+    stats[:, 2] = roots
+    return vl, fl, stats
+
+
+def mesh_components(faces, n_verts):
+    """Connected components of an indexed triangle mesh (two vertices are connected if a face contains both): ``(vert_labels int32
+    [V], face_labels int32 [F], stats int32 [K,3])``.  Components 1..K in increasing order of their smallest vertex index; a vertex
+    used by no face is a component of its own; a face has the label of its first vertex; stats rows: vertex count, face count,
+    smallest vertex index.  Device tensors run on ia_mesh_components (two host synchronisations: the index range check and K)."""
+    n_verts = int(n_verts)
+    if n_verts < 0 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f'faces must be [F,3] and n_verts >= 0, got {tuple(faces.shape)} and {n_verts}')
+    if isinstance(faces, torch.Tensor) and faces.is_cuda:
+        from . import hipops
+        if faces.shape[0] and (int(faces.min()) < 0 or int(faces.max()) >= n_verts):
+            raise ValueError(f'faces index vertices outside [0, {n_verts})')
+        f32 = faces.to(torch.int32).contiguous()
+        vl, k = hipops.mesh_components(f32, n_verts)
+        return vl, vl[faces[:, 0].long()], hipops.mesh_component_stats(f32, vl, k)
+    vl, fl, stats = _mesh_components_numpy(_np(faces), n_verts)
+    return _as_out(vl, faces, np.int32), _as_out(fl, faces, np.int32), _as_out(stats, faces, np.int32)
+
+
+def keep_mesh_components(verts, faces, keep='largest', extras=()):
+    """The mesh restricted to the components ``select_components`` keeps (sizes = vertex counts): ``(verts, faces, extras, info)`` with
+    the vertices compacted in their old order, the faces re-indexed (int64) and every per-vertex array in ``extras`` (colours, normals)
+    carried along.  ``info = {'count': K, 'kept': labels, 'stats': [K,3]}``.  NumPy in, NumPy out; tensors stay on their device."""
+    as_np = not isinstance(verts, torch.Tensor)
+    tv, tf = torch.as_tensor(verts), torch.as_tensor(faces).to(torch.as_tensor(verts).device)
+    vl, fl, stats = mesh_components(tf, tv.shape[0])
+    kept = select_components(stats, keep)
+    k = int(stats.shape[0])
+    flag = torch.zeros(k + 1, dtype=torch.bool)
+    flag[kept] = True
+    flag = flag.to(tv.device)
+    vmask, fmask = flag[vl.long()], flag[fl.long()]
+    new_index = torch.cumsum(vmask, 0) - 1
+    out_f = new_index[tf[fmask].long()].reshape(-1, 3)
+    out = [tv[vmask], out_f] + [torch.as_tensor(e).to(tv.device)[vmask] for e in extras]
+    if as_np:
+        out = [o.numpy() for o in out]
+        stats = _np(stats)
+    return out[0], out[1], out[2:], {'count': k, 'kept': kept, 'stats': stats}
 
 
 # ------------------------------------------------------------------ generator-level helpers

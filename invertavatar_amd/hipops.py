@@ -1441,6 +1441,104 @@ def volume_gradient(volume, lo, step, points):
     return grad
 
 
+# ------------------------------------------------------------------ connected components (csrc/components.hip)
+
+def _i32c(t, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise RuntimeError(f'{what} must be a contiguous int32 device tensor')
+    return t
+
+
+def volume_components(volume, level, connectivity=26):
+    """Components of {volume > level} (see ia_volume_components): volume [nx,ny,nz] -> (labels int32 [nx,ny,nz], K).  One host
+    synchronisation (K)."""
+    nx, ny, nz = _volume_checked(volume)
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_components_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_components_scratch_bytes')
+    dev = volume.device
+    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=dev)
+    labels = torch.empty(nx, ny, nz, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _Timed('volume_components', 0.0, 4.0 * volume.numel() * 8, f'{nx}x{ny}x{nz} c{connectivity}'):
+            st = lib.ia_volume_components(_p(volume), nx, ny, nz, float(level), int(connectivity), _p(labels), _p(scratch),
+                                          scratch.numel() * 4, _p(count), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_volume_components')
+        return labels, int(count.cpu())
+
+
+def component_stats(labels, k):
+    """Per-component statistics (see ia_component_stats): labels int32 [nx,ny,nz], K -> int32 [K,8] = count, smallest linear index,
+    imin, jmin, kmin, imax, jmax, kmax."""
+    _i32c(labels, 'labels')
+    if labels.dim() != 3:
+        raise RuntimeError(f'labels must be [nx,ny,nz], got {tuple(labels.shape)}')
+    nx, ny, nz = labels.shape
+    dev = labels.device
+    stats = torch.empty(max(int(k), 0), 8, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _Timed('component_stats', 0.0, 4.0 * labels.numel(), f'{nx}x{ny}x{nz} K={k}'):
+        st = _lib.load().ia_component_stats(_p(labels), nx, ny, nz, int(k), _p(stats), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_component_stats')
+    return stats
+
+
+def volume_keep(volume, labels, keep_flags, fill, out=None):
+    """The filter (see ia_volume_keep): points of components 1..K whose flag is 0 become ``fill``; keep_flags uint8 [K+1] on the device.
+    ``out``: where to write (``volume`` itself for in place); default a new tensor."""
+    _f32c(volume, 'volume')
+    _i32c(labels, 'labels')
+    if labels.shape != volume.shape or labels.device != volume.device:
+        raise RuntimeError(f'labels {tuple(labels.shape)} on {labels.device} do not match volume {tuple(volume.shape)} on {volume.device}')
+    if not (keep_flags.is_cuda and keep_flags.dtype == torch.uint8 and keep_flags.is_contiguous() and keep_flags.dim() == 1
+            and keep_flags.numel() >= 1 and keep_flags.device == volume.device):
+        raise RuntimeError('keep_flags must be a contiguous uint8 device tensor [K+1] on the volume\'s device')
+    if out is None:
+        out = torch.empty_like(volume)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == volume.shape and out.device == volume.device):
+        raise RuntimeError('out must be a contiguous float32 tensor of the volume\'s shape and device')
+    dev = volume.device
+    with torch.cuda.device(dev), _Timed('volume_keep', 0.0, 12.0 * volume.numel(), f'{tuple(volume.shape)}'):
+        st = _lib.load().ia_volume_keep(_p(volume), _p(labels), volume.numel(), _p(keep_flags), keep_flags.numel() - 1, float(fill),
+                                        _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_volume_keep')
+    return out
+
+
+def mesh_components(faces, n_verts):
+    """Components of a mesh's vertices (see ia_mesh_components): faces int32 [F,3], V -> (vert_labels int32 [V], K).  One host
+    synchronisation (K)."""
+    _i32c(faces, 'faces')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f'faces must be [F,3], got {tuple(faces.shape)}')
+    v, f = int(n_verts), faces.shape[0]
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_mesh_components_scratch_bytes(v, ctypes.byref(nbytes)), 'ia_mesh_components_scratch_bytes')
+    dev = faces.device
+    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=dev)
+    labels = torch.empty(v, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _Timed('mesh_components', 0.0, 12.0 * f + 32.0 * v, f'F={f} V={v}'):
+            st = lib.ia_mesh_components(_p(faces), f, v, _p(labels), _p(scratch), scratch.numel() * 4, _p(count), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_mesh_components')
+        return labels, int(count.cpu())
+
+
+def mesh_component_stats(faces, vert_labels, k):
+    """int32 [K,3] = vertex count, face count, smallest vertex index per component (see ia_mesh_component_stats)."""
+    _i32c(faces, 'faces')
+    _i32c(vert_labels, 'vert_labels')
+    dev = faces.device
+    stats = torch.empty(max(int(k), 0), 3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _Timed('mesh_component_stats', 0.0, 4.0 * (faces.numel() + vert_labels.numel()), f'K={k}'):
+        st = _lib.load().ia_mesh_component_stats(_p(faces), faces.shape[0], vert_labels.numel(), _p(vert_labels), int(k), _p(stats),
+                                                 _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_component_stats')
+    return stats
+
+
 IMAGE_LAYOUT_F32_NCHW, IMAGE_LAYOUT_U8_NHWC = 0, 1
 
 

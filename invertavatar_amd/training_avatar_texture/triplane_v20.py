@@ -535,13 +535,17 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         with_normals=False, **synthesis_kwargs):
+                         with_normals=False, keep=None, min_voxels=0, **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
         'colors' uint8 [V,3] (the decoder's rgb[:3] at the vertices) and, with ``with_normals``, 'normals' float32 [V,3]
         (``geometry.volume_normals``: unit, toward decreasing density).  ``level`` = 10 is the EG3D-family shape threshold: a knob, not a
-        constant of the model.  The planes are computed once per call; device tensors stay on the device throughout."""
+        constant of the model.  With ``keep`` (``'largest'``, an int n or a list of labels; ``min_voxels``: see
+        ``geometry.select_components``) the detached components of {density > level} are removed from the volume first
+        (``geometry.keep_components``, 26-connectivity): 'volume' is then the filtered volume, mesh, colours and normals come from it, and
+        'components' holds {'count', 'kept', 'stats'}.  The planes are computed once per call; device tensors stay on the device
+        throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
         length = box_warp if cube_length is None else cube_length
@@ -551,25 +555,30 @@ class TriPlaneGenerator(torch.nn.Module):
         axes = [geometry.lattice_axis(n, ls[a], org[a]) for a, n in enumerate(res)]
         out = []
         for b in range(volume.shape[0]):
-            verts, faces = geometry.marching_cubes(volume[b], level, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
-            item = {'volume': volume[b], 'verts': verts, 'faces': faces}
+            vol_b, info = volume[b], None
+            if keep is not None:
+                vol_b, info = geometry.keep_components(vol_b, level, keep, min_voxels)
+            verts, faces = geometry.marching_cubes(vol_b, level, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
+            item = {'volume': vol_b, 'verts': verts, 'faces': faces}
+            if info is not None:
+                item['components'] = info
             if with_colors:
                 item['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, verts, box_warp)
             if with_normals:
-                item['normals'] = geometry.volume_normals(volume[b], verts, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
+                item['normals'] = geometry.volume_normals(vol_b, verts, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
             out.append(item)
         return out
 
     @torch.no_grad()
     def render_geometry(self, ws, c, mesh_condition, resolution=512, volume_resolution=256, level=10.0, cube_length=None, with_colors=False,
-                        **synthesis_kwargs):
+                        keep=None, min_voxels=0, **synthesis_kwargs):
         """Surface renders of the avatar's shape from the cameras ``c`` ([B,25] or [B,V,25]): per identity the density volume of
         ``extract_geometry`` (``volume_resolution``^3 over ``cube_length``, default box_warp) and the first hit of every camera ray
         (``geometry.raycast``; rays of the generator's ray sampler, so pixels align with ``image_depth`` at the same resolution) with
         {density > level}, all views of an identity in one launch.  Returns NCHW 'depth' [B(,V),1,H,W] (ray parameter; 0 on a miss),
         'mask' bool [B(,V),1,H,W], 'normal' [B(,V),3,H,W] (unit, toward decreasing density), 'shaded' [B(,V),1,H,W] (headlight
         Lambert, ``geometry.shade``) and, with ``with_colors``, 'rgb' [B(,V),3,H,W] (the decoder's rgb[:3] at the hit points, 0 on a
-        miss)."""
+        miss).  ``keep`` / ``min_voxels``: as in ``extract_geometry``, the volume is filtered before the bricks and the ray cast."""
         from .. import geometry
         single = c.dim() == 2
         cams = c[:, None] if single else c
@@ -588,7 +597,8 @@ class TriPlaneGenerator(torch.nn.Module):
         rays_o, rays_d = rays_o.reshape(B, V * resolution * resolution, 3), rays_d.reshape(B, V * resolution * resolution, 3)
         outs = []
         for b in range(B):
-            hit = geometry.raycast(volume[b], level, lo, step, rays_o[b], rays_d[b])
+            vol_b = volume[b] if keep is None else geometry.keep_components(volume[b], level, keep, min_voxels)[0]
+            hit = geometry.raycast(vol_b, level, lo, step, rays_o[b], rays_d[b])
             hit['shaded'] = geometry.shade(hit['normal'], rays_d[b], hit['mask'])
             if with_colors:
                 pts = (rays_o[b] + hit['depth'][:, None] * rays_d[b])[None]

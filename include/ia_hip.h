@@ -924,6 +924,54 @@ int ia_mesh_components(const int* faces, int64_t F, int V, int* vert_labels, voi
                        void* stream);
 int ia_mesh_component_stats(const int* faces, int64_t F, int V, const int* vert_labels, int K, int* stats, void* stream);
 
+/*
+ * Distance between surfaces (csrc/surface_distance.hip; no counterpart in the reference): exact distance from points to a triangle
+ * mesh, and the reductions behind Chamfer distance, Hausdorff distance and F-score.
+ *
+ * The distance from p to a triangle is the Euclidean distance to the closed triangle (a triangle without area is a segment or a
+ * point); the distance to a mesh is the minimum over its usable triangles of ONE fp32 per-triangle function, taken on the pair
+ * (distance, index).  The grid only prunes: results are bit-identical with and without it, for every grid resolution, run to run.
+ *
+ * ia_tri_pack: tris = float4 [F,3] (48 bytes per triangle, 16-byte aligned): A, B, C with A.w = 1 for a usable triangle and 0 for an
+ * ignored one (a non-finite coordinate, or an index outside [0, V)).  faces int32 [F,3], F <= 2^25.
+ *
+ * ia_trigrid_plan (host arithmetic only): from F and the bounding box [lo, hi] of the finite vertices, dims[3] (about one cubic cell
+ * per triangle, at most 256 per axis; request[a] > 0 fixes an axis, up to 1024; request may be NULL) and inv_cell[3].  The cell of a
+ * coordinate x along an axis is clamp(floor((x - lo) * inv_cell), 0, dims - 1), in fp32.  At most 2^26 cells.
+ *
+ * ia_trigrid_count: cell_start int32 [ncell + 2] (ncell = dims[0] * dims[1] * dims[2], x slowest).  A usable triangle is counted in
+ * every cell its bounding box covers, or, if these are more than 64, as oversize.  On return cell_start[0 .. ncell] are the exclusive
+ * offsets (cell_start[ncell] = entries <= 64 F) and cell_start[ncell + 1] = the number of oversize triangles; the caller reads these
+ * two (one host synchronisation) and sizes cell_tris = int32 [entries + n_over].
+ * ia_trigrid_fill: writes the cells' triangle lists (in any order) and, behind them, the oversize list, which every query tests.
+ * scratch: 4 * (ncell + 1) bytes.
+ *
+ * ia_closest_point: per query point (float32 [N,3]) dist float32 [N], face int32 [N] (the triangle that attains the fp32 minimum; the
+ * lowest index among equals), point float32 [N,3] (the closest point on that triangle).  A non-finite query gives NaN / -1 / NaN, a
+ * mesh without usable triangles +inf / -1 / NaN.  cell_start == NULL: brute mode, the same kernel body walks all F triangles (lo,
+ * inv_cell, dims, cell_tris, entries, n_over are then ignored).  mesh_extent: the largest |coordinate| of the mesh (it scales the
+ * safety margin of the shell search; a larger value only costs time).
+ *
+ * ia_distance_stats: out = double [14]: number of finite entries of dist, their sum, sum of squares and maximum (-inf if none), the
+ * sum of |normals_a[i] . normals_b[face[i]]| over finite entries with face in [0, Fb) (0 without normals: face, normals_a, normals_b
+ * all NULL), the number of non-finite entries, and for k < n_thresholds <= 8 the number of finite entries <= thresholds[k] (a host
+ * array).  Double sums per workgroup, combined in index order by a second launch: no floating-point atomics, bit-equal run to run.
+ * scratch: ia_distance_stats_scratch_bytes(N) bytes, 8-byte aligned.
+ */
+int ia_tri_pack(const float* verts, int V, const int* faces, int64_t F, void* tris, void* stream);
+int ia_trigrid_plan(int64_t F, const float* h_lo, const float* h_hi, const int* h_request, int* h_dims, float* h_inv_cell);
+int ia_trigrid_count(const void* tris, int64_t F, const float* h_lo, const float* h_inv_cell, const int* h_dims, int* cell_start,
+                     void* stream);
+int ia_trigrid_fill(const void* tris, int64_t F, const float* h_lo, const float* h_inv_cell, const int* h_dims, const int* cell_start,
+                    int entries, int n_over, void* scratch, size_t scratch_bytes, int* cell_tris, void* stream);
+int ia_closest_point(const float* points, int64_t N, const void* tris, int64_t F, float mesh_extent, const float* h_lo,
+                     const float* h_inv_cell, const int* h_dims, const int* cell_start, const int* cell_tris, int entries, int n_over,
+                     float* dist, int* face, float* point, void* stream);
+int ia_distance_stats_scratch_bytes(int64_t N, size_t* h_bytes);
+int ia_distance_stats(const float* dist, int64_t N, const float* h_thresholds, int n_thresholds, const int* face,
+                      const float* normals_a, const float* normals_b, int64_t Fb, void* scratch, size_t scratch_bytes, double* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

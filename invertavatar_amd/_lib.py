@@ -116,6 +116,16 @@ _SIGNATURES = {
     'ia_mesh_components_scratch_bytes': [c_int, ctypes.POINTER(ctypes.c_size_t)],
     'ia_mesh_components': [c_void_p, c_int64, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     'ia_mesh_component_stats': [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    'ia_tri_pack': [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_trigrid_plan': [c_int64, _f32p, _f32p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), _f32p],
+    'ia_trigrid_count': [c_void_p, c_int64, _f32p, _f32p, ctypes.POINTER(c_int), c_void_p, c_void_p],
+    'ia_trigrid_fill': [c_void_p, c_int64, _f32p, _f32p, ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t,
+                        c_void_p, c_void_p],
+    'ia_closest_point': [c_void_p, c_int64, c_void_p, c_int64, c_float, _f32p, _f32p, ctypes.POINTER(c_int), c_void_p, c_void_p, c_int,
+                         c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_distance_stats_scratch_bytes': [c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_distance_stats': [c_void_p, c_int64, _f32p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p,
+                          c_void_p],
 }
 
 

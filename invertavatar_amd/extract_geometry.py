@@ -8,15 +8,18 @@ PLY with per-vertex colours, and with ``--normals`` vertex normals); ``--save-vo
 camera radius and pivot) and writes the shaded views as 8-bit PNGs ``seed%04d_view%02d.png`` (``--save-depth``: the depth maps as
 ``seed%04d_depth.npy``, [N,R,R]).  ``--keep largest`` (or ``--keep N``) removes the detached components of {density > level} from the
 volume first, so the PLY, the views and the saved depth show the N largest only; ``--min-voxels M`` also drops kept components of fewer
-than M lattice points; a line per seed reports how many components there were and the sizes of the kept ones.  Runs on the device when
-there is one."""
+than M lattice points; a line per seed reports how many components there were and the sizes of the kept ones.  ``--compare REF.ply``
+prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh against ``REF.ply`` and writes them as
+``seed%04d_geometry.json`` (``geometry_metrics.compare_meshes``); ``--error-ply`` also writes ``seed%04d_error.ply``, the mesh coloured by
+its distance to the reference.  Runs on the device when there is one."""
 import argparse
+import json
 import os
 
 import numpy as np
 import torch
 
-from . import geometry, synthetic
+from . import geometry, geometry_metrics, synthetic
 from .reenact_avatar_next3d import FolderDrive, build_generator, parse_range, seed_latents
 from .training_avatar_texture.camera_utils import FOV_to_intrinsics, LookAtPoseSampler
 
@@ -69,6 +72,8 @@ def main(argv=None):
     ap.add_argument('--save-depth', action='store_true', help='with --views: also write the depth maps as .npy')
     ap.add_argument('--keep', type=parse_keep, default=None, help="'largest' or N: keep only the N largest connected components of the shape")
     ap.add_argument('--min-voxels', type=int, default=0, help='with --keep: also drop kept components of fewer lattice points')
+    ap.add_argument('--compare', default=None, metavar='REF.ply', help='score the extracted mesh against this mesh (Chamfer, Hausdorff, F-score)')
+    ap.add_argument('--error-ply', action='store_true', help='with --compare: also write the mesh coloured by its distance to REF.ply')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -88,6 +93,14 @@ def main(argv=None):
             info = out['components']
             sizes = [int(info['stats'][c - 1, 0]) for c in info['kept']]
             print(f'seed {seed}: {info["count"]} connected components, kept {len(sizes)} of {sizes} lattice points')
+        if args.compare:
+            rv, rf, _ = geometry.read_ply(args.compare)
+            rv, rf = torch.from_numpy(rv).to(out['verts'].device), torch.from_numpy(rf).to(out['verts'].device)
+            err = os.path.join(args.outdir, f'seed{seed:04d}_error.ply') if args.error_ply else None
+            out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err)
+            with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
+                json.dump(out['metrics'], fh, indent=1)
+            print(f'seed {seed}: against {args.compare}: {geometry_metrics.summary(out["metrics"])}')
         if args.views > 0:
             from PIL import Image
             cams = orbit_cameras(G, args.views, device=args.device)[None]

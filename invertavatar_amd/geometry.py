@@ -18,6 +18,10 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   that drops floaters before meshing or ray casting; ``mesh_components`` / ``keep_mesh_components``: the same for an indexed mesh.
   Device tensors go to ``ia_volume_components`` + ``ia_component_stats`` + ``ia_volume_keep`` (``ia_mesh_components`` for meshes); CPU
   tensors and NumPy arrays take a NumPy union-find restatement of the same definitions.
+- ``closest_point`` / ``TriangleGrid`` / ``surface_distance``: exact point-to-mesh distance and the numbers made of it (Chamfer and
+  Hausdorff distance, F-score, normal consistency), with ``face_normals`` and ``sample_surface``.  Device tensors go to ``ia_tri_pack`` +
+  ``ia_trigrid_count`` / ``ia_trigrid_fill`` + ``ia_closest_point`` + ``ia_distance_stats``; CPU tensors and NumPy arrays take a NumPy
+  restatement (``point_triangle``: the kernel's per-triangle function line by line, float64; brute force over all triangles).
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
@@ -587,6 +591,301 @@ def keep_mesh_components(verts, faces, keep='largest', extras=()):
         out = [o.numpy() for o in out]
         stats = _np(stats)
     return out[0], out[1], out[2:], {'count': k, 'kept': kept, 'stats': stats}
+
+
+# ------------------------------------------------------------------ surface distance
+
+def _dot3(u, v):
+    return (u[..., 0] * v[..., 0] + u[..., 1] * v[..., 1]) + u[..., 2] * v[..., 2]
+
+
+def _cross3(u, v):
+    return np.stack([u[..., 1] * v[..., 2] - u[..., 2] * v[..., 1], u[..., 2] * v[..., 0] - u[..., 0] * v[..., 2],
+                     u[..., 0] * v[..., 1] - u[..., 1] * v[..., 0]], -1)
+
+
+def _segment(a, e, ee, best, q, dtype):
+    """Closest point of the segment a + t e, t in [0, 1] (ee = e . e), to the origin; kept where its squared distance is below ``best``."""
+    pos = ee > 0
+    t = np.where(pos, np.minimum(np.maximum(-_dot3(a, e) / np.where(pos, ee, dtype(1)), dtype(0)), dtype(1)), dtype(0))
+    r = a + t[..., None] * e
+    d2 = _dot3(r, r)
+    take = d2 < best
+    return np.where(take, d2, best), np.where(take[..., None], r, q)
+
+
+def point_triangle(p, A, B, C, dtype=np.float64):
+    """The per-triangle function (csrc/surface_distance.hip tri_dist), evaluated in ``dtype`` on broadcastable [..., 3] arrays:
+    ``(dist, q)`` with q the closest point of the closed triangle relative to p.  In coordinates relative to the query point: the
+    minimum of the three clamped point-to-segment distances, replaced by the plane distance ``|n . a| / |n|`` (n: the cross product of
+    the two shorter edges) when ``n . n > 0``, the origin projects inside and the plane distance is the smaller one (``n . (a x (b - a))``, ``n . (b x (c - b))``, ``n . (c x (a - c))`` all ``>= 0``).  Every operation is
+    rounded on its own and dot products are ``(x + y) + z``, so the float32 run follows the kernel operation by operation."""
+    p, A, B, C = (np.asarray(x, dtype=dtype) for x in (p, A, B, C))
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore', under='ignore'):
+        a, b, c = A - p, B - p, C - p
+        a, b, c = np.broadcast_arrays(a, b, c)
+        d2 = np.full(a.shape[:-1], np.inf, dtype=dtype)
+        q = np.full(a.shape, np.nan, dtype=dtype)
+        eab, ebc, eca = b - a, c - b, a - c
+        lab, lbc, lca = _dot3(eab, eab), _dot3(ebc, ebc), _dot3(eca, eca)
+        d2, q = _segment(a, eab, lab, d2, q, dtype)
+        d2, q = _segment(b, ebc, lbc, d2, q, dtype)
+        d2, q = _segment(c, eca, lca, d2, q, dtype)
+        d = np.sqrt(d2)
+        # the normal from the two shorter edges (eab x ebc = ebc x eca = eca x eab): no cancellation on needle-shaped triangles
+        ab_longest, bc_longest = (lab >= lbc) & (lab >= lca), lbc >= lca
+        n = np.where(ab_longest[..., None], _cross3(ebc, eca), np.where(bc_longest[..., None], _cross3(eca, eab), _cross3(eab, ebc)))
+        nn = _dot3(n, n)
+        inside = (nn > 0) & (_dot3(n, _cross3(a, eab)) >= 0) & (_dot3(n, _cross3(b, ebc)) >= 0) & (_dot3(n, _cross3(c, eca)) >= 0)
+        na = _dot3(n, a)
+        safe = np.where(inside, nn, dtype(1))
+        dp = np.abs(na) / np.sqrt(safe)
+        inside &= dp < d                                               # (a vertex or edge that p lies on keeps its exact 0)
+        d = np.where(inside, dp, d)
+        q = np.where(inside[..., None], n * (na / safe)[..., None], q)
+    return d.astype(dtype), q.astype(dtype)
+
+
+def _closest_numpy(points, verts, faces, dtype=np.float64, pairs=1 << 20):
+    """NumPy restatement of ia_closest_point in ``dtype``: brute force over all usable triangles, ``pairs`` point-triangle pairs at a
+    time; the minimum on the pair (distance, index).  (dist [N], face int32 [N], point [N,3]), all computed in ``dtype``."""
+    p = np.asarray(points, dtype=F32).reshape(-1, 3).astype(dtype)
+    v = np.asarray(verts, dtype=F32).reshape(-1, 3).astype(dtype)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    n = p.shape[0]
+    dist, face, point = np.full(n, np.inf, dtype=dtype), np.full(n, -1, dtype=np.int32), np.full((n, 3), np.nan, dtype=dtype)
+    in_range = ((f >= 0) & (f < v.shape[0])).all(1)
+    tri = v[np.where(in_range[:, None], f, 0)]                                    # [F,3,3]
+    usable = np.flatnonzero(in_range & np.isfinite(tri).all((1, 2)))             # increasing: argmin picks the lowest index among equals
+    tri = tri[usable]
+    ok = np.isfinite(p).all(1)
+    dist[~ok] = np.nan
+    rows = np.flatnonzero(ok)
+    if usable.size and rows.size:
+        step = max(1, pairs // usable.size)
+        for s in range(0, rows.size, step):
+            r = rows[s:s + step]
+            d, _ = point_triangle(p[r, None, :], tri[None, :, 0], tri[None, :, 1], tri[None, :, 2], dtype)
+            d = np.where(np.isnan(d), np.inf, d)
+            j = np.argmin(d, axis=1)                                              # the first of equal minima
+            dj = d[np.arange(r.size), j]
+            hit = dj < np.inf
+            _, q = point_triangle(p[r], tri[j, 0], tri[j, 1], tri[j, 2], dtype)
+            dist[r] = dj
+            face[r] = np.where(hit, usable[j], -1)
+            point[r] = np.where(hit[:, None], p[r] + q, np.nan)
+    return dist, face, point
+
+
+def _mesh_args(verts, faces):
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f'a mesh is verts [V,3] and faces [F,3], got {tuple(verts.shape)} and {tuple(faces.shape)}')
+
+
+class TriangleGrid:
+    """The search structure of one mesh on the device, built once: packed triangles and a uniform grid of triangle lists (CSR) over
+    the bounding box of the finite vertices.  ``cells``: None (about one cell per triangle), an int or a triple.  A triangle whose
+    bounding box covers more than 64 cells is kept in a separate list that every query tests, so the structure stays bounded for
+    meshes that mix millions of small triangles with a few that span the box.  ``closest(points)`` -> {'dist','face','point'}; the
+    structure changes no result (see ``closest_point``)."""
+
+    def __init__(self, verts, faces, cells=None, build=True):
+        from . import hipops
+        _mesh_args(verts, faces)
+        if not (isinstance(verts, torch.Tensor) and verts.is_cuda):
+            raise ValueError('TriangleGrid holds device tensors; CPU meshes go to closest_point directly')
+        self.verts = verts.detach().float().contiguous()
+        self.faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+        self.tris = hipops.tri_pack(self.verts, self.faces)
+        fin = self.verts[torch.isfinite(self.verts).all(1)]
+        if fin.shape[0]:
+            box = torch.stack([fin.amin(0), fin.amax(0)]).cpu().tolist()           # one host synchronisation
+        else:
+            box = [[0.0] * 3, [0.0] * 3]
+        self.lo, self.hi = box
+        self.extent = max(max(abs(x) for x in self.lo), max(abs(x) for x in self.hi))
+        self.grid = None
+        if build:
+            self.dims, self.inv_cell = hipops.trigrid_plan(self.faces.shape[0], self.lo, self.hi, cells)
+            self.cell_start, self.cell_tris, self.entries, self.n_over = hipops.trigrid_build(self.tris, self.lo, self.inv_cell, self.dims)
+            self.grid = (self.lo, self.inv_cell, self.dims, self.cell_start, self.cell_tris, self.entries, self.n_over)
+
+    def closest(self, points, brute=False, sort=True):
+        """{'dist' [N], 'face' int64 [N], 'point' [N,3]} for points [N,3] on the grid's device.  ``sort``: query in the order of the
+        points' cells (neighbouring lanes then walk the same lists) and return in the caller's order."""
+        from . import hipops
+        pts = points.detach().to(self.verts.device).float().reshape(-1, 3).contiguous()
+        grid = None if brute else self.grid
+        order = None
+        if sort and grid is not None and pts.shape[0] > 64:
+            lo = torch.tensor(self.lo, device=pts.device)
+            inv = torch.tensor(self.inv_cell, device=pts.device)
+            top = torch.tensor(self.dims, device=pts.device) - 1
+            c = torch.minimum(((pts - lo) * inv).floor().nan_to_num(0.0, 0.0, 0.0).clamp(0, 1024).long(), top)
+            order = torch.argsort((c[:, 0] * self.dims[1] + c[:, 1]) * self.dims[2] + c[:, 2])
+            pts = pts[order]
+        dist, face, point = hipops.closest_point(pts, self.tris, self.extent, grid)
+        if order is not None:
+            back = torch.empty_like(order)
+            back[order] = torch.arange(order.numel(), device=order.device)
+            dist, face, point = dist[back], face[back], point[back]
+        return {'dist': dist, 'face': face.long(), 'point': point}
+
+
+def closest_point(points, verts, faces, grid=None, brute=False):
+    """Exact distance from points [N,3] to the triangle mesh (verts float32 [V,3], faces [F,3]): ``{'dist' float32 [N] (unsigned),
+    'face' int64 [N], 'point' float32 [N,3]}``.  The distance to a triangle is the distance to the closed triangle (a triangle of zero
+    area is a segment or a point; a triangle with a non-finite vertex is ignored), the distance to the mesh the minimum over its
+    triangles; ``face`` is the triangle that attains the minimum (the lowest index among equal distances) and ``point`` the closest
+    point on it.  A non-finite query gives NaN / -1 / NaN, a mesh without usable triangles +inf / -1 / NaN.  Device tensors run on
+    ia_closest_point, through ``grid`` (a ``TriangleGrid`` of this mesh; built here if None) or, with ``brute=True``, over all triangles:
+    both give bit-identical results.  CPU tensors and NumPy arrays take the NumPy restatement (float64, brute force in chunks)."""
+    _mesh_args(verts, faces)
+    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+        if grid is None:
+            grid = TriangleGrid(verts, faces, build=not brute)
+        return grid.closest(points, brute=brute)
+    if faces.shape[0] and (_np(faces).min() < 0 or _np(faces).max() >= verts.shape[0]):
+        raise ValueError(f'faces index vertices outside [0, {verts.shape[0]})')
+    lead = tuple(points.shape[:-1])
+    dist, face, point = _closest_numpy(_np(points), _np(verts), _np(faces))
+    return {'dist': _as_out(dist.reshape(lead), points), 'face': _as_out(face.reshape(lead), points, np.int64),
+            'point': _as_out(point.reshape(lead + (3,)), points)}
+
+
+def face_normals(verts, faces):
+    """Unit normals [F,3] of the faces, ``(B - A) x (C - A)`` normalised (0 for a face without area).  Torch tensors stay on their
+    device; NumPy in, NumPy out."""
+    v, f = torch.as_tensor(verts).float(), torch.as_tensor(faces).long()
+    f = f.to(v.device)
+    n = torch.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=-1)
+    nrm = n.norm(dim=-1, keepdim=True)
+    out = torch.where(nrm > 0, n / nrm.clamp_min(1e-38), torch.zeros_like(n))
+    return out if isinstance(verts, torch.Tensor) else out.numpy()
+
+
+def sample_surface(verts, faces, n, seed=0):
+    """``n`` points distributed uniformly over the surface: ``(points float32 [n,3], face int64 [n])``.  The face is drawn with
+    probability proportional to its area (float64 cumulative areas + ``searchsorted``), the point on it with square-root barycentrics
+    ``(1 - sqrt(u), sqrt(u) (1 - v), sqrt(u) v)``; all draws come from a CPU generator seeded with ``seed``, so the samples are the
+    same on every device.  Faces with a non-finite vertex have no area here."""
+    v, f = torch.as_tensor(verts).float(), torch.as_tensor(faces).long()
+    f = f.to(v.device)
+    tri = v[f].double()
+    area = 0.5 * torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=-1).norm(dim=-1)
+    area = torch.where(torch.isfinite(area), area, torch.zeros_like(area))
+    cum = torch.cumsum(area, 0)
+    if f.shape[0] == 0 or not float(cum[-1]) > 0:
+        raise ValueError('sample_surface: the mesh has no area')
+    gen = torch.Generator().manual_seed(int(seed))
+    u = torch.rand(int(n), 3, generator=gen, dtype=torch.float64).to(v.device)
+    idx = torch.searchsorted(cum, u[:, 0] * cum[-1], right=True).clamp_max(f.shape[0] - 1)
+    s = u[:, 1].sqrt()
+    w = torch.stack([1 - s, s * (1 - u[:, 2]), s * u[:, 2]], -1)
+    pts = (w[:, :, None] * tri[idx]).sum(1).float()
+    if isinstance(verts, torch.Tensor):
+        return pts, idx
+    return pts.numpy(), idx.numpy()
+
+
+def _stats_numpy(dist, thresholds, face=None, na=None, nb=None):
+    """NumPy restatement of ia_distance_stats (float64)."""
+    d = np.asarray(dist, dtype=F32)
+    ok = np.isfinite(d)
+    x = d[ok].astype(np.float64)
+    out = np.zeros(14)
+    out[0], out[1], out[2], out[3], out[5] = x.size, x.sum(), (x * x).sum(), x.max() if x.size else -np.inf, d.size - x.size
+    if face is not None:
+        fa = np.asarray(face)
+        use = ok & (fa >= 0) & (fa < len(nb))
+        a, b = np.asarray(na, dtype=np.float64)[use], np.asarray(nb, dtype=np.float64)[fa[use]]
+        out[4] = np.abs((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]).sum()
+    for k, t in enumerate(thresholds):
+        out[6 + k] = np.count_nonzero(d[ok] <= F32(t))
+    return out
+
+
+def _sample_set(verts, faces, samples, seed, points):
+    """(points, their face normals or None): the vertices, area-weighted samples, or the points given."""
+    if points is not None:
+        return points, None
+    if samples is None:
+        return verts, None
+    pts, idx = sample_surface(verts, faces, samples, seed)
+    nrm = face_normals(verts, faces)
+    return pts, nrm[idx]
+
+
+def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None):
+    """How far surface a is from surface b.  The sample set of each mesh is its vertices (``samples=None``), ``samples`` area-weighted
+    points (``sample_surface`` with ``seed`` for a and ``seed + 1`` for b) or the points given (``points_a`` / ``points_b``).  With
+    ``d_ab`` the exact distances of a's samples to mesh b and ``d_ba`` those of b's samples to mesh a (``closest_point``; non-finite
+    distances are left out and counted in ``skipped_ab`` / ``skipped_ba``), the result is a dict of plain floats and per-threshold lists:
+
+    - ``mean_ab``, ``rms_ab``, ``max_ab`` and ``mean_ba``, ``rms_ba``, ``max_ba``: mean, root mean square and maximum per direction;
+    - ``chamfer = (mean_ab + mean_ba) / 2``;  ``chamfer_sq = mean(d_ab^2) + mean(d_ba^2)``;  ``hausdorff = max(max_ab, max_ba)``;
+    - ``thresholds``: the values used (default: 0.5 %, 1 % and 2 % of the larger bounding-box diagonal of the two meshes; at most 8);
+      ``precision[k]`` = share of a's samples within ``thresholds[k]`` of b, ``recall[k]`` = share of b's samples within it of a,
+      ``fscore[k] = 2 P R / (P + R)`` (0 when ``P + R = 0``);
+    - ``normal_consistency``: mean over both directions of ``|n . n'|`` between the normal of the sample's own face and the normal of
+      the closest face of the other mesh; it needs samples that know their face, so it is None unless ``samples`` is given;
+    - ``n_a``, ``n_b``: the numbers of samples.
+
+    Device meshes run on the kernels (one ``TriangleGrid`` per mesh, ia_distance_stats for the sums); CPU tensors and NumPy arrays take
+    the NumPy restatements."""
+    _mesh_args(verts_a, faces_a)
+    _mesh_args(verts_b, faces_b)
+    on_dev = isinstance(verts_a, torch.Tensor) and verts_a.is_cuda
+    if thresholds is None:
+        diag = 0.0
+        for v in (verts_a, verts_b):
+            x = torch.as_tensor(_np(v) if not on_dev else v).float()
+            x = x[torch.isfinite(x).all(1)]
+            if x.shape[0]:
+                diag = max(diag, float((x.amax(0) - x.amin(0)).double().norm()))
+        thresholds = [0.005 * diag, 0.01 * diag, 0.02 * diag]
+    thresholds = [float(F32(t)) for t in thresholds]
+    if len(thresholds) > 8:
+        raise ValueError(f'at most 8 thresholds, got {len(thresholds)}')
+    pa, na = _sample_set(verts_a, faces_a, samples, seed, points_a)
+    pb, nb = _sample_set(verts_b, faces_b, samples, seed + 1, points_b)
+    fn_a = face_normals(verts_a, faces_a) if na is not None else None
+    fn_b = face_normals(verts_b, faces_b) if nb is not None else None
+    if on_dev:
+        from . import hipops
+        grid_a, grid_b = TriangleGrid(verts_a, faces_a), TriangleGrid(verts_b, faces_b)
+        stats = []
+        for pts, nrm, grid, fn in ((pa, na, grid_b, fn_b), (pb, nb, grid_a, fn_a)):
+            r = grid.closest(pts)
+            if nrm is not None:
+                s = hipops.distance_stats(r['dist'], thresholds, r['face'].int(), nrm.float().contiguous(), fn.float().contiguous())
+            else:
+                s = hipops.distance_stats(r['dist'], thresholds)
+            stats.append(s)
+        s_ab, s_ba = torch.stack(stats).cpu().numpy()
+    else:
+        out = []
+        for pts, nrm, v, f, fn in ((pa, na, verts_b, faces_b, fn_b), (pb, nb, verts_a, faces_a, fn_a)):
+            r = closest_point(_np(pts), _np(v), _np(f))
+            out.append(_stats_numpy(r['dist'], thresholds, *((r['face'], _np(nrm), _np(fn)) if nrm is not None else ())))
+        s_ab, s_ba = out
+
+    def direction(s):
+        cnt = s[0]
+        if cnt == 0:
+            return float('nan'), float('nan'), float('nan'), float('nan'), [0.0] * len(thresholds)
+        return s[1] / cnt, s[2] / cnt, float(np.sqrt(s[2] / cnt)), s[3], [float(s[6 + k] / cnt) for k in range(len(thresholds))]
+    mean_ab, sq_ab, rms_ab, max_ab, prec = direction(s_ab)
+    mean_ba, sq_ba, rms_ba, max_ba, rec = direction(s_ba)
+    res = {'mean_ab': float(mean_ab), 'rms_ab': rms_ab, 'max_ab': float(max_ab), 'mean_ba': float(mean_ba), 'rms_ba': rms_ba,
+           'max_ba': float(max_ba), 'chamfer': float((mean_ab + mean_ba) / 2), 'chamfer_sq': float(sq_ab + sq_ba),
+           'hausdorff': float(max(max_ab, max_ba)), 'thresholds': thresholds, 'precision': prec, 'recall': rec,
+           'fscore': [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(prec, rec)],
+           'normal_consistency': None, 'n_a': int(s_ab[0] + s_ab[5]), 'n_b': int(s_ba[0] + s_ba[5]),
+           'skipped_ab': int(s_ab[5]), 'skipped_ba': int(s_ba[5])}
+    if na is not None and nb is not None and s_ab[0] + s_ba[0] > 0:
+        res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
+    return res
 
 
 # ------------------------------------------------------------------ generator-level helpers

@@ -1566,3 +1566,114 @@ def image_metrics(a, b, data_range, levels=5):
                                   _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_image_metrics')
     return out
+
+
+# ------------------------------------------------------------------ surface distance (csrc/surface_distance.hip)
+
+def _f3(values):
+    return (ctypes.c_float * 3)(*[float(v) for v in values])
+
+
+def _i3(values):
+    return (ctypes.c_int * 3)(*[int(v) for v in values])
+
+
+def tri_pack(verts, faces):
+    """Packed triangles (see ia_tri_pack): verts float32 [V,3], faces int32 [F,3] -> float32 [F,3,4]."""
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise RuntimeError(f'verts [V,3] and faces [F,3] on one device, got {tuple(verts.shape)} and {tuple(faces.shape)}')
+    dev = verts.device
+    tris = torch.empty(faces.shape[0], 3, 4, device=dev)
+    with torch.cuda.device(dev), _Timed('tri_pack', 0.0, 84.0 * faces.shape[0], f'F={faces.shape[0]}'):
+        st = _lib.load().ia_tri_pack(_p(verts), verts.shape[0], _p(faces), faces.shape[0], _p(tris), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_tri_pack')
+    return tris
+
+
+def trigrid_plan(n_faces, lo, hi, cells=None):
+    """Grid dimensions and inverse cell sizes for a mesh of ``n_faces`` triangles in the box [lo, hi] (host arithmetic, see
+    ia_trigrid_plan).  ``cells``: None, an int or a triple fixes the cells per axis."""
+    req = (0, 0, 0) if cells is None else ((int(cells),) * 3 if isinstance(cells, int) else tuple(int(c) for c in cells))
+    if len(req) != 3 or (cells is not None and min(req) < 1):
+        raise ValueError(f'cells must be None, an int >= 1 or three of them, got {cells!r}')
+    dims, inv = (ctypes.c_int * 3)(), (ctypes.c_float * 3)()
+    _lib.check(_lib.load().ia_trigrid_plan(int(n_faces), _f3(lo), _f3(hi), _i3(req), dims, inv), 'ia_trigrid_plan')
+    return tuple(dims), tuple(inv)
+
+
+def trigrid_build(tris, lo, inv_cell, dims):
+    """The CSR cell lists of packed triangles (see ia_trigrid_count / ia_trigrid_fill): -> (cell_start int32 [ncell + 2], cell_tris
+    int32 [entries + n_over], entries, n_over).  One host synchronisation (the two totals)."""
+    _f32c(tris, 'tris')
+    f = tris.shape[0]
+    dev = tris.device
+    ncell = int(dims[0]) * int(dims[1]) * int(dims[2])
+    lib = _lib.load()
+    clo, cinv, cdims = _f3(lo), _f3(inv_cell), _i3(dims)
+    cell_start = torch.empty(ncell + 2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _Timed('trigrid_count', 0.0, 48.0 * f + 8.0 * ncell, f'F={f} cells={tuple(dims)}'):
+            st = lib.ia_trigrid_count(_p(tris), f, clo, cinv, cdims, _p(cell_start), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_trigrid_count')
+        entries, n_over = (int(v) for v in cell_start[ncell:].cpu())
+        cell_tris = torch.empty(max(entries + n_over, 1), dtype=torch.int32, device=dev)
+        scratch = torch.empty(ncell + 1, dtype=torch.int32, device=dev)
+        with _Timed('trigrid_fill', 0.0, 48.0 * f + 8.0 * ncell + 4.0 * entries, f'F={f} entries={entries} oversize={n_over}'):
+            st = lib.ia_trigrid_fill(_p(tris), f, clo, cinv, cdims, _p(cell_start), entries, n_over, _p(scratch), scratch.numel() * 4,
+                                     _p(cell_tris), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_trigrid_fill')
+    return cell_start, cell_tris, entries, n_over
+
+
+def closest_point(points, tris, mesh_extent, grid=None):
+    """Closest triangle per point (see ia_closest_point): points float32 [N,3], tris from ``tri_pack`` -> (dist [N], face int32 [N],
+    point [N,3]).  ``grid``: (lo, inv_cell, dims, cell_start, cell_tris, entries, n_over), or None for the brute mode."""
+    _f32c(points, 'points')
+    _f32c(tris, 'tris')
+    if points.dim() != 2 or points.shape[1] != 3 or points.device != tris.device:
+        raise RuntimeError(f'points must be [N,3] on the device of the triangles, got {tuple(points.shape)} on {points.device}')
+    n, f, dev = points.shape[0], tris.shape[0], points.device
+    dist = torch.empty(n, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    point = torch.empty(n, 3, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev), _Timed('closest_point', 0.0, 32.0 * n, f'N={n} F={f} {"brute" if grid is None else tuple(grid[2])}'):
+        if grid is None:
+            st = lib.ia_closest_point(_p(points), n, _p(tris), f, float(mesh_extent), None, None, None, None, None, 0, 0, _p(dist), _p(face),
+                                      _p(point), _lib.stream_ptr(dev))
+        else:
+            lo, inv, dims, cell_start, cell_tris, entries, n_over = grid
+            st = lib.ia_closest_point(_p(points), n, _p(tris), f, float(mesh_extent), _f3(lo), _f3(inv), _i3(dims), _p(cell_start),
+                                      _p(cell_tris), int(entries), int(n_over), _p(dist), _p(face), _p(point), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_closest_point')
+    return dist, face, point
+
+
+def distance_stats(dist, thresholds=(), face=None, normals_a=None, normals_b=None):
+    """Reductions of a distance array (see ia_distance_stats): float64 device tensor [14] = finite count, sum, sum of squares, max,
+    sum |n_a . n_b|, non-finite count, counts <= thresholds[k]."""
+    _f32c(dist, 'dist')
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > 8:
+        raise ValueError(f'at most 8 thresholds per call, got {len(thresholds)}')
+    n, dev = dist.numel(), dist.device
+    with_normals = face is not None
+    if with_normals:
+        _i32c(face, 'face')
+        _f32c(normals_a, 'normals_a')
+        _f32c(normals_b, 'normals_b')
+        if face.numel() != n or tuple(normals_a.shape) != (n, 3) or normals_b.dim() != 2 or normals_b.shape[1] != 3:
+            raise RuntimeError('face [N], normals_a [N,3] and normals_b [Fb,3] do not match the distances')
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_distance_stats_scratch_bytes(n, ctypes.byref(nbytes)), 'ia_distance_stats_scratch_bytes')
+    scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(14, dtype=torch.float64, device=dev)
+    thr = (ctypes.c_float * max(len(thresholds), 1))(*thresholds)
+    with torch.cuda.device(dev), _Timed('distance_stats', 0.0, (32.0 if with_normals else 4.0) * n, f'N={n}'):
+        st = lib.ia_distance_stats(_p(dist), n, thr, len(thresholds), _p(face), _p(normals_a), _p(normals_b),
+                                   normals_b.shape[0] if with_normals else 0, _p(scratch), scratch.numel() * 8, _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_distance_stats')
+    return out

@@ -972,6 +972,70 @@ int ia_distance_stats(const float* dist, int64_t N, const float* h_thresholds, i
                       const float* normals_a, const float* normals_b, int64_t Fb, void* scratch, size_t scratch_bytes, double* out,
                       void* stream);
 
+/*
+ * Mesh simplification by quadric vertex clustering (csrc/simplify.hip; no counterpart in the reference; the definition is written out
+ * in invertavatar_amd/geometry.py simplify_mesh and DESIGN.md 4.15).  Additive entry points: the ABI version is unchanged.
+ *
+ * The cell of a coordinate is the fp32 function of ia_trigrid_plan, clamp(floor((x - lo) * inv_cell), 0, dims - 1); the key of a vertex
+ * is its linear cell index (x slowest) as int64, INT64_MAX for a vertex with a non-finite coordinate.  V, F <= 2^28, dims <= 2^20.
+ *
+ * ia_simplify_plan (host arithmetic only): exactly one of cells[3] (cells per axis), cells_long (cubic cells, that many along the
+ * longest axis of the box) and cell_size (the edge) is given (NULL / 0 / 0.0 otherwise) -> dims[3], inv_cell[3] = fp32(1 / cell), cell[3]
+ * (double edge per axis; an axis without extent has the edge 1 under cells[3]).
+ * ia_simplify_box: box = device float [6], lo and hi of the finite vertices (+inf / -inf without one).  scratch: 24576 bytes.
+ * ia_simplify_keys: keys int64 [V].
+ * ia_simplify_clusters: from the sorted keys and the permutation that sorted them (int64 [V] both): vert_cluster int32 [V] (ordinal of
+ * the vertex's cluster in ascending key order, -1 without a cell), sorted_cluster int32 [V] (the same by sorted position, INT32_MAX
+ * without a cell), cluster_start int32 [capacity + 1] (first sorted position; cluster_start[K] = number of vertices with a cell),
+ * cluster_key int64 [capacity], count = device int [2]: K and the number of vertices with a cell.  scratch: 4 (V + 1) bytes.
+ * ia_simplify_classify: per face (int32 [F,3]; an index outside [0, V) makes it unusable) tri int32 [F,3] (the three cluster ordinals
+ * rotated smallest first, INT32_MAX x 3 unless the face is usable with three different clusters), key int64 [F] ((a K + b) K + c, or
+ * b K + c when K^3 >= 9e18: sort by key, then stably by a; INT64_MAX for a face that does not survive), ref int32 [K] (1 for a cluster
+ * of a surviving face; may be NULL), pairs int32 [3 F] (per corner the cluster the face's quadric goes to, INT32_MAX for an unusable
+ * face or a cluster an earlier corner named; may be NULL), count = device int [3]: usable faces, surviving faces, pairs.
+ * ia_simplify_face_heads: perm int64 [F] sorts the faces by tri -> face_pos int32 [F + 1]: exclusive count of unique surviving
+ * triples before each sorted position, face_pos[F] = F'.       ia_simplify_refs: out_index int32 [K + 1] = exclusive scan of ref.
+ * ia_simplify_outputs: vertex_map int64 [V]; for each of the out_index[K] output vertices (at most capacity are written) out_cluster
+ * int32 and cluster_size int64.       ia_simplify_faces: faces_out int64 [capacity,3], unique, lexicographically increasing.
+ * ia_simplify_accumulate_verts: sums double [K,4]: per cluster the sums of columns col0 .. col0 + ncols (<= 4) of cols double [V,ld]
+ * over its vertices, n = number of vertices with a cell.  ia_simplify_accumulate_faces: sums double [K,9]: per cluster the sum over its
+ * pairs (pair_order int64 [>= n] and sorted_pairs int32 [>= n]: the stable sort of pairs, n = count[2]) of n n^T (xx xy xz yy yz zz)
+ * and -n (n . (A - centre)), n the normal from the two shorter edges, centre the centre of the cluster's cell, all in double.  Both:
+ * chunks of 32 entries in index order, partial rows reduced level by level; no floating-point atomics, bit-equal from run to run.
+ * scratch: ia_simplify_accumulate_scratch_bytes(n, 4 or 9) bytes, 8-byte aligned.
+ * ia_simplify_place: verts_out float32 [n_out,3]: the cluster mean (quadric_sums NULL) or the minimiser of the summed quadric about
+ * the mean (cyclic Jacobi, 8 sweeps; eigenvalues <= 1e-3 of the largest dropped) clamped to the cell.
+ * ia_simplify_means: out[o, col0 .. col0 + ncols) = sums / cluster size, out double [capacity, ld].
+ */
+int ia_simplify_plan(const float* h_lo, const float* h_hi, const int* h_cells, int cells_long, double cell_size, int* h_dims,
+                     float* h_inv_cell, double* h_cell);
+int ia_simplify_box(const float* verts, int64_t V, void* scratch, size_t scratch_bytes, float* box, void* stream);
+int ia_simplify_keys(const float* verts, int64_t V, const float* h_lo, const float* h_inv_cell, const int* h_dims, int64_t* keys,
+                     void* stream);
+int ia_simplify_clusters(const int64_t* sorted_keys, const int64_t* order, int64_t V, int* vert_cluster, int* sorted_cluster,
+                         int* cluster_start, int64_t* cluster_key, int64_t capacity, void* scratch, size_t scratch_bytes, int* count,
+                         void* stream);
+int ia_simplify_classify(const int* faces, int64_t F, int64_t V, const int* vert_cluster, int K, int* tri, int64_t* key, int* ref,
+                         int* pairs, int* count, void* stream);
+int ia_simplify_face_heads(const int* tri, const int64_t* perm, int64_t F, int* face_pos, void* stream);
+int ia_simplify_refs(const int* ref, int K, int* out_index, void* stream);
+int ia_simplify_outputs(const int* vert_cluster, int64_t V, const int* ref, const int* out_index, const int* cluster_start, int K,
+                        int64_t* vertex_map, int* out_cluster, int64_t* cluster_size, int64_t capacity, void* stream);
+int ia_simplify_faces(const int* tri, const int64_t* perm, const int* face_pos, int64_t F, const int* out_index, int K,
+                      int64_t* faces_out, int64_t capacity, void* stream);
+int ia_simplify_accumulate_scratch_bytes(int64_t n, int width, size_t* h_bytes);
+int ia_simplify_accumulate_verts(const double* cols, int ld, int col0, int ncols, const int64_t* order, const int* sorted_cluster,
+                                 int64_t n, int64_t V, int K, double* sums, void* scratch, size_t scratch_bytes, void* stream);
+int ia_simplify_accumulate_faces(const float* verts, int64_t V, const int* faces, int64_t F, const int64_t* pair_order,
+                                 const int* sorted_pairs, int64_t n, const int64_t* cluster_key, int K, const float* h_lo,
+                                 const float* h_inv_cell, const double* h_cell, const int* h_dims, double* sums, void* scratch,
+                                 size_t scratch_bytes, void* stream);
+int ia_simplify_place(const double* vert_sums, const double* quadric_sums, const int* out_cluster, const int* cluster_start,
+                      const int64_t* cluster_key, int K, int64_t n_out, const float* h_lo, const float* h_inv_cell, const double* h_cell,
+                      const int* h_dims, float* verts_out, int64_t capacity, void* stream);
+int ia_simplify_means(const double* vert_sums, const int* out_cluster, const int* cluster_start, int K, int64_t n_out, int ncols,
+                      double* out, int ld, int col0, int64_t capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

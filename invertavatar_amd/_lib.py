@@ -126,6 +126,25 @@ _SIGNATURES = {
     'ia_distance_stats_scratch_bytes': [c_int64, ctypes.POINTER(ctypes.c_size_t)],
     'ia_distance_stats': [c_void_p, c_int64, _f32p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p,
                           c_void_p],
+    'ia_simplify_plan': [_f32p, _f32p, ctypes.POINTER(c_int), c_int, ctypes.c_double, ctypes.POINTER(c_int), _f32p,
+                         ctypes.POINTER(ctypes.c_double)],
+    'ia_simplify_box': [c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_simplify_keys': [c_void_p, c_int64, _f32p, _f32p, ctypes.POINTER(c_int), c_void_p, c_void_p],
+    'ia_simplify_clusters': [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, ctypes.c_size_t,
+                             c_void_p, c_void_p],
+    'ia_simplify_classify': [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_simplify_face_heads': [c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_simplify_refs': [c_void_p, c_int, c_void_p, c_void_p],
+    'ia_simplify_outputs': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    'ia_simplify_faces': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p],
+    'ia_simplify_accumulate_scratch_bytes': [c_int64, c_int, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_simplify_accumulate_verts': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                     ctypes.c_size_t, c_void_p],
+    'ia_simplify_accumulate_faces': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, _f32p, _f32p,
+                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int), c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
+    'ia_simplify_place': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, _f32p, _f32p, ctypes.POINTER(ctypes.c_double),
+                          ctypes.POINTER(c_int), c_void_p, c_int64, c_void_p],
+    'ia_simplify_means': [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p],
 }
 
 

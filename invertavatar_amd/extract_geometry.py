@@ -11,7 +11,10 @@ volume first, so the PLY, the views and the saved depth show the N largest only;
 than M lattice points; a line per seed reports how many components there were and the sizes of the kept ones.  ``--compare REF.ply``
 prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh against ``REF.ply`` and writes them as
 ``seed%04d_geometry.json`` (``geometry_metrics.compare_meshes``); ``--error-ply`` also writes ``seed%04d_error.ply``, the mesh coloured by
-its distance to the reference.  Runs on the device when there is one."""
+its distance to the reference.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
+clustering; the line per seed then shows the triangle counts before and after), ``--simplify-cells C`` to a grid of C cells along the
+longest axis; ``--simplify-check`` scores the simplified mesh against the full one (``geometry.surface_distance``), prints both directed
+Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -74,6 +77,10 @@ def main(argv=None):
     ap.add_argument('--min-voxels', type=int, default=0, help='with --keep: also drop kept components of fewer lattice points')
     ap.add_argument('--compare', default=None, metavar='REF.ply', help='score the extracted mesh against this mesh (Chamfer, Hausdorff, F-score)')
     ap.add_argument('--error-ply', action='store_true', help='with --compare: also write the mesh coloured by its distance to REF.ply')
+    grp = ap.add_mutually_exclusive_group()
+    grp.add_argument('--simplify', type=int, default=None, metavar='N', help='simplify the mesh to at most N triangles')
+    grp.add_argument('--simplify-cells', type=int, default=None, metavar='C', help='simplify on a grid of C cells along the longest axis')
+    ap.add_argument('--simplify-check', action='store_true', help='with --simplify / --simplify-cells: distance of the simplified mesh to the full one')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -81,14 +88,35 @@ def main(argv=None):
     os.makedirs(args.outdir, exist_ok=True)
     ws, _ = seed_latents(G, args.seeds, args.trunc, args.trunc_cutoff)
     results = []
+    simplify = args.simplify if args.simplify is not None else ({'cells': args.simplify_cells} if args.simplify_cells is not None else None)
+    if args.simplify_check and simplify is None:
+        ap.error('--simplify-check needs --simplify or --simplify-cells')
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
-                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, noise_mode='const')[0]
+                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, noise_mode='const')[0]
         path = os.path.join(args.outdir, f'seed{seed:04d}.ply')
         geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'), out.get('normals'))
         if args.save_volume:
             np.save(os.path.join(args.outdir, f'seed{seed:04d}.npy'), out['volume'].cpu().numpy())
         print(f'seed {seed}: {out["verts"].shape[0]} vertices, {out["faces"].shape[0]} triangles -> {path}')
+        if 'simplify' in out:
+            info = out['simplify']
+            print(f'seed {seed}: simplified {info["faces_before"]} -> {info["faces_after"]} triangles, {info["verts_before"]} -> '
+                  f'{info["verts_after"]} vertices, grid {info["dims"]}, cell {info["cell_size"]:.6g}')
+            meta = {'simplify': dict(info)}
+            if args.simplify_check:
+                full = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, keep=args.keep, min_voxels=args.min_voxels,
+                                          noise_mode='const')[0]
+                samples = 200000 if out['verts'].is_cuda else 2000                # (the host route is brute force)
+                d = geometry.surface_distance(out['verts'], out['faces'], full['verts'], full['faces'], samples=samples)
+                diag = float(np.sqrt(3.0) * info['cell_size'])
+                meta['simplify']['check'] = {'simplified_to_full': d['max_ab'], 'full_to_simplified': d['max_ba'], 'chamfer': d['chamfer'],
+                                             'cell_diagonal': diag}
+                print(f'seed {seed}: Hausdorff simplified -> full {d["max_ab"]:.6g}, full -> simplified {d["max_ba"]:.6g}, cell diagonal '
+                      f'{diag:.6g}, Chamfer {d["chamfer"]:.6g}')
+            out['simplify'] = meta['simplify']
+            with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
+                json.dump(meta, fh, indent=1)
         if 'components' in out:
             info = out['components']
             sizes = [int(info['stats'][c - 1, 0]) for c in info['kept']]
@@ -99,7 +127,7 @@ def main(argv=None):
             err = os.path.join(args.outdir, f'seed{seed:04d}_error.ply') if args.error_ply else None
             out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err)
             with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
-                json.dump(out['metrics'], fh, indent=1)
+                json.dump(dict(out['metrics'], simplify=out['simplify']) if 'simplify' in out else out['metrics'], fh, indent=1)
             print(f'seed {seed}: against {args.compare}: {geometry_metrics.summary(out["metrics"])}')
         if args.views > 0:
             from PIL import Image

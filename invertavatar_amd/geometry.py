@@ -22,6 +22,9 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   Hausdorff distance, F-score, normal consistency), with ``face_normals`` and ``sample_surface``.  Device tensors go to ``ia_tri_pack`` +
   ``ia_trigrid_count`` / ``ia_trigrid_fill`` + ``ia_closest_point`` + ``ia_distance_stats``; CPU tensors and NumPy arrays take a NumPy
   restatement (``point_triangle``: the kernel's per-triangle function line by line, float64; brute force over all triangles).
+- ``simplify_mesh``: quadric vertex clustering on a uniform grid, to a cell size or to a target face count.  Device tensors go to the
+  kernels of csrc/simplify.hip (``ia_simplify_*``; the sorts of integer keys are ``torch.sort``); CPU tensors and NumPy arrays take the
+  NumPy restatement that is the definition (float64).
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
@@ -886,6 +889,346 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     if na is not None and nb is not None and s_ab[0] + s_ba[0] > 0:
         res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
     return res
+
+
+# ------------------------------------------------------------------ simplification
+
+_NO_CELL = np.iinfo(np.int64).max
+_JACOBI_SWEEPS = 8
+
+
+def _simplify_plan(lo, hi, cells=None, cell_size=None):
+    """Host arithmetic of ia_simplify_plan: (dims, inv_cell float32 [3], cell float64 [3]) from the box of the finite vertices."""
+    ext = [float(hi[a]) - float(lo[a]) for a in range(3)]
+    longest = max(ext)
+    dims, inv, cell = [], [], []
+    for a in range(3):
+        if cells is not None and not np.isscalar(cells):
+            n = int(cells[a])
+            h = ext[a] / n if ext[a] > 0 else 1.0
+        else:
+            h = float(cell_size) if cells is None else (longest / int(cells) if longest > 0 else 1.0)
+            n = max(1, int(np.ceil(ext[a] / h)))
+            if cells is not None and longest > 0 and ext[a] == longest:
+                n = int(cells)
+        if n > 1 << 20:
+            raise ValueError(f'more than 2^20 cells along axis {a}')
+        i = F32(1.0 / h)
+        if not (np.isfinite(i) and i > 0):
+            raise ValueError(f'the cell size {h} has no float32 inverse')
+        dims.append(n), inv.append(i), cell.append(h)
+    return tuple(dims), np.asarray(inv, dtype=F32), np.asarray(cell, dtype=np.float64)
+
+
+def _simplify_keys_numpy(v32, lo, inv, dims):
+    """Linear cell index (x slowest, z fastest) per vertex in int64, ``_NO_CELL`` for a vertex with a non-finite coordinate; the cell
+    per axis is the fp32 ``clamp(floor((x - lo) * inv), 0, n - 1)`` of TriangleGrid."""
+    fin = np.isfinite(v32).all(1)
+    c = []
+    with np.errstate(invalid='ignore', over='ignore'):
+        for a in range(3):
+            t = np.floor((np.where(fin, v32[:, a], F32(0)) - F32(lo[a])) * F32(inv[a]))
+            c.append(np.minimum(np.maximum(t, F32(0)), F32(dims[a] - 1)).astype(np.int64))
+    return np.where(fin, (c[0] * dims[1] + c[1]) * dims[2] + c[2], _NO_CELL)
+
+
+def _simplify_topology_numpy(keys, faces):
+    """The integer part of the definition from per-vertex keys: clusters in ascending key order, usable and surviving faces, the
+    referenced clusters and their output indices, the rotated, unique, sorted output faces."""
+    valid = keys != _NO_CELL
+    ckey, inverse = np.unique(keys[valid], return_inverse=True)
+    k = ckey.size
+    vcl = np.full(keys.shape[0], -1, dtype=np.int64)
+    vcl[valid] = inverse
+    c = vcl[faces]                                                       # [F,3]
+    usable = (c >= 0).all(1)
+    surv = usable & (c[:, 0] != c[:, 1]) & (c[:, 1] != c[:, 2]) & (c[:, 0] != c[:, 2])
+    ref = np.zeros(k, dtype=bool)
+    ref[c[surv].reshape(-1)] = True
+    outidx = np.cumsum(ref) - 1
+    t = c[surv]
+    first = np.argmin(t, axis=1)[:, None]
+    t = np.take_along_axis(t, (first + np.arange(3)[None]) % 3, axis=1)  # smallest first, orientation kept
+    t = np.unique(t, axis=0) if t.shape[0] else t.reshape(0, 3)          # unique rows, lexicographically increasing
+    return {'K': k, 'ckey': ckey, 'vcl': vcl, 'c': c, 'usable': usable, 'n_usable': int(usable.sum()), 'ref': ref, 'outidx': outidx,
+            'tri': t, 'faces': outidx[t].astype(np.int64).reshape(-1, 3),
+            'vertex_map': np.where((vcl >= 0) & ref[np.maximum(vcl, 0)] if k else np.zeros(vcl.shape, bool), outidx[np.maximum(vcl, 0)] if k else -1, -1).astype(np.int64),
+            'cluster_size': np.bincount(vcl[valid], minlength=k)[ref].astype(np.int64)}
+
+
+def _cluster_sums(idx, rows, k):
+    """Per cluster the float64 sums of ``rows`` [n,C] over the entries with cluster ``idx``, each added in index order."""
+    return np.stack([np.bincount(idx, weights=rows[:, j], minlength=k) for j in range(rows.shape[1])], -1) if rows.shape[1] else np.zeros((k, 0))
+
+
+def _cell_centres(ckey, lo, cell, dims):
+    ijk = np.stack([ckey // (dims[2] * dims[1]), (ckey // dims[2]) % dims[1], ckey % dims[2]], -1).astype(np.float64)
+    return np.asarray(lo, dtype=F32).astype(np.float64)[None] + (ijk + 0.5) * cell[None]
+
+
+def _quadric_sums_numpy(v64, faces, top, lo, cell, dims):
+    """float64 [K,9]: n n^T (xx xy xz yy yz zz) and -n (n . (A - centre)) of every usable face, added once to each distinct cluster among
+    its corners (in the order face, corner); n: the cross product of the two shorter edges (as ``point_triangle``), centre: the centre
+    of the cluster's cell."""
+    f = faces[top['usable']]
+    c = top['c'][top['usable']]
+    A, B, C = v64[f[:, 0]], v64[f[:, 1]], v64[f[:, 2]]
+    eab, ebc, eca = B - A, C - B, A - C
+    lab, lbc, lca = _dot3(eab, eab), _dot3(ebc, ebc), _dot3(eca, eca)
+    ab_longest, bc_longest = (lab >= lbc) & (lab >= lca), lbc >= lca
+    n = np.where(ab_longest[:, None], _cross3(ebc, eca), np.where(bc_longest[:, None], _cross3(eca, eab), _cross3(eab, ebc)))
+    take = np.stack([np.ones(len(f), bool), c[:, 1] != c[:, 0], (c[:, 2] != c[:, 0]) & (c[:, 2] != c[:, 1])], -1)       # [U,3]
+    fi, ji = np.nonzero(take)                                           # in the order (face, corner)
+    cl = c[fi, ji]
+    nn = n[fi]
+    d = _dot3(nn, A[fi] - _cell_centres(top['ckey'][cl], lo, cell, dims))
+    rows = np.stack([nn[:, 0] * nn[:, 0], nn[:, 0] * nn[:, 1], nn[:, 0] * nn[:, 2], nn[:, 1] * nn[:, 1], nn[:, 1] * nn[:, 2],
+                     nn[:, 2] * nn[:, 2], -(nn[:, 0] * d), -(nn[:, 1] * d), -(nn[:, 2] * d)], -1)
+    return _cluster_sums(cl, rows, top['K'])
+
+
+def _quadric_place_numpy(q, m, cell):
+    """csrc/simplify.hip place_kernel line by line (float64): q [n,9] summed quadrics, m [n,3] cluster means, both relative to the cell
+    centre -> the representative relative to the centre.  Cyclic Jacobi with ``_JACOBI_SWEEPS`` fixed sweeps over (0,1), (0,2), (1,2);
+    ``x = m + sum_j v_j (v_j . r) / lambda_j`` over the eigenvalues ``> 1e-3 lambda_max``, ``r = -b - A m``; clamped to the cell."""
+    n = q.shape[0]
+    a = np.zeros((n, 3, 3))
+    a[:, 0, 0], a[:, 0, 1], a[:, 0, 2], a[:, 1, 1], a[:, 1, 2], a[:, 2, 2] = (q[:, j] for j in range(6))
+    a[:, 1, 0], a[:, 2, 0], a[:, 2, 1] = a[:, 0, 1], a[:, 0, 2], a[:, 1, 2]
+    zero = (q[:, :6] == 0).all(1)
+    with np.errstate(all='ignore'):
+        r = np.stack([-q[:, 6 + i] - ((a[:, i, 0] * m[:, 0] + a[:, i, 1] * m[:, 1]) + a[:, i, 2] * m[:, 2]) for i in range(3)], -1)
+        v = np.tile(np.eye(3), (n, 1, 1))
+        for _ in range(_JACOBI_SWEEPS):
+            for p, qq in ((0, 1), (0, 2), (1, 2)):
+                rr = 3 - p - qq
+                apq = a[:, p, qq].copy()
+                on = apq != 0
+                theta = (a[:, qq, qq] - a[:, p, p]) / (2.0 * np.where(on, apq, 1.0))
+                t = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                c, s, t = np.where(on, c, 1.0), np.where(on, s, 0.0), np.where(on, t, 0.0)
+                a[:, p, p] = np.where(on, a[:, p, p] - t * apq, a[:, p, p])
+                a[:, qq, qq] = np.where(on, a[:, qq, qq] + t * apq, a[:, qq, qq])
+                a[:, p, qq] = a[:, qq, p] = np.where(on, 0.0, apq)
+                arp, arq = a[:, rr, p].copy(), a[:, rr, qq].copy()
+                a[:, rr, p] = a[:, p, rr] = np.where(on, c * arp - s * arq, arp)
+                a[:, rr, qq] = a[:, qq, rr] = np.where(on, s * arp + c * arq, arq)
+                vp, vq = v[:, :, p].copy(), v[:, :, qq].copy()
+                v[:, :, p] = np.where(on[:, None], c[:, None] * vp - s[:, None] * vq, vp)
+                v[:, :, qq] = np.where(on[:, None], s[:, None] * vp + c[:, None] * vq, vq)
+        lam = np.stack([a[:, 0, 0], a[:, 1, 1], a[:, 2, 2]], -1)
+        lmax = lam.max(1)
+        x = m.copy()
+        for j in range(3):
+            use = ~zero & (lmax > 0) & (lam[:, j] > 1e-3 * lmax)
+            w = ((v[:, 0, j] * r[:, 0] + v[:, 1, j] * r[:, 1]) + v[:, 2, j] * r[:, 2]) / np.where(use, lam[:, j], 1.0)
+            x = np.where(use[:, None], x + v[:, :, j] * w[:, None], x)
+        half = 0.5 * cell[None]
+        return np.where(np.isnan(x), m, np.minimum(np.maximum(x, -half), half))
+
+
+def _cast_extra(mean, like):
+    dt = like.dtype
+    if isinstance(mean, torch.Tensor):
+        return (mean.round() if not dt.is_floating_point else mean).to(dt)
+    return (np.rint(mean) if not np.issubdtype(dt, np.floating) else mean).astype(dt)
+
+
+def _simplify_numpy(verts, faces, grid, placement='quadric', extras=(), as64=False):
+    """The definition of ``simplify_mesh`` on NumPy arrays, float64.  ``grid``: (dims, lo, inv_cell, cell) or None for the identity
+    clustering (every vertex with finite coordinates is a cluster of its own, in index order).  ``as64`` returns the positions before they are
+    rounded to float32 (the tests take the definition's own sensitivity to the order of summation from two such runs)."""
+    v32 = np.ascontiguousarray(verts, dtype=F32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    nv = v32.shape[0]
+    if grid is None:
+        keys = np.where(np.isfinite(v32).all(1), np.arange(nv, dtype=np.int64), _NO_CELL)
+    else:
+        dims, lo, inv, cell = grid
+        keys = _simplify_keys_numpy(v32, lo, inv, dims)
+    top = _simplify_topology_numpy(keys, f)
+    k, ref = top['K'], top['ref']
+    valid = np.flatnonzero(top['vcl'] >= 0)
+    idx = top['vcl'][valid]
+    cnt = np.bincount(idx, minlength=k).astype(np.float64)[ref]
+    v64 = v32.astype(np.float64)
+    mean = _cluster_sums(idx, v64[valid], k)[ref] / cnt[:, None]
+    if grid is None or placement == 'mean' or not ref.any():
+        pos = mean
+    else:
+        cc = _cell_centres(top['ckey'][ref], lo, cell, dims)
+        q = _quadric_sums_numpy(v64, f, top, lo, cell, dims)[ref]
+        pos = cc + _quadric_place_numpy(q, mean - cc, cell)
+    out_extras = []
+    for e in extras:
+        e = np.asarray(e)
+        rows = e.reshape(nv, -1).astype(np.float64)
+        out_extras.append(_cast_extra((_cluster_sums(idx, rows[valid], k)[ref] / cnt[:, None]).reshape((-1,) + e.shape[1:]), e))
+    return {'verts': pos if as64 else pos.astype(F32), 'faces': top['faces'], 'vertex_map': top['vertex_map'], 'cluster_size': top['cluster_size'],
+            'extras': out_extras, 'usable_faces': top['n_usable']}
+
+
+def _simplify_count_numpy(v32, f, grid):
+    dims, lo, inv, cell = grid
+    return _simplify_topology_numpy(_simplify_keys_numpy(v32, lo, inv, dims), f)['faces'].shape[0]
+
+
+def _simplify_device(verts, faces32, grid, placement, extras, count_only=False):
+    """The device route of ``simplify_mesh``: every step is a kernel of csrc/simplify.hip except the three sorts of integer keys
+    (``torch.sort``: vertex keys, face keys, (cluster, face) pairs)."""
+    from . import hipops
+    nv = verts.shape[0]
+    if grid is None:
+        fin = torch.isfinite(verts).all(1)
+        keys = torch.where(fin, torch.arange(nv, device=verts.device), torch.full_like(fin, _NO_CELL, dtype=torch.int64))
+    else:
+        dims, lo, inv, cell = grid
+        keys = hipops.simplify_keys(verts, lo, inv, dims)
+    quadric = grid is not None and placement == 'quadric'
+    s = hipops.simplify_topology(keys, faces32, full=not count_only, pairs=quadric and not count_only)
+    if count_only:
+        return s
+    faces_out, vertex_map, csize, ocl = hipops.simplify_outputs(s)
+    cols = [verts.double()] + [torch.as_tensor(e).to(verts.device).reshape(nv, -1).double() for e in extras]
+    sums = hipops.simplify_vertex_sums(s, torch.cat(cols, 1).contiguous())
+    if grid is None:
+        pos = hipops.simplify_means(s, ocl, sums[:, :3].contiguous()).float()             # clusters of one vertex: the vertex itself
+    else:
+        qsum = hipops.simplify_quadric_sums(s, verts, lo, inv, cell, dims) if quadric else None
+        pos = hipops.simplify_place(s, ocl, sums[:, :3].contiguous(), qsum, lo, inv, cell, dims)
+    out_extras, c0 = [], 3
+    for e in extras:
+        e = torch.as_tensor(e)
+        c = cols[len(out_extras) + 1].shape[1]
+        mean = hipops.simplify_means(s, ocl, sums[:, c0:c0 + c].contiguous()) if c else torch.zeros(ocl.numel(), 0, dtype=torch.float64, device=verts.device)
+        out_extras.append(_cast_extra(mean.reshape((-1,) + tuple(e.shape[1:])), e))
+        c0 += c
+    return {'verts': pos, 'faces': faces_out, 'vertex_map': vertex_map, 'cluster_size': csize, 'extras': out_extras, 'usable_faces': s['usable']}
+
+
+def simplify_mesh(verts, faces, cells=None, cell_size=None, target_faces=None, placement='quadric', extras=(), max_cells=4096):
+    """Simplify a triangle mesh (verts float32 [V,3], faces int64 [F,3]) by quadric vertex clustering on a uniform grid: all vertices
+    of a grid cell become one vertex.  Returns a dict: 'verts' float32 [V',3], 'faces' int64 [F',3], 'vertex_map' int64 [V],
+    'cluster_size' int64 [V'], 'extras' (list), 'dims' (nx, ny, nz), 'cell_size' float, 'lo' (3 floats), 'input_faces' F,
+    'usable_faces', and with ``target_faces`` 'steps' (count-only passes).  Exactly one of ``cells``, ``cell_size``, ``target_faces``:
+
+    - ``cells``: an int c = cubic cells of edge ``h = longest / c``, c of them along the longest axis of the box of the finite vertices
+      and ``max(1, ceil(extent / h))`` along the others; or a triple = cells per axis (edge ``extent / n`` per axis).
+    - ``cell_size``: the edge h of cubic cells, ``max(1, ceil(extent / h))`` per axis.
+    - ``target_faces = n``: if the mesh has at most n usable faces it is returned through the identity clustering (every vertex with
+      finite coordinates is its own cluster, numbered in input order; no grid is run, 'dims' is None and 'cell_size' 0: a plain
+      renumbering that drops unusable and degenerate faces, exact duplicates and unreferenced vertices).  Otherwise the int ``cells``
+      is bisected in [1, ``max_cells``] with a count-only pass (no positions): the result has ``c`` with ``F'(c) <= n`` and either
+      ``F'(c + 1) > n`` or ``c == max_cells``.  F' need not grow monotonically with c; that adjacent pair, not "closest to n", is the
+      contract.
+
+    The definition:
+
+    1. Cells.  ``lo`` and the extents are those of the vertices with three finite coordinates.  The cell of a vertex is, per axis and
+       in fp32, ``clamp(floor((x - lo) * inv), 0, n - 1)`` with ``inv = fp32(1 / h)`` (the function of ``TriangleGrid``); its linear index
+       ``(ix * ny + iy) * nz + iz`` (x slowest, z fastest).  A vertex with a non-finite coordinate has no cell.  A cluster is the set
+       of vertices of one cell.
+    2. A face is usable if its three vertices have cells, and survives if they lie in three different cells.  Indices outside [0, V)
+       raise ``ValueError``, as in ``mesh_components`` and ``closest_point``.
+    3. One output vertex per cell that a surviving face references (none is unreferenced), numbered by ascending linear cell index.
+       ``vertex_map[v]``: the output vertex of input vertex v, -1 if v has no cell or its cell is not referenced; ``cluster_size``:
+       input vertices per output vertex.
+    4. Every surviving face is mapped through ``vertex_map`` and rotated so that its smallest index comes first (orientation kept);
+       exact duplicates are removed and the faces sorted lexicographically.  Two faces on the same three vertices with opposite
+       orientation are both kept.  ``faces``, ``vertex_map`` and ``cluster_size`` are integer functions of the input that do not depend on
+       the order of its vertices and faces.
+    5. ``placement='mean'``: the arithmetic mean of the cluster's vertices (float64, rounded to float32).
+    6. ``placement='quadric'``: every usable face (surviving or not) adds ``(n n^T, -n (n . (A - c)))`` once to each distinct cluster
+       among its corners: n the unnormalised normal from the two shorter edges (as ``point_triangle``; the weight is the squared
+       area), A its first vertex, c the centre of the cluster's cell.  With ``A x = -b`` the summed system and m the cluster mean
+       relative to c, the representative is ``c + clamp(m + A^+ (-b - A m))``: ``A^+`` the pseudo-inverse from a cyclic Jacobi
+       eigen-decomposition (8 fixed sweeps, float64) that drops eigenvalues ``<= 1e-3`` of the largest (Lindstrom, out-of-core
+       simplification), so a planar or creased cluster moves from m only along well-determined directions; the clamp is to the
+       closed box of the cell, ``[-h/2, h/2]`` about c.  A cluster whose matrix is all zero takes m.
+    7. ``extras``: per-vertex arrays [V, ...] are averaged per cluster in float64 and returned in their dtype (integer types rounded
+       to nearest); normals are the caller's to renormalise.
+
+    A result without a surviving face (``cells=1``, V = 0, F = 0) is a valid empty mesh.  Vertex clustering can pinch the surface: the
+    output need not be manifold even if the input is.  Every point of the output lies within one cell diagonal of the input surface.
+
+    Device tensors run on the kernels of csrc/simplify.hip (sums in double, in an order fixed by the data layout: the same bits from
+    run to run); CPU tensors and NumPy arrays take the NumPy restatement of the same definition (float64, positions rounded to
+    float32 at the end)."""
+    _mesh_args(verts, faces)
+    if sum(x is not None for x in (cells, cell_size, target_faces)) != 1:
+        raise ValueError('exactly one of cells, cell_size and target_faces must be given')
+    if placement not in ('quadric', 'mean'):
+        raise ValueError(f"placement must be 'quadric' or 'mean', got {placement!r}")
+    max_cells = int(max_cells)
+    if not 1 <= max_cells <= 1 << 20:
+        raise ValueError(f'max_cells must be in [1, 2^20], got {max_cells}')
+    if cells is not None:
+        cells = int(cells) if np.isscalar(cells) else tuple(int(c) for c in cells)
+        if (np.isscalar(cells) and not 1 <= cells <= 1 << 20) or (not np.isscalar(cells) and (len(cells) != 3 or min(cells) < 1 or max(cells) > 1 << 20)):
+            raise ValueError(f'cells must be an int in [1, 2^20] or three of them, got {cells!r}')
+    if cell_size is not None and not (np.isfinite(float(cell_size)) and float(cell_size) > 0):
+        raise ValueError(f'cell_size must be finite and > 0, got {cell_size!r}')
+    if target_faces is not None and int(target_faces) < 1:
+        raise ValueError(f'target_faces must be >= 1, got {target_faces!r}')
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    for e in extras:
+        if e.shape[0] != nv:
+            raise ValueError(f'an extra has {e.shape[0]} rows for {nv} vertices')
+    on_dev = isinstance(verts, torch.Tensor) and verts.is_cuda
+    if on_dev:
+        from . import hipops
+        v = verts.detach().float().contiguous()
+        if nf and (int(faces.min()) < 0 or int(faces.max()) >= nv):
+            raise ValueError(f'faces index vertices outside [0, {nv})')
+        f = faces.to(device=v.device, dtype=torch.int32).contiguous()
+        box = hipops.simplify_box(v)
+        run = lambda grid: _simplify_device(v, f, grid, placement, extras)
+        count = lambda grid: _simplify_device(v, f, grid, placement, (), count_only=True)['n_faces']
+        usable = lambda: _simplify_device(v, f, None, placement, (), count_only=True)['usable']
+    else:
+        v, f = np.ascontiguousarray(_np(verts), dtype=F32), _np(faces).astype(np.int64)
+        if nf and (f.min() < 0 or f.max() >= nv):
+            raise ValueError(f'faces index vertices outside [0, {nv})')
+        fin = v[np.isfinite(v).all(1)]
+        box = (fin.min(0).tolist(), fin.max(0).tolist()) if fin.shape[0] else None
+        np_extras = [_np(e) for e in extras]
+        run = lambda grid: _simplify_numpy(v, f, grid, placement, np_extras)
+        count = lambda grid: _simplify_count_numpy(v, f, grid)
+        usable = lambda: int(np.isfinite(v).all(1)[f].all(1).sum())
+    lo, hi = box if box is not None else ([0.0] * 3, [0.0] * 3)
+
+    def plan(c=None, h=None):
+        dims, inv, cell = _simplify_plan(lo, hi, c, h)
+        return dims, lo, inv, cell
+    steps, grid = 0, None
+    if target_faces is None:
+        grid = plan(cells, cell_size)
+    elif usable() > int(target_faces):
+        n = int(target_faces)
+        steps = 1
+        if count(plan(max_cells)) <= n:
+            c = max_cells
+        else:
+            c, above = 1, max_cells                                     # F'(1) = 0 <= n < F'(above)
+            while above - c > 1:
+                mid = (c + above) // 2
+                steps += 1
+                if count(plan(mid)) <= n:
+                    c = mid
+                else:
+                    above = mid
+        grid = plan(c)
+    out = run(grid)
+    if not on_dev:
+        out = {k: ([_as_out(e, verts, e.dtype) for e in x] if k == 'extras' else _as_out(x, verts, x.dtype) if isinstance(x, np.ndarray) else x)
+               for k, x in out.items()}
+    out.update(dims=None if grid is None else tuple(int(d) for d in grid[0]), cell_size=0.0 if grid is None else float(max(grid[3])),
+               cell=None if grid is None else tuple(float(h) for h in grid[3]), lo=tuple(float(x) for x in lo), input_faces=nf)
+    if target_faces is not None:
+        out['steps'] = steps
+    return out
 
 
 # ------------------------------------------------------------------ generator-level helpers

@@ -1677,3 +1677,211 @@ def distance_stats(dist, thresholds=(), face=None, normals_a=None, normals_b=Non
                                    normals_b.shape[0] if with_normals else 0, _p(scratch), scratch.numel() * 8, _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_distance_stats')
     return out
+
+
+# ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
+
+SIMPLIFY_TIMES = None        # a dict collects seconds per phase (each phase then ends in a device synchronise): tools/bench_simplify.py
+
+
+class _Phase:
+    def __init__(self, name, dev):
+        self.name, self.dev = name, dev
+
+    def __enter__(self):
+        if SIMPLIFY_TIMES is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            self.t0 = time.perf_counter()
+        return self
+
+    def __exit__(self, *exc):
+        if SIMPLIFY_TIMES is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            SIMPLIFY_TIMES[self.name] = SIMPLIFY_TIMES.get(self.name, 0.0) + time.perf_counter() - self.t0
+        return False
+
+
+def _d3(values):
+    return (ctypes.c_double * 3)(*[float(v) for v in values])
+
+
+def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):
+    """Grid of the clustering (host arithmetic, see ia_simplify_plan): -> (dims, inv_cell, cell)."""
+    dims, inv, cell = (ctypes.c_int * 3)(), (ctypes.c_float * 3)(), (ctypes.c_double * 3)()
+    st = _lib.load().ia_simplify_plan(_f3(lo), _f3(hi), None if cells is None else _i3(cells), int(cells_long), float(cell_size), dims, inv, cell)
+    _lib.check(st, 'ia_simplify_plan')
+    return tuple(dims), tuple(inv), tuple(cell)
+
+
+def simplify_box(verts):
+    """(lo, hi) of the finite vertices as lists of floats, or None without a finite vertex (see ia_simplify_box).  One host
+    synchronisation."""
+    _f32c(verts, 'verts')
+    dev = verts.device
+    scratch = torch.empty(6 * 1024, device=dev)
+    box = torch.empty(6, device=dev)
+    with torch.cuda.device(dev), _Phase('keys', dev):
+        st = _lib.load().ia_simplify_box(_p(verts), verts.shape[0], _p(scratch), scratch.numel() * 4, _p(box), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_simplify_box')
+        b = box.cpu().tolist()
+    if not all(math.isfinite(x) for x in b):
+        return None
+    return b[:3], b[3:]
+
+
+def simplify_keys(verts, lo, inv_cell, dims):
+    """int64 [V]: the linear cell index of every vertex, INT64_MAX without a cell (see ia_simplify_keys)."""
+    _f32c(verts, 'verts')
+    dev = verts.device
+    keys = torch.empty(verts.shape[0], dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev), _Phase('keys', dev):
+        st = _lib.load().ia_simplify_keys(_p(verts), verts.shape[0], _f3(lo), _f3(inv_cell), _i3(dims), _p(keys), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_simplify_keys')
+    return keys
+
+
+def simplify_topology(keys, faces, full=True, pairs=False):
+    """The integer part of the clustering from per-vertex keys int64 [V] and faces int32 [F,3] (ia_simplify_clusters, _classify,
+    _face_heads, _refs; the two key sorts are torch.sort).  Returns a dict of device arrays and the host counts 'K', 'n_valid',
+    'usable', 'surviving', 'n_pairs', 'n_faces' (unique surviving faces) and, with ``full``, 'n_verts'.  ``full=False`` is the
+    count-only pass.  Two host synchronisations."""
+    _i32c(faces, 'faces')
+    if not (keys.is_cuda and keys.dtype == torch.int64 and keys.is_contiguous() and keys.device == faces.device):
+        raise RuntimeError('keys must be a contiguous int64 tensor on the device of the faces')
+    lib, dev = _lib.load(), faces.device
+    v, f = keys.numel(), faces.shape[0]
+    i32 = dict(dtype=torch.int32, device=dev)
+    s = {'V': v, 'F': f}
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        with _Phase('sorts', dev):
+            skeys, order = torch.sort(keys, stable=True)
+        with _Phase('keys', dev):
+            vcluster, vseg = torch.empty(v, **i32), torch.empty(v, **i32)
+            cstart, ckey = torch.empty(v + 1, **i32), torch.empty(max(v, 1), dtype=torch.int64, device=dev)
+            scratch, count = torch.empty(v + 1, **i32), torch.empty(2, **i32)
+            st = lib.ia_simplify_clusters(_p(skeys), _p(order), v, _p(vcluster), _p(vseg), _p(cstart), _p(ckey), v, _p(scratch),
+                                          scratch.numel() * 4, _p(count), stream)
+            _lib.check(st, 'ia_simplify_clusters')
+            k, n_valid = (int(x) for x in count.cpu())
+        with _Phase('faces', dev):
+            tri, key = torch.empty(max(f, 1), 3, **i32), torch.empty(max(f, 1), dtype=torch.int64, device=dev)
+            ref = torch.empty(max(k, 1), **i32) if full else None
+            pr = torch.empty(max(3 * f, 1), **i32) if pairs else None
+            fcount = torch.empty(3, **i32)
+            st = lib.ia_simplify_classify(_p(faces), f, v, _p(vcluster), k, _p(tri), _p(key), _p(ref), _p(pr), _p(fcount), stream)
+            _lib.check(st, 'ia_simplify_classify')
+        with _Phase('sorts', dev):
+            perm = torch.sort(key[:f], stable=True)[1]
+            if float(k) ** 3 >= 9.0e18:                                   # the key holds (b, c) only: a second, stable sort by a
+                perm = perm[torch.sort(tri[:f, 0][perm], stable=True)[1]].contiguous()
+        with _Phase('faces', dev):
+            fpos = torch.empty(f + 1, **i32)
+            _lib.check(lib.ia_simplify_face_heads(_p(tri), _p(perm), f, _p(fpos), stream), 'ia_simplify_face_heads')
+            outidx = None
+            if full:
+                outidx = torch.empty(k + 1, **i32)
+                _lib.check(lib.ia_simplify_refs(_p(ref), k, _p(outidx), stream), 'ia_simplify_refs')
+            tail = torch.cat([fcount, fpos[f:], outidx[k:]] if full else [fcount, fpos[f:]]).cpu().tolist()
+    s.update(K=k, n_valid=n_valid, usable=tail[0], surviving=tail[1], n_pairs=tail[2], n_faces=tail[3], n_verts=tail[4] if full else None,
+             order=order, vcluster=vcluster, vseg=vseg, cstart=cstart, ckey=ckey, tri=tri, perm=perm, fpos=fpos, ref=ref, outidx=outidx,
+             pairs=pr, faces=faces)
+    return s
+
+
+def simplify_outputs(s):
+    """faces int64 [F',3], vertex_map int64 [V], cluster_size int64 [V'] and the cluster of every output vertex (int32 [V']) of a full
+    ``simplify_topology`` state (ia_simplify_outputs, ia_simplify_faces)."""
+    lib, dev = _lib.load(), s['faces'].device
+    v, f, k, nv, nf = s['V'], s['F'], s['K'], s['n_verts'], s['n_faces']
+    vertex_map = torch.empty(v, dtype=torch.int64, device=dev)
+    ocl = torch.empty(nv, dtype=torch.int32, device=dev)
+    csize = torch.empty(nv, dtype=torch.int64, device=dev)
+    faces_out = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev), _Phase('faces', dev):
+        stream = _lib.stream_ptr(dev)
+        st = lib.ia_simplify_outputs(_p(s['vcluster']), v, _p(s['ref']), _p(s['outidx']), _p(s['cstart']), k, _p(vertex_map), _p(ocl),
+                                     _p(csize), nv, stream)
+        _lib.check(st, 'ia_simplify_outputs')
+        st = lib.ia_simplify_faces(_p(s['tri']), _p(s['perm']), _p(s['fpos']), f, _p(s['outidx']), k, _p(faces_out), nf, stream)
+        _lib.check(st, 'ia_simplify_faces')
+    return faces_out, vertex_map, csize, ocl
+
+
+def _acc_scratch(lib, n, width, dev):
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.ia_simplify_accumulate_scratch_bytes(n, width, ctypes.byref(nbytes)), 'ia_simplify_accumulate_scratch_bytes')
+    return torch.empty((nbytes.value + 7) // 8 + 1, dtype=torch.float64, device=dev)
+
+
+def simplify_vertex_sums(s, cols):
+    """float64 [K, C]: per cluster the sums of the columns of ``cols`` (float64 [V,C]) over its vertices, four columns per call of
+    ia_simplify_accumulate_verts."""
+    if not (cols.is_cuda and cols.dtype == torch.float64 and cols.is_contiguous() and cols.dim() == 2 and cols.shape[0] == s['V']):
+        raise RuntimeError(f'cols must be a contiguous float64 [V,C] device tensor, got {cols.dtype} {tuple(cols.shape)}')
+    lib, dev = _lib.load(), cols.device
+    k, c = s['K'], cols.shape[1]
+    out = torch.zeros(k, c, dtype=torch.float64, device=dev)
+    if k == 0 or c == 0:
+        return out
+    scratch = _acc_scratch(lib, s['n_valid'], 4, dev)
+    with torch.cuda.device(dev), _Phase('accumulate', dev):
+        for c0 in range(0, c, 4):
+            nc = min(4, c - c0)
+            sums = torch.empty(k, 4, dtype=torch.float64, device=dev)
+            st = lib.ia_simplify_accumulate_verts(_p(cols), c, c0, nc, _p(s['order']), _p(s['vseg']), s['n_valid'], s['V'], k, _p(sums),
+                                                  _p(scratch), scratch.numel() * 8, _lib.stream_ptr(dev))
+            _lib.check(st, 'ia_simplify_accumulate_verts')
+            out[:, c0:c0 + nc] = sums[:, :nc]
+    return out
+
+
+def simplify_quadric_sums(s, verts, lo, inv_cell, cell, dims):
+    """float64 [K,9]: per cluster the summed plane quadrics of its usable faces (ia_simplify_accumulate_faces; the stable sort of the
+    (cluster, face) pairs is torch.sort)."""
+    _f32c(verts, 'verts')
+    lib, dev = _lib.load(), verts.device
+    k, f, n = s['K'], s['F'], s['n_pairs']
+    sums = torch.zeros(max(k, 1), 9, dtype=torch.float64, device=dev)
+    if k == 0:
+        return sums
+    with torch.cuda.device(dev):
+        with _Phase('sorts', dev):
+            spairs, porder = torch.sort(s['pairs'][:3 * f], stable=True)
+        scratch = _acc_scratch(lib, n, 9, dev)
+        with _Phase('accumulate', dev):
+            st = lib.ia_simplify_accumulate_faces(_p(verts), s['V'], _p(s['faces']), f, _p(porder), _p(spairs), n, _p(s['ckey']), k, _f3(lo),
+                                                  _f3(inv_cell), _d3(cell), _i3(dims), _p(sums), _p(scratch), scratch.numel() * 8,
+                                                  _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_simplify_accumulate_faces')
+    return sums
+
+
+def simplify_place(s, ocl, vsum, qsum, lo, inv_cell, cell, dims):
+    """float32 [V',3]: the representatives (ia_simplify_place); ``qsum`` None: the cluster means."""
+    lib, dev = _lib.load(), ocl.device
+    nv = ocl.numel()
+    out = torch.empty(nv, 3, device=dev)
+    vs = vsum if vsum.shape[1] == 4 else torch.nn.functional.pad(vsum, (0, 4 - vsum.shape[1]))
+    with torch.cuda.device(dev), _Phase('place', dev):
+        st = lib.ia_simplify_place(_p(vs.contiguous()), _p(qsum), _p(ocl), _p(s['cstart']), _p(s['ckey']), s['K'], nv, _f3(lo), _f3(inv_cell),
+                                   _d3(cell), _i3(dims), _p(out), nv, _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_simplify_place')
+    return out
+
+
+def simplify_means(s, ocl, sums):
+    """float64 [V',C]: ``sums`` (float64 [K,C]) over the cluster sizes at the output vertices (ia_simplify_means)."""
+    lib, dev = _lib.load(), ocl.device
+    nv, c = ocl.numel(), sums.shape[1]
+    out = torch.empty(nv, c, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _Phase('place', dev):
+        for c0 in range(0, c, 4):
+            nc = min(4, c - c0)
+            block = torch.zeros(max(s['K'], 1), 4, dtype=torch.float64, device=dev)
+            block[:s['K'], :nc] = sums[:, c0:c0 + nc]
+            st = lib.ia_simplify_means(_p(block), _p(ocl), _p(s['cstart']), s['K'], nv, nc, _p(out), c, c0, nv, _lib.stream_ptr(dev))
+            _lib.check(st, 'ia_simplify_means')
+    return out

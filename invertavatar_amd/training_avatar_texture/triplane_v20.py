@@ -535,7 +535,7 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         with_normals=False, keep=None, min_voxels=0, **synthesis_kwargs):
+                         with_normals=False, keep=None, min_voxels=0, simplify=None, **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
@@ -544,8 +544,11 @@ class TriPlaneGenerator(torch.nn.Module):
         constant of the model.  With ``keep`` (``'largest'``, an int n or a list of labels; ``min_voxels``: see
         ``geometry.select_components``) the detached components of {density > level} are removed from the volume first
         (``geometry.keep_components``, 26-connectivity): 'volume' is then the filtered volume, mesh, colours and normals come from it, and
-        'components' holds {'count', 'kept', 'stats'}.  The planes are computed once per call; device tensors stay on the device
-        throughout."""
+        'components' holds {'count', 'kept', 'stats'}.  ``simplify`` (None: nothing changes; an int = ``target_faces``; or a dict of
+        ``geometry.simplify_mesh`` keyword arguments) simplifies the mesh after the filter and marching cubes: 'verts' and 'faces' are
+        then the simplified mesh, colours and normals are queried at its vertices (exact there, and cheaper than averaging), and
+        'simplify' holds {'dims', 'cell_size', 'faces_before', 'faces_after', 'verts_before', 'verts_after'} (and 'steps' with a
+        target).  The planes are computed once per call; device tensors stay on the device throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
         length = box_warp if cube_length is None else cube_length
@@ -562,6 +565,14 @@ class TriPlaneGenerator(torch.nn.Module):
             item = {'volume': vol_b, 'verts': verts, 'faces': faces}
             if info is not None:
                 item['components'] = info
+            if simplify is not None:
+                kw = dict(simplify) if isinstance(simplify, dict) else {'target_faces': int(simplify)}
+                simple = geometry.simplify_mesh(verts, faces, **kw)
+                item['simplify'] = {'dims': simple['dims'], 'cell_size': simple['cell_size'], 'faces_before': int(faces.shape[0]),
+                                    'faces_after': int(simple['faces'].shape[0]), 'verts_before': int(verts.shape[0]),
+                                    'verts_after': int(simple['verts'].shape[0]), **({'steps': simple['steps']} if 'steps' in simple else {})}
+                verts, faces = simple['verts'], simple['faces']
+                item['verts'], item['faces'] = verts, faces
             if with_colors:
                 item['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, verts, box_warp)
             if with_normals:

@@ -1036,6 +1036,46 @@ int ia_simplify_place(const double* vert_sums, const double* quadric_sums, const
 int ia_simplify_means(const double* vert_sums, const int* out_cluster, const int* cluster_start, int K, int64_t n_out, int ncols,
                       double* out, int ld, int col0, int64_t capacity, void* stream);
 
+/* Mesh smoothing (Taubin lambda | mu, Laplacian) and vertex normals from the mesh (csrc/smooth.hip; definition: geometry.smooth_mesh,
+ * geometry.MeshAdjacency, geometry.mesh_normals and their NumPy restatement).  verts float32 [V,3], faces int32 [F,3],
+ * V, F <= 2^28.  A face is usable if its indices are distinct, in [0, V), and its vertices finite.
+ *
+ * ia_mesh_edge_keys: edge_keys int64 [6 F] (per usable face (a,b,c) the keys i V + j of (a,b) (b,a) (b,c) (c,b) (c,a) (a,c); INT64_MAX
+ * for an unusable face), vertex_keys int64 [3 F] (v F + f per corner, INT64_MAX likewise).  count = device int [8], cleared here and filled
+ * by this and the next two calls: [0] usable faces, [1] 1 if an index is outside [0, V), [2] directed entries with one face, [3] with
+ * more than two faces, [4] boundary vertices, [5] largest degree, [6] vertices of degree > 64, [7] E (distinct directed edges).
+ * ia_mesh_edge_heads: from the edge keys sorted ascending (stable), scratch (ia_mesh_edge_heads_scratch_bytes(F) bytes) receives the first
+ * CSR slot of every workgroup of 256 sorted entries and count[7] = E.
+ * ia_mesh_csr: usable = count[0] and E = count[7] as read by the host; scratch as left by ia_mesh_edge_heads; vertex_order int64 [3 F]
+ * is the permutation that sorted vertex_keys.  offsets int32 [V + 1], neighbors / edge_faces / run_start int32 [E] (run_start: first
+ * sorted position of the slot's entries), slot_keys int64 [E], boundary uint8 [V], face_offsets int32 [V + 1], face_ids int32
+ * [3 usable], heavy int32 [V] (the first count[6] entries: vertices of degree > 64, in no particular order).
+ * ia_mesh_cotangent: weights float32 [E] = max(0, 1/2 sum cot) over the faces on the edge in face order (double); edge_order int64 [6 F]
+ * is the permutation that sorted edge_keys.
+ * ia_smooth_pinned: pinned uint8 [V]: non-finite, no neighbour, all weights zero (weights may be NULL: uniform), boundary if
+ * fix_boundary, or fixed (uint8 [V], may be NULL).
+ * ia_smooth_steps: n_steps Jacobi steps p' = fp32(p + f (sum w p_j / sum w - p)) with the host factors h_factors[n_steps], from verts_a
+ * into verts_b and back; the result is in verts_a if n_steps is even, else in verts_b.  No host synchronisation.  heavy / n_heavy: as
+ * left by ia_mesh_csr (count[6]).
+ * ia_mesh_normals: normals float32 [V,3]: the normalised sum over the vertex's usable faces of the cross product (angle = 0) or of the
+ * unit normal times the corner angle (angle = 1); 0 where the sum has no direction.
+ */
+int ia_mesh_edge_keys(const float* verts, int64_t V, const int* faces, int64_t F, int64_t* edge_keys, int64_t* vertex_keys, int* count,
+                      void* stream);
+int ia_mesh_edge_heads_scratch_bytes(int64_t F, size_t* h_bytes);
+int ia_mesh_edge_heads(const int64_t* sorted_keys, int64_t F, void* scratch, size_t scratch_bytes, int* count, void* stream);
+int ia_mesh_csr(const int64_t* sorted_keys, const int64_t* sorted_vertex_keys, const int64_t* vertex_order, int64_t V, int64_t F,
+                int64_t usable, int64_t E, const void* scratch, int* offsets, int* neighbors, int* edge_faces, int* run_start,
+                int64_t* slot_keys, unsigned char* boundary, int* face_offsets, int* face_ids, int* heavy, int* count, void* stream);
+int ia_mesh_cotangent(const float* verts, int64_t V, const int* faces, int64_t F, const int64_t* edge_order, const int64_t* slot_keys,
+                      const int* run_start, const int* edge_faces, int64_t E, float* weights, void* stream);
+int ia_smooth_pinned(const float* verts, int64_t V, const int* offsets, const float* weights, const unsigned char* boundary,
+                     int fix_boundary, const unsigned char* fixed, unsigned char* pinned, void* stream);
+int ia_smooth_steps(float* verts_a, float* verts_b, int64_t V, const int* offsets, const int* neighbors, const float* weights,
+                    const unsigned char* pinned, const int* heavy, int n_heavy, const double* h_factors, int n_steps, void* stream);
+int ia_mesh_normals(const float* verts, int64_t V, const int* faces, int64_t F, const int* face_offsets, const int* face_ids, int angle,
+                    float* normals, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,15 @@ _SIGNATURES = {
     'ia_simplify_place': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, _f32p, _f32p, ctypes.POINTER(ctypes.c_double),
                           ctypes.POINTER(c_int), c_void_p, c_int64, c_void_p],
     'ia_simplify_means': [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p],
+    'ia_mesh_edge_keys': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_mesh_edge_heads_scratch_bytes': [c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_mesh_edge_heads': [c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_mesh_csr': [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64] + [c_void_p] * 12,
+    'ia_mesh_cotangent': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_smooth_pinned': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    'ia_smooth_steps': [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
+                        c_int, c_void_p],
+    'ia_mesh_normals': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
 }
 
 

@@ -14,7 +14,11 @@ prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh ag
 its distance to the reference.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
 clustering; the line per seed then shows the triangle counts before and after), ``--simplify-cells C`` to a grid of C cells along the
 longest axis; ``--simplify-check`` scores the simplified mesh against the full one (``geometry.surface_distance``), prints both directed
-Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  Runs on the device when there is one."""
+Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  ``--smooth N`` smooths the mesh with N
+Taubin pairs (``geometry.smooth_mesh``, after ``--keep`` and ``--simplify``; ``--smooth-lambda``, ``--smooth-mu`` (``none``: plain Laplacian
+steps) and ``--smooth-weights`` set its arguments; normals then come from the mesh) and prints the boundary and non-manifold edge counts;
+``--smooth-check`` prints the signed volume before and after and both directed Hausdorff distances between the smoothed and the
+unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -56,6 +60,16 @@ def parse_keep(s):
     return n
 
 
+def parse_mu(s):
+    """A float, or 'none' (plain Laplacian smoothing)."""
+    if s.lower() == 'none':
+        return None
+    try:
+        return float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--smooth-mu takes a number or 'none', got {s!r}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Density volumes and meshes of tri-plane avatars')
     ap.add_argument('--seeds', type=parse_range, required=True)
@@ -81,6 +95,11 @@ def main(argv=None):
     grp.add_argument('--simplify', type=int, default=None, metavar='N', help='simplify the mesh to at most N triangles')
     grp.add_argument('--simplify-cells', type=int, default=None, metavar='C', help='simplify on a grid of C cells along the longest axis')
     ap.add_argument('--simplify-check', action='store_true', help='with --simplify / --simplify-cells: distance of the simplified mesh to the full one')
+    ap.add_argument('--smooth', type=int, default=None, metavar='N', help='smooth the mesh with N Taubin pairs (after --keep and --simplify)')
+    ap.add_argument('--smooth-lambda', type=float, default=0.5)
+    ap.add_argument('--smooth-mu', type=parse_mu, default=-0.53, help="the negative factor of a pair, or 'none' for plain Laplacian steps")
+    ap.add_argument('--smooth-weights', default='uniform', choices=['uniform', 'cotangent'])
+    ap.add_argument('--smooth-check', action='store_true', help='with --smooth: signed volume before and after, distance to the unsmoothed mesh')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -91,9 +110,13 @@ def main(argv=None):
     simplify = args.simplify if args.simplify is not None else ({'cells': args.simplify_cells} if args.simplify_cells is not None else None)
     if args.simplify_check and simplify is None:
         ap.error('--simplify-check needs --simplify or --simplify-cells')
+    if args.smooth_check and args.smooth is None:
+        ap.error('--smooth-check needs --smooth')
+    smooth = None if args.smooth is None else {'iterations': args.smooth, 'lam': args.smooth_lambda, 'mu': args.smooth_mu,
+                                               'weights': args.smooth_weights}
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
-                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, noise_mode='const')[0]
+                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, smooth=smooth, noise_mode='const')[0]
         path = os.path.join(args.outdir, f'seed{seed:04d}.ply')
         geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'), out.get('normals'))
         if args.save_volume:
@@ -117,6 +140,29 @@ def main(argv=None):
             out['simplify'] = meta['simplify']
             with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
                 json.dump(meta, fh, indent=1)
+        if 'smooth' in out:
+            info = out['smooth']
+            print(f'seed {seed}: smoothed with {info["steps"]} steps, {info["edges"]} edges, {info["boundary_edges"]} boundary edges, '
+                  f'{info["nonmanifold_edges"]} non-manifold edges')
+            meta = {'smooth': dict(info)}
+            if args.smooth_check:
+                rough = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, keep=args.keep, min_voxels=args.min_voxels,
+                                           simplify=simplify, noise_mode='const')[0]
+                samples = 200000 if out['verts'].is_cuda else 2000                # (the host route is brute force)
+                d = geometry.surface_distance(out['verts'], out['faces'], rough['verts'], rough['faces'], samples=samples)
+                meta['smooth']['check'] = {'volume_before': geometry.signed_volume(rough['verts'], rough['faces']),
+                                           'volume_after': geometry.signed_volume(out['verts'], out['faces']),
+                                           'smoothed_to_input': d['max_ab'], 'input_to_smoothed': d['max_ba'], 'chamfer': d['chamfer']}
+                chk = meta['smooth']['check']
+                print(f'seed {seed}: signed volume {chk["volume_before"]:.6g} -> {chk["volume_after"]:.6g}, Hausdorff smoothed -> input '
+                      f'{d["max_ab"]:.6g}, input -> smoothed {d["max_ba"]:.6g}')
+            out['smooth'] = meta['smooth']
+            gpath = os.path.join(args.outdir, f'seed{seed:04d}_geometry.json')
+            if 'simplify' in out and os.path.exists(gpath):
+                with open(gpath) as fh:
+                    meta = dict(json.load(fh), **meta)
+            with open(gpath, 'w') as fh:
+                json.dump(meta, fh, indent=1)
         if 'components' in out:
             info = out['components']
             sizes = [int(info['stats'][c - 1, 0]) for c in info['kept']]
@@ -127,7 +173,7 @@ def main(argv=None):
             err = os.path.join(args.outdir, f'seed{seed:04d}_error.ply') if args.error_ply else None
             out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err)
             with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
-                json.dump(dict(out['metrics'], simplify=out['simplify']) if 'simplify' in out else out['metrics'], fh, indent=1)
+                json.dump(dict(out['metrics'], **{k: out[k] for k in ('simplify', 'smooth') if k in out}), fh, indent=1)
             print(f'seed {seed}: against {args.compare}: {geometry_metrics.summary(out["metrics"])}')
         if args.views > 0:
             from PIL import Image

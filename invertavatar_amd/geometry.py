@@ -25,6 +25,10 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
 - ``simplify_mesh``: quadric vertex clustering on a uniform grid, to a cell size or to a target face count.  Device tensors go to the
   kernels of csrc/simplify.hip (``ia_simplify_*``; the sorts of integer keys are ``torch.sort``); CPU tensors and NumPy arrays take the
   NumPy restatement that is the definition (float64).
+- ``smooth_mesh`` / ``MeshAdjacency`` / ``mesh_normals``: Taubin and Laplacian smoothing of an indexed mesh (uniform or cotangent
+  weights, pinned boundary) and vertex normals from the mesh itself.  Device tensors go to the kernels of csrc/smooth.hip (``ia_mesh_*``,
+  ``ia_smooth_*``; the two sorts of integer keys are ``torch.sort``); CPU tensors and NumPy arrays take the NumPy restatement that is the
+  definition (float64 sums, positions rounded to float32 once per step).
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
@@ -1229,6 +1233,277 @@ def simplify_mesh(verts, faces, cells=None, cell_size=None, target_faces=None, p
     if target_faces is not None:
         out['steps'] = steps
     return out
+
+
+# ------------------------------------------------------------------ mesh smoothing and mesh normals
+
+_WEIGHTS = ('uniform', 'cotangent')
+_BOUNDARY = ('fixed', 'free')
+_NORMAL_WEIGHTING = ('area', 'angle')
+
+
+def _len3(u):
+    return np.sqrt((u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2])
+
+
+def _segment_sums(idx, rows, n, dtype=np.float64):
+    """Per segment the sums of ``rows`` [m] or [m,C] over the entries with segment ``idx``, each added in entry order, in ``dtype``."""
+    rows = np.asarray(rows, dtype=dtype)
+    if dtype == np.float64:
+        if rows.ndim == 1:
+            return np.bincount(idx, weights=rows, minlength=n)
+        return np.stack([np.bincount(idx, weights=rows[:, c], minlength=n) for c in range(rows.shape[1])], -1)
+    out = np.zeros((n,) + rows.shape[1:], dtype=dtype)
+    np.add.at(out, idx, rows)
+    return out
+
+
+def _adjacency_numpy(v32, f):
+    """The integer part of the definition of ``MeshAdjacency`` on NumPy arrays (verts float32 [V,3], faces int64 [F,3], indices in
+    range): CSR neighbour lists, faces per edge, boundary flags, the vertex -> face incidence and, for the cotangent weights, the
+    sorted directed entries (``run``: the CSR slot of every entry, ``ent``: its (i, j, opposite vertex), in face order per slot)."""
+    nv, nf = v32.shape[0], f.shape[0]
+    fin = np.isfinite(v32).all(1)
+    usable = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    if nf:
+        usable &= fin[f].all(1)
+    uf = np.flatnonzero(usable)
+    a, b, c = (f[uf, k] for k in range(3))
+    src = np.stack([a, b, b, c, c, a], -1).reshape(-1)
+    dst = np.stack([b, a, c, b, a, c], -1).reshape(-1)
+    opp = np.stack([c, c, a, a, b, b], -1).reshape(-1)
+    order = np.argsort(src * nv + dst, kind='stable')                    # entries of one key stay in face order
+    src, dst, opp = src[order], dst[order], opp[order]
+    head = np.ones(src.size, dtype=bool)
+    head[1:] = (src[1:] != src[:-1]) | (dst[1:] != dst[:-1])
+    start = np.flatnonzero(head)
+    row, nbr = src[start], dst[start]
+    edge_faces = np.diff(np.append(start, src.size))
+    deg = np.bincount(row, minlength=nv)
+    offsets = np.zeros(nv + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(deg)
+    boundary = np.bincount(row, weights=(edge_faces == 1), minlength=nv) > 0
+    corner = f[uf].reshape(-1)
+    vorder = np.argsort(corner * max(nf, 1) + np.repeat(uf, 3), kind='stable')
+    face_offsets = np.zeros(nv + 1, dtype=np.int64)
+    face_offsets[1:] = np.cumsum(np.bincount(corner, minlength=nv))
+    info = {'edges': int(start.size // 2), 'boundary_edges': int((edge_faces == 1).sum() // 2),
+            'nonmanifold_edges': int((edge_faces > 2).sum() // 2), 'boundary_verts': int(boundary.sum()), 'usable_faces': int(uf.size),
+            'max_degree': int(deg.max()) if nv else 0}
+    return {'offsets': offsets.astype(np.int32), 'neighbors': nbr.astype(np.int32), 'edge_faces': edge_faces.astype(np.int32),
+            'boundary': boundary, 'face_offsets': face_offsets.astype(np.int32), 'face_ids': np.repeat(uf, 3)[vorder].astype(np.int32),
+            'info': info, 'row': row, 'run': np.cumsum(head) - 1, 'ent': (src, dst, opp), 'finite': fin}
+
+
+def _cotangent_numpy(v32, adj, dtype=np.float64):
+    """float32 [E]: ``max(0, 1/2 sum cot)`` per directed edge, the sum over the usable faces on the edge in face order, in ``dtype``
+    (float64 is the definition; the tests take the definition's own sensitivity from a float32 run)."""
+    i, j, o = adj['ent']
+    p = v32.astype(dtype)
+    u, v = p[i] - p[o], p[j] - p[o]
+    with np.errstate(all='ignore'):
+        ln = _len3(_cross3(u, v))
+        ok = np.isfinite(ln) & (ln > 0)
+        cot = np.where(ok, _dot3(u, v) / np.where(ok, ln, 1), 0).astype(dtype)
+    s = _segment_sums(adj['run'], cot, adj['neighbors'].size, dtype)
+    return np.maximum(dtype(0), dtype(0.5) * s).astype(F32)
+
+
+def _pinned_numpy(adj, w, boundary, fixed):
+    deg = np.diff(adj['offsets'].astype(np.int64))
+    pinned = ~adj['finite'] | (deg == 0)
+    if w is not None:
+        pinned |= np.bincount(adj['row'], weights=(w > 0), minlength=deg.size) == 0
+    if boundary == 'fixed':
+        pinned |= adj['boundary']
+    if fixed is not None:
+        pinned |= fixed
+    return pinned
+
+
+def _smooth_numpy(v32, adj, w, pinned, factors, round32=True):
+    """The steps of the definition of ``smooth_mesh``: float64 [V,3].  ``round32=False`` carries the positions in float64 throughout
+    (the tests take the definition's own sensitivity to its rounding points from the two runs)."""
+    nv = v32.shape[0]
+    p = v32.astype(np.float64)
+    move = np.flatnonzero(~pinned)
+    if not move.size:
+        return p
+    nbr = adj['neighbors'].astype(np.int64)
+    w64 = np.ones(nbr.size) if w is None else w.astype(np.float64)
+    wsum = np.bincount(adj['row'], weights=w64, minlength=nv)[move, None]
+    for fac in factors:
+        s = _segment_sums(adj['row'], w64[:, None] * p[nbr], nv)[move]
+        q = p[move] + float(fac) * (s / wsum - p[move])
+        p = p.copy()
+        p[move] = q.astype(F32).astype(np.float64) if round32 else q
+    return p
+
+
+def _mesh_normals_numpy(v32, f, adj, weighting, dtype=np.float64):
+    nv = v32.shape[0]
+    p = v32.astype(dtype)
+    fid = adj['face_ids'].astype(np.int64)
+    rows = np.repeat(np.arange(nv), np.diff(adj['face_offsets'].astype(np.int64)))
+    t = f[fid].reshape(-1, 3)
+    n = _cross3(p[t[:, 1]] - p[t[:, 0]], p[t[:, 2]] - p[t[:, 0]])
+    with np.errstate(all='ignore'):
+        if weighting == 'angle':
+            ln = _len3(n)
+            ok = np.isfinite(ln) & (ln > 0)
+            k = np.argmax(t == rows[:, None], axis=1) if t.size else np.zeros(0, dtype=np.int64)
+            ar = np.arange(t.shape[0])
+            e1, e2 = p[t[ar, (k + 1) % 3]] - p[rows], p[t[ar, (k + 2) % 3]] - p[rows]
+            ang = np.arctan2(ln, _dot3(e1, e2))
+            n = np.where(ok[:, None], n / np.where(ok, ln, 1)[:, None] * ang[:, None], 0).astype(dtype)
+        s = _segment_sums(rows, n, nv, dtype)
+        ln = _len3(s)
+        ok = np.isfinite(ln) & (ln > 0)
+        return np.where(ok[:, None], s / np.where(ok, ln, 1)[:, None], 0).astype(F32)
+
+
+def _faces_in_range(faces, nv):
+    if faces.shape[0] and (int(faces.min()) < 0 or int(faces.max()) >= nv):
+        raise ValueError(f'faces index vertices outside [0, {nv})')
+
+
+class MeshAdjacency:
+    """The neighbourhood structure of one indexed mesh (verts float32 [V,3], faces [F,3]), built once for many calls of ``smooth_mesh``
+    and ``mesh_normals`` (as ``TriangleGrid`` is for ``closest_point``).  See ``smooth_mesh`` for the definitions.
+
+    - ``offsets`` int32 [V+1], ``neighbors`` int32 [E]: the distinct neighbours of vertex i, ascending, at ``offsets[i] .. offsets[i+1]``;
+    - ``edge_faces`` int32 [E]: usable faces on the edge (duplicates counted); ``boundary`` bool [V];
+    - ``face_offsets`` int32 [V+1], ``face_ids`` int32 [3 * usable faces]: the usable faces of vertex i, ascending;
+    - ``cotangent()``: float32 [E], computed on first use from the positions the structure was built with;
+    - ``info``: 'edges', 'boundary_edges', 'nonmanifold_edges' (undirected), 'boundary_verts', 'usable_faces', 'max_degree'.
+
+    ``offsets``, ``neighbors``, ``edge_faces`` and ``boundary`` do not depend on the order of the faces.  Device tensors are built by the
+    kernels of csrc/smooth.hip (the two sorts of integer keys are ``torch.sort``; two host synchronisations), CPU tensors and NumPy
+    arrays by the NumPy restatement; the arrays are in the caller's container.  An index outside [0, V) raises ``ValueError``."""
+
+    def __init__(self, verts, faces):
+        _mesh_args(verts, faces)
+        self.device = isinstance(verts, torch.Tensor) and verts.is_cuda
+        self.n_verts, self.n_faces = int(verts.shape[0]), int(faces.shape[0])
+        self._cot = None
+        if self.device:
+            from . import hipops
+            self.verts = verts.detach().float().contiguous()
+            self.faces = faces.to(device=verts.device, dtype=torch.int32).contiguous()
+            self._state = hipops.mesh_adjacency(self.verts, self.faces)
+            if self._state['out_of_range']:
+                raise ValueError(f'faces index vertices outside [0, {self.n_verts})')
+            for k in ('offsets', 'neighbors', 'edge_faces', 'boundary', 'face_offsets', 'face_ids', 'info'):
+                setattr(self, k, self._state[k])
+        else:
+            self.verts = np.ascontiguousarray(_np(verts), dtype=F32)
+            self.faces = _np(faces).astype(np.int64)
+            _faces_in_range(self.faces, self.n_verts)
+            self._state = _adjacency_numpy(self.verts, self.faces)
+            for k in ('offsets', 'neighbors', 'edge_faces', 'face_offsets', 'face_ids'):
+                setattr(self, k, _as_out(self._state[k], verts, np.int32))
+            self.boundary = _as_out(self._state['boundary'], verts, bool)
+            self.info = self._state['info']
+
+    def cotangent(self):
+        if self._cot is None:
+            if self.device:
+                from . import hipops
+                self._cot = hipops.mesh_cotangent(self._state, self.verts, self.faces)
+            else:
+                self._cot = _cotangent_numpy(self.verts, self._state)
+        return self._cot if self.device or not isinstance(self.offsets, torch.Tensor) else torch.from_numpy(self._cot)
+
+    def _check(self, verts, faces):
+        if (isinstance(verts, torch.Tensor) and verts.is_cuda) != self.device or verts.shape[0] != self.n_verts or faces.shape[0] != self.n_faces:
+            raise ValueError('the adjacency was built for another mesh or on another device')
+
+
+def smooth_mesh(verts, faces, iterations=10, lam=0.5, mu=-0.53, weights='uniform', boundary='fixed', fixed=None, adjacency=None):
+    """Smooth a triangle mesh (verts float32 [V,3], faces [F,3]; the faces are not touched): Taubin's lambda | mu smoothing, which
+    removes ripples without shrinking the shape (``mu`` a float: ``iterations`` pairs of a step with ``lam`` and a step with ``mu``), or
+    plain Laplacian smoothing (``mu=None``: ``iterations`` steps with ``lam``), which shrinks.  Returns a dict: 'verts' float32 [V,3] in
+    the caller's container, 'pinned' bool [V], 'info' (the adjacency's, plus 'steps') and 'adjacency' (a ``MeshAdjacency``, to hand to
+    later calls on the same mesh).  The definition:
+
+    1. A face is usable if its three indices are distinct and its three vertices finite; other faces are skipped.  An index outside
+       [0, V) raises ``ValueError``.  Every usable face (a, b, c) contributes the directed entries (a,b) (b,a) (b,c) (c,b) (c,a) (a,c);
+       the neighbours of i are the distinct j with an entry (i, j), ascending; ``edge_faces(i, j)`` is the number of entries (i, j).  An
+       edge with one face is a boundary edge (its ends are boundary vertices), with more than two non-manifold.
+    2. ``weights='uniform'``: w_ij = 1.  ``'cotangent'``: w_ij = max(0, 1/2 sum cot theta) over the usable faces on the edge, theta
+       the angle opposite the edge at the INPUT positions, cot = dot(u, v) / |cross(u, v)| (0 for a face whose cross product is zero or
+       not finite), in double, summed in face order, stored as float32 and fixed for all iterations.
+    3. A pinned vertex keeps its input bits: a non-finite vertex, a vertex without neighbours or whose weights are all zero, a boundary
+       vertex under ``boundary='fixed'`` (``'free'``: boundary vertices move like any other), and where the bool mask ``fixed`` [V] is set.
+    4. One step with factor f moves every other vertex to ``fl32(p_i + f ((sum_j w_ij p_j) / (sum_j w_ij) - p_i))``: the sums in double
+       in ascending j, every p_j from the previous step (Jacobi), one rounding to float32 per step and coordinate.
+
+    ``iterations=0`` returns the input bits.  Device tensors run on the kernels of csrc/smooth.hip (no floating-point atomics, the order
+    of every sum fixed by the sorted layout: the same bits from run to run; no host synchronisation between the steps); CPU tensors and
+    NumPy arrays take the NumPy restatement of the same definition."""
+    _mesh_args(verts, faces)
+    if weights not in _WEIGHTS:
+        raise ValueError(f'weights must be one of {_WEIGHTS}, got {weights!r}')
+    if boundary not in _BOUNDARY:
+        raise ValueError(f'boundary must be one of {_BOUNDARY}, got {boundary!r}')
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f'iterations must be >= 0, got {iterations}')
+    factors = [float(lam)] * iterations if mu is None else [float(lam), float(mu)] * iterations
+    if not all(np.isfinite(x) for x in factors):
+        raise ValueError(f'lam and mu must be finite, got {lam!r} and {mu!r}')
+    nv = int(verts.shape[0])
+    if fixed is not None and tuple(fixed.shape) != (nv,):
+        raise ValueError(f'fixed must be a bool mask [{nv}], got {tuple(fixed.shape)}')
+    adj = MeshAdjacency(verts, faces) if adjacency is None else adjacency
+    adj._check(verts, faces)
+    info = dict(adj.info, steps=len(factors))
+    if adj.device:
+        from . import hipops
+        v = verts.detach().float().contiguous()
+        w = adj.cotangent() if weights == 'cotangent' else None
+        fx = None if fixed is None else torch.as_tensor(fixed).to(device=v.device, dtype=torch.bool).contiguous()
+        pinned = hipops.smooth_pinned(adj._state, v, w, boundary == 'fixed', fx)
+        out = hipops.smooth_steps(adj._state, v, w, pinned, factors)
+        return {'verts': out, 'pinned': pinned, 'info': info, 'adjacency': adj}
+    v = np.ascontiguousarray(_np(verts), dtype=F32)
+    if weights == 'cotangent':
+        adj.cotangent()
+    w = adj._cot if weights == 'cotangent' else None
+    pinned = _pinned_numpy(adj._state, w, boundary, None if fixed is None else _np(fixed).astype(bool))
+    out = v.copy()
+    move = ~pinned
+    out[move] = _smooth_numpy(v, adj._state, w, pinned, factors)[move].astype(F32)
+    return {'verts': _as_out(out, verts), 'pinned': _as_out(pinned, verts, bool), 'info': info, 'adjacency': adj}
+
+
+def mesh_normals(verts, faces, weighting='area', adjacency=None):
+    """Unit vertex normals float32 [V,3] from the mesh itself (no volume needed: a smoothed or simplified mesh, or one read with
+    ``read_ply``).  Per vertex the sum over its usable faces (see ``smooth_mesh``) in ascending face index of the raw cross product
+    ``(B - A) x (C - A)`` (``weighting='area'``) or of the unit face normal times the corner angle at the vertex (``'angle'``; a face
+    without area contributes 0), in double, normalised and stored as float32; (0, 0, 0) where the sum has zero or non-finite length.
+    Device tensors run on ia_mesh_normals (csrc/smooth.hip), CPU tensors and NumPy arrays on the NumPy restatement."""
+    _mesh_args(verts, faces)
+    if weighting not in _NORMAL_WEIGHTING:
+        raise ValueError(f'weighting must be one of {_NORMAL_WEIGHTING}, got {weighting!r}')
+    adj = MeshAdjacency(verts, faces) if adjacency is None else adjacency
+    adj._check(verts, faces)
+    if adj.device:
+        from . import hipops
+        return hipops.mesh_normals(adj._state, verts.detach().float().contiguous(), adj.faces, weighting == 'angle')
+    v = np.ascontiguousarray(_np(verts), dtype=F32)
+    return _as_out(_mesh_normals_numpy(v, adj.faces, adj._state, weighting), verts)
+
+
+def signed_volume(verts, faces):
+    """Signed volume of an indexed mesh (positive for a closed outward-wound one), float64 on the host; faces with a non-finite vertex
+    count 0."""
+    v, f = _np(verts).astype(np.float64), _np(faces).astype(np.int64)
+    if not f.shape[0]:
+        return 0.0
+    a, b, c = (v[f[:, k]] for k in range(3))
+    t = _dot3(a, _cross3(b, c))
+    return float(t[np.isfinite(t)].sum() / 6)
 
 
 # ------------------------------------------------------------------ generator-level helpers

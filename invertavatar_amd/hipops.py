@@ -1885,3 +1885,131 @@ def simplify_means(s, ocl, sums):
             st = lib.ia_simplify_means(_p(block), _p(ocl), _p(s['cstart']), s['K'], nv, nc, _p(out), c, c0, nv, _lib.stream_ptr(dev))
             _lib.check(st, 'ia_simplify_means')
     return out
+
+
+# ------------------------------------------------------------------ mesh smoothing and mesh normals (csrc/smooth.hip)
+
+SMOOTH_TIMES = None          # a dict collects seconds per phase (each phase then ends in a device synchronise): tools/bench_smooth.py
+
+
+class _SmoothPhase(_Phase):
+    def __enter__(self):
+        if SMOOTH_TIMES is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            self.t0 = time.perf_counter()
+        return self
+
+    def __exit__(self, *exc):
+        if SMOOTH_TIMES is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            SMOOTH_TIMES[self.name] = SMOOTH_TIMES.get(self.name, 0.0) + time.perf_counter() - self.t0
+        return False
+
+
+def mesh_adjacency(verts, faces):
+    """The neighbourhood structure of a mesh (verts float32 [V,3], faces int32 [F,3]) as a dict of device arrays: 'offsets',
+    'neighbors', 'edge_faces', 'boundary', 'face_offsets', 'face_ids' (see geometry.MeshAdjacency), the host dict 'info', the flag
+    'out_of_range' and what ``mesh_cotangent`` and ``smooth_steps`` need (ia_mesh_edge_keys, _edge_heads, _csr; the two key sorts are
+    torch.sort).  Two host synchronisations."""
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise RuntimeError('a mesh is verts [V,3] and faces [F,3] on one device')
+    lib, dev = _lib.load(), verts.device
+    v, f = verts.shape[0], faces.shape[0]
+    i32 = dict(dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        count = torch.empty(8, **i32)
+        with _SmoothPhase('keys', dev):
+            ekeys, vkeys = torch.empty(6 * f, dtype=torch.int64, device=dev), torch.empty(3 * f, dtype=torch.int64, device=dev)
+            _lib.check(lib.ia_mesh_edge_keys(_p(verts), v, _p(faces), f, _p(ekeys), _p(vkeys), _p(count), stream), 'ia_mesh_edge_keys')
+        with _SmoothPhase('sorts', dev):
+            skeys, order = torch.sort(ekeys, stable=True)
+            svkeys, vorder = torch.sort(vkeys, stable=True)
+            del ekeys, vkeys
+        with _SmoothPhase('csr', dev):
+            nbytes = ctypes.c_size_t(0)
+            _lib.check(lib.ia_mesh_edge_heads_scratch_bytes(f, ctypes.byref(nbytes)), 'ia_mesh_edge_heads_scratch_bytes')
+            scratch = torch.empty(nbytes.value // 4, **i32)
+            _lib.check(lib.ia_mesh_edge_heads(_p(skeys), f, _p(scratch), nbytes.value, _p(count), stream), 'ia_mesh_edge_heads')
+            head = count.cpu().tolist()
+            usable, oob, e = head[0], bool(head[1]), head[7]
+            s = {'V': v, 'F': f, 'E': e, 'out_of_range': oob, 'order': order}
+            if oob:
+                return s
+            offsets, face_offsets = torch.empty(v + 1, **i32), torch.empty(v + 1, **i32)
+            neighbors, edge_faces, run_start = torch.empty(e, **i32), torch.empty(e, **i32), torch.empty(e, **i32)
+            slot_keys = torch.empty(e, dtype=torch.int64, device=dev)
+            boundary = torch.empty(v, dtype=torch.bool, device=dev)
+            face_ids, heavy = torch.empty(3 * usable, **i32), torch.empty(max(v, 1), **i32)
+            st = lib.ia_mesh_csr(_p(skeys), _p(svkeys), _p(vorder), v, f, usable, e, _p(scratch), _p(offsets), _p(neighbors), _p(edge_faces),
+                                 _p(run_start), _p(slot_keys), _p(boundary), _p(face_offsets), _p(face_ids), _p(heavy), _p(count), stream)
+            _lib.check(st, 'ia_mesh_csr')
+            c = count.cpu().tolist()
+    s.update(offsets=offsets, neighbors=neighbors, edge_faces=edge_faces, boundary=boundary, face_offsets=face_offsets, face_ids=face_ids,
+             run_start=run_start, slot_keys=slot_keys, heavy=heavy, n_heavy=c[6],
+             info={'edges': e // 2, 'boundary_edges': c[2] // 2, 'nonmanifold_edges': c[3] // 2, 'boundary_verts': c[4], 'usable_faces': usable,
+                   'max_degree': c[5]})
+    return s
+
+
+def mesh_cotangent(s, verts, faces):
+    """float32 [E]: the cotangent weight of every directed edge of a ``mesh_adjacency`` state (ia_mesh_cotangent)."""
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    dev = verts.device
+    w = torch.empty(s['E'], device=dev)
+    with torch.cuda.device(dev), _SmoothPhase('cotangent', dev):
+        st = _lib.load().ia_mesh_cotangent(_p(verts), s['V'], _p(faces), s['F'], _p(s['order']), _p(s['slot_keys']), _p(s['run_start']),
+                                           _p(s['edge_faces']), s['E'], _p(w), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_cotangent')
+    return w
+
+
+def smooth_pinned(s, verts, weights, fix_boundary, fixed):
+    """bool [V]: the vertices that a smoothing step leaves alone (ia_smooth_pinned)."""
+    _f32c(verts, 'verts')
+    dev = verts.device
+    if verts.shape[0] != s['V'] or (weights is not None and (weights.numel() != s['E'] or weights.dtype != torch.float32)):
+        raise RuntimeError('verts and weights must match the adjacency')
+    if fixed is not None and not (fixed.is_cuda and fixed.dtype == torch.bool and fixed.is_contiguous() and fixed.numel() == s['V']):
+        raise RuntimeError('fixed must be a contiguous bool [V] device tensor')
+    pinned = torch.empty(s['V'], dtype=torch.bool, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.load().ia_smooth_pinned(_p(verts), s['V'], _p(s['offsets']), _p(weights), _p(s['boundary']), int(bool(fix_boundary)), _p(fixed),
+                                          _p(pinned), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_smooth_pinned')
+    return pinned
+
+
+def smooth_steps(s, verts, weights, pinned, factors):
+    """float32 [V,3]: ``verts`` after one Jacobi step per factor (ia_smooth_steps: every launch on the current stream, no host
+    synchronisation).  ``verts`` is not written."""
+    _f32c(verts, 'verts')
+    dev = verts.device
+    a, b = verts.clone(), torch.empty_like(verts)
+    n = len(factors)
+    if n == 0 or s['V'] == 0:
+        return a
+    fac = (ctypes.c_double * n)(*[float(x) for x in factors])
+    with torch.cuda.device(dev), _SmoothPhase('steps', dev):
+        st = _lib.load().ia_smooth_steps(_p(a), _p(b), s['V'], _p(s['offsets']), _p(s['neighbors']), _p(weights), _p(pinned), _p(s['heavy']),
+                                         s['n_heavy'], fac, n, _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_smooth_steps')
+    return a if n % 2 == 0 else b
+
+
+def mesh_normals(s, verts, faces, angle=False):
+    """float32 [V,3]: unit vertex normals from the mesh (ia_mesh_normals)."""
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    dev = verts.device
+    out = torch.empty(s['V'], 3, device=dev)
+    with torch.cuda.device(dev), _SmoothPhase('normals', dev):
+        st = _lib.load().ia_mesh_normals(_p(verts), s['V'], _p(faces), s['F'], _p(s['face_offsets']), _p(s['face_ids']), int(bool(angle)),
+                                         _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_normals')
+    return out

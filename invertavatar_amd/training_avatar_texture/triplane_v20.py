@@ -535,7 +535,7 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         with_normals=False, keep=None, min_voxels=0, simplify=None, **synthesis_kwargs):
+                         with_normals=False, keep=None, min_voxels=0, simplify=None, smooth=None, **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
@@ -548,7 +548,11 @@ class TriPlaneGenerator(torch.nn.Module):
         ``geometry.simplify_mesh`` keyword arguments) simplifies the mesh after the filter and marching cubes: 'verts' and 'faces' are
         then the simplified mesh, colours and normals are queried at its vertices (exact there, and cheaper than averaging), and
         'simplify' holds {'dims', 'cell_size', 'faces_before', 'faces_after', 'verts_before', 'verts_after'} (and 'steps' with a
-        target).  The planes are computed once per call; device tensors stay on the device throughout."""
+        target).  ``smooth`` (None: nothing changes; an int = Taubin pairs with the defaults of ``geometry.smooth_mesh``; or a dict of
+        its keyword arguments) smooths the mesh after the filter and after ``simplify``: 'faces' stay, 'verts' move, colours are
+        queried at the final vertices, normals come from the mesh (``geometry.mesh_normals``) instead of the volume, and 'smooth' holds
+        the smoothing's 'info' ('edges', 'boundary_edges', 'nonmanifold_edges', 'steps', ...).  The planes are computed once per call;
+        device tensors stay on the device throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
         length = box_warp if cube_length is None else cube_length
@@ -573,9 +577,17 @@ class TriPlaneGenerator(torch.nn.Module):
                                     'verts_after': int(simple['verts'].shape[0]), **({'steps': simple['steps']} if 'steps' in simple else {})}
                 verts, faces = simple['verts'], simple['faces']
                 item['verts'], item['faces'] = verts, faces
+            adjacency = None
+            if smooth is not None:
+                kw = dict(smooth) if isinstance(smooth, dict) else {'iterations': int(smooth)}
+                smoothed = geometry.smooth_mesh(verts, faces, **kw)
+                verts, adjacency = smoothed['verts'], smoothed['adjacency']
+                item['verts'], item['smooth'] = verts, dict(smoothed['info'])
             if with_colors:
                 item['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, verts, box_warp)
-            if with_normals:
+            if with_normals and smooth is not None:
+                item['normals'] = geometry.mesh_normals(verts, faces, adjacency=adjacency)
+            elif with_normals:
                 item['normals'] = geometry.volume_normals(vol_b, verts, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
             out.append(item)
         return out

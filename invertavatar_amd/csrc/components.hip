@@ -21,18 +21,19 @@
 // cannot see (outside the tile, in the tile pass) counts as outside, which only ever adds a redundant union.
 //
 // Only integer atomics (min on parents; add / min / max in the statistics): labels and statistics are bit-reproducible.
-#include "ia_common.h"
+#include "geom_common.h"
 
 #include <climits>
 
 namespace {
+
+using ia::blocks; using ia::check_volume; using ia::kScanBlock; using ia::on_device; using ia::unravel;
 
 constexpr int kBlock = 256;
 constexpr int kTX = 8, kTY = 8, kTZ = 64;            // tile: 64 rows of 64 points, 16 rows per wave
 constexpr int kRows = kTX * kTY, kTilePts = kRows * kTZ;
 constexpr int kPer = 4;                              // consecutive points per thread in the linear passes
 constexpr int kChunk = kBlock * kPer;
-constexpr int kScanBlock = 1024;
 constexpr int kRun = 8;                              // consecutive items per thread in the statistics
 
 struct CcVol {
@@ -185,13 +186,6 @@ __global__ __launch_bounds__(kBlock) void cc_seam_kernel(CcVol m, int* parent) {
     }
 }
 
-__device__ __forceinline__ void unravel(int n, int ny, int nz, int& i, int& j, int& k) {
-    const unsigned u = (unsigned)n, q = u / (unsigned)nz;
-    k = (int)(u - q * (unsigned)nz);
-    i = (int)(q / (unsigned)ny);
-    j = (int)(q - (unsigned)i * (unsigned)ny);
-}
-
 // A point whose parent lies in another tile was a tile root; it jumps to its root now, so that the points below it find the root in
 // a few steps.  Readers see the old or the new parent, both ancestors.
 __global__ __launch_bounds__(kBlock) void cc_shortcut_kernel(int* parent, int64_t N, int ny, int nz) {
@@ -210,22 +204,6 @@ __global__ __launch_bounds__(kBlock) void cc_shortcut_kernel(int* parent, int64_
     g_store(parent + n, g_find(parent, y));
 }
 
-__device__ __forceinline__ void block_scan(int a, int& excl, int& total) {
-    __shared__ int s[kBlock];
-    const int t = threadIdx.x;
-    s[t] = a;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const int x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    excl = s[t] - a;
-    total = s[kBlock - 1];
-    __syncthreads();
-}
-
 // root[n] = root of n (-1 outside); chunk_cnt[chunk] = roots in the chunk.  parent is read-only here.
 __global__ __launch_bounds__(kBlock) void cc_flatten_kernel(const int* __restrict__ parent, int64_t N, int* __restrict__ root,
                                                            int* __restrict__ chunk_cnt) {
@@ -241,33 +219,14 @@ __global__ __launch_bounds__(kBlock) void cc_flatten_kernel(const int* __restric
         root[n] = x;
     }
     int excl, total;
-    block_scan(cnt, excl, total);
+    ia::block_scan<kBlock>(cnt, excl, total);
     if (threadIdx.x == 0) chunk_cnt[blockIdx.x] = total;
 }
 
 // One workgroup: chunk counts -> exclusive offsets in place, count[0] = K.
-__global__ __launch_bounds__(kScanBlock) void cc_scan_kernel(int* __restrict__ chunk_cnt, int n_chunks, int* __restrict__ count) {
-    __shared__ int s[kScanBlock];
-    const int t = threadIdx.x;
-    const int per = (n_chunks + kScanBlock - 1) / kScanBlock;
-    const int c0 = min(t * per, n_chunks), c1 = min(c0 + per, n_chunks);
-    int a = 0;
-    for (int c = c0; c < c1; ++c) a += chunk_cnt[c];
-    s[t] = a;
-    __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        const int x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    int run = s[t] - a;
-    for (int c = c0; c < c1; ++c) {
-        const int v = chunk_cnt[c];
-        chunk_cnt[c] = run;
-        run += v;
-    }
-    if (t == kScanBlock - 1) count[0] = s[t];         // K <= N < 2^31
+__global__ __launch_bounds__(kScanBlock) void cc_scan_kernel(int* chunk_cnt, int n_chunks, int* __restrict__ count) {
+    const int total = ia::scan_workgroup<int>(chunk_cnt, chunk_cnt, n_chunks);
+    if (threadIdx.x == 0) count[0] = total;          // K <= N < 2^31
 }
 
 // rank[r] = 0-based rank of root r in index order (only root entries are written).
@@ -277,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void cc_rank_kernel(const int* __restrict__
     int cnt = 0;
     for (int q = 0; q < kPer && n0 + q < N; ++q) cnt += root[n0 + q] == (int)(n0 + q);
     int excl, total;
-    block_scan(cnt, excl, total);
+    ia::block_scan<kBlock>(cnt, excl, total);
     int id = chunk_off[blockIdx.x] + excl;
     for (int q = 0; q < kPer && n0 + q < N; ++q)
         if (root[n0 + q] == (int)(n0 + q)) rank[n0 + q] = id++;
@@ -389,24 +348,7 @@ __global__ __launch_bounds__(kBlock) void mesh_stats_faces_kernel(const int* __r
 
 // ------------------------------------------------------------------ host side
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-int check_volume(int nx, int ny, int nz, const char* what) {
-    if (nx < 2 || ny < 2 || nz < 2) return ia::fail(IA_ERR_INVALID_ARG, "%s: every dimension must be >= 2, got %d x %d x %d", what, nx, ny, nz);
-    if ((int64_t)nx * ny * nz >= ((int64_t)1 << 31))
-        return ia::fail(IA_ERR_INVALID_ARG, "%s: %d x %d x %d volume has 2^31 points or more (int32 point indices)", what, nx, ny, nz);
-    return IA_OK;
-}
-
 size_t linear_scratch(int64_t n) { return sizeof(int) * ((size_t)n + (size_t)ia::ceil_div(n, kChunk)); }
-
-unsigned blocks(int64_t n, int per) { return (unsigned)ia::ceil_div(n < 1 ? 1 : n, per); }
 
 // flatten .. relabel over a parent array of n entries: labels and count[0] = K.
 int number_components(int* parent, int64_t n, int* labels, int* count, hipStream_t s, const char* what) {

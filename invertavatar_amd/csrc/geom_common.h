@@ -1,0 +1,140 @@
+// Primitives shared by the geometry translation units (geometry, raycast, components, surface_distance, simplify, smooth): scans,
+// wave reductions, 3-vectors, lattice helpers and the host-side argument checks.  Device code is __forceinline__ functions and
+// templates only, no kernels: every .hip is its own code object, so a kernel that needs one of these (the scan) is a wrapper of a few
+// lines in that file's anonymous namespace.  Every operation order here is part of the results (geometry.py restates them in NumPy).
+#pragma once
+
+#include "ia_common.h"
+
+namespace ia {
+
+// ------------------------------------------------------------------ scans
+
+constexpr int kScanBlock = 1024;
+
+// Exclusive scan of in[0 .. n) into out[0 .. n) by ONE workgroup of kScanBlock threads; returns the total to every thread.  A thread
+// sums a contiguous slice, the partial sums are scanned in LDS (Hillis-Steele) and the slice is written back with a running sum.
+// in == out is allowed.  Acc: the type the sums are carried in (out receives its low 32 bits).
+template <class Acc>
+__device__ __forceinline__ Acc scan_workgroup(const int* in, int* out, int64_t n) {
+    __shared__ Acc s[kScanBlock];
+    const int t = threadIdx.x;
+    const int64_t per = (n + kScanBlock - 1) / kScanBlock;
+    const int64_t c0 = min((int64_t)t * per, n), c1 = min(c0 + per, n);
+    Acc a = 0;
+    for (int64_t c = c0; c < c1; ++c) a += in[c];
+    s[t] = a;
+    __syncthreads();
+    for (int off = 1; off < kScanBlock; off <<= 1) {
+        const Acc x = t >= off ? s[t - off] : 0;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    Acc run = s[t] - a;
+    for (int64_t c = c0; c < c1; ++c) {
+        const int v = in[c];
+        out[c] = (int)run;
+        run += v;
+    }
+    const Acc total = s[kScanBlock - 1];
+    __syncthreads();                                                      // (s may be written again by a following call)
+    return total;
+}
+
+// Exclusive scan of one int per thread over a workgroup of kThreads threads, and the workgroup total.
+template <int kThreads>
+__device__ __forceinline__ void block_scan(int a, int& excl, int& total) {
+    __shared__ int s[kThreads];
+    const int t = threadIdx.x;
+    s[t] = a;
+    __syncthreads();
+    for (int off = 1; off < kThreads; off <<= 1) {
+        const int x = t >= off ? s[t - off] : 0;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    excl = s[t] - a;
+    total = s[kThreads - 1];
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------ wave reductions (every lane receives the result)
+
+__device__ __forceinline__ float lesser(float a, float b) { return fminf(a, b); }      // fminf / fmaxf, fmin / fmax drop a NaN
+__device__ __forceinline__ double lesser(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ int lesser(int a, int b) { return min(a, b); }
+__device__ __forceinline__ float greater(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double greater(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ int greater(int a, int b) { return max(a, b); }
+
+// Butterfly from offset 32 down to 1: every lane combines the same pairs, so a floating-point sum has one order and one result.
+template <class T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = lesser(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = greater(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// *dst += number of lanes of the wave with `p` set: a ballot and one integer atomic by the first such lane.
+__device__ __forceinline__ void wave_count(bool p, int* dst) {
+    const unsigned long long m = __ballot(p);
+    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(dst, __popcll(m));
+}
+
+// ------------------------------------------------------------------ 3-vectors, cells, lattice indices
+
+template <class T> struct Vec3 { T x, y, z; };
+
+template <class T> __device__ __forceinline__ Vec3<T> sub(Vec3<T> a, Vec3<T> b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+template <class T> __device__ __forceinline__ T dot(Vec3<T> a, Vec3<T> b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+template <class T> __device__ __forceinline__ Vec3<T> cross(Vec3<T> a, Vec3<T> b) {
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+template <class T> __device__ __forceinline__ bool finite3(Vec3<T> a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+
+// Cell of coordinate x along an axis of n cells that starts at lo, inv = 1 / cell size; a NaN lands in cell 0.
+__device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
+    return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));
+}
+
+// Linear point index n (0 <= n < 2^31, z fastest) of an [nx, ny, nz] lattice -> (i, j, k).
+__device__ __forceinline__ void unravel(int n, int ny, int nz, int& i, int& j, int& k) {
+    const unsigned u = (unsigned)n, q = u / (unsigned)nz;
+    k = (int)(u - q * (unsigned)nz);
+    i = (int)(q / (unsigned)ny);
+    j = (int)(q - (unsigned)i * (unsigned)ny);
+}
+
+// ------------------------------------------------------------------ host side
+
+inline bool on_device(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
+}
+
+// A lattice volume: every dimension >= 2 and fewer than 2^31 points (point, vertex and label indices are int32).
+inline int check_volume(int nx, int ny, int nz, const char* what) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail(IA_ERR_INVALID_ARG, "%s: every dimension must be >= 2, got %d x %d x %d", what, nx, ny, nz);
+    if ((int64_t)nx * ny * nz >= ((int64_t)1 << 31))
+        return fail(IA_ERR_INVALID_ARG, "%s: %d x %d x %d volume has 2^31 points or more", what, nx, ny, nz);
+    return IA_OK;
+}
+
+// Workgroups of `per` items that cover n items (at least one).
+inline unsigned blocks(int64_t n, int per) { return (unsigned)ceil_div(n < 1 ? 1 : n, per); }
+
+}  // namespace ia

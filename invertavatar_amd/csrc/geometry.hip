@@ -19,12 +19,14 @@
 //           (2) recounts each chunk's cells and writes their triangles at the scanned offsets, in table order (mc_tables.h), looking the
 //               vertex ids of the cell's edges up in vbase.
 // No atomics: the output is a function of the volume alone, bit for bit.  Every output write is checked against the caller's capacity.
-#include "ia_common.h"
+#include "geom_common.h"
 
 #define IA_MC_TABLE_QUALIFIER static __constant__ const
 #include "mc_tables.h"
 
 namespace {
+
+using ia::block_scan; using ia::check_volume; using ia::kScanBlock; using ia::on_device; using ia::streaming_grid;
 
 constexpr int kBlock = 256;
 constexpr int kHidden = 64;
@@ -188,7 +190,6 @@ __global__ __launch_bounds__(kBlock) void density_grid_kernel(const float* __res
 
 constexpr int kMcPer = 4;                       // consecutive points per thread
 constexpr int kMcChunk = kBlock * kMcPer;       // points per workgroup
-constexpr int kScanBlock = 1024;
 
 struct McVol {
     const float* v;
@@ -221,33 +222,8 @@ __device__ __forceinline__ void classify(const McVol& m, int64_t n, int i, int j
     }
 }
 
-__device__ __forceinline__ void unravel(const McVol& m, int64_t n, int& i, int& j, int& k) {
-    const unsigned u = (unsigned)n, nz = (unsigned)m.nz, ny = (unsigned)m.ny;      // n < 2^31
-    const unsigned q = u / nz;
-    k = (int)(u - q * nz);
-    i = (int)(q / ny);
-    j = (int)(q - (unsigned)i * ny);
-}
-
 __device__ __forceinline__ void step_point(const McVol& m, int& i, int& j, int& k) {
     if (++k == m.nz) { k = 0; if (++j == m.ny) { j = 0; ++i; } }
-}
-
-// Exclusive workgroup scan of two ints (kBlock threads); returns the workgroup totals too.
-__device__ __forceinline__ void block_scan2(int a, int b, int& ea, int& eb, int& ta, int& tb) {
-    __shared__ int sa[kBlock], sb[kBlock];
-    const int t = threadIdx.x;
-    sa[t] = a; sb[t] = b;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const int xa = t >= off ? sa[t - off] : 0, xb = t >= off ? sb[t - off] : 0;
-        __syncthreads();
-        sa[t] += xa; sb[t] += xb;
-        __syncthreads();
-    }
-    ea = sa[t] - a; eb = sb[t] - b;
-    ta = sa[kBlock - 1]; tb = sb[kBlock - 1];
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(kBlock) void mc_count_kernel(McVol m, int* __restrict__ chunk_v, int* __restrict__ chunk_t) {
@@ -255,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void mc_count_kernel(McVol m, int* __restri
     int nv = 0, nt = 0;
     if (n0 < m.N) {
         int i, j, k;
-        unravel(m, n0, i, j, k);
+        ia::unravel((int)n0, m.ny, m.nz, i, j, k);
         for (int q = 0; q < kMcPer && n0 + q < m.N; ++q, step_point(m, i, j, k)) {
             int vmask, cfg;
             float cv[8];
@@ -264,37 +240,19 @@ __global__ __launch_bounds__(kBlock) void mc_count_kernel(McVol m, int* __restri
             nt += cfg >= 0 ? (int)ia_mc_tri_count[cfg] : 0;
         }
     }
-    int ea, eb, ta, tb;
-    block_scan2(nv, nt, ea, eb, ta, tb);
-    if (threadIdx.x == 0) { chunk_v[blockIdx.x] = ta; chunk_t[blockIdx.x] = tb; }
+    int excl, tv, tt;
+    block_scan<kBlock>(nv, excl, tv);
+    block_scan<kBlock>(nt, excl, tt);
+    if (threadIdx.x == 0) { chunk_v[blockIdx.x] = tv; chunk_t[blockIdx.x] = tt; }
 }
 
 // One workgroup: chunk counts -> exclusive chunk offsets (in place), totals -> totals[0..1] (-1 where a total exceeds INT32_MAX).
-__global__ __launch_bounds__(kScanBlock) void mc_scan_kernel(int* __restrict__ chunk_v, int* __restrict__ chunk_t, int n_chunks,
-                                                            int* __restrict__ totals) {
-    __shared__ long long sv[kScanBlock], st[kScanBlock];
-    const int t = threadIdx.x;
-    const int per = (n_chunks + kScanBlock - 1) / kScanBlock;
-    const int c0 = min(t * per, n_chunks), c1 = min(c0 + per, n_chunks);
-    long long a = 0, b = 0;
-    for (int c = c0; c < c1; ++c) { a += chunk_v[c]; b += chunk_t[c]; }
-    sv[t] = a; st[t] = b;
-    __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        const long long xa = t >= off ? sv[t - off] : 0, xb = t >= off ? st[t - off] : 0;
-        __syncthreads();
-        sv[t] += xa; st[t] += xb;
-        __syncthreads();
-    }
-    long long ra = sv[t] - a, rb = st[t] - b;
-    for (int c = c0; c < c1; ++c) {
-        const int va = chunk_v[c], vb = chunk_t[c];
-        chunk_v[c] = (int)ra; chunk_t[c] = (int)rb;      // (wraps only when the total does, which the caller sees as -1)
-        ra += va; rb += vb;
-    }
-    if (t == kScanBlock - 1) {
-        totals[0] = sv[t] <= INT32_MAX ? (int)sv[t] : -1;
-        totals[1] = st[t] <= INT32_MAX ? (int)st[t] : -1;
+__global__ __launch_bounds__(kScanBlock) void mc_scan_kernel(int* chunk_v, int* chunk_t, int n_chunks, int* __restrict__ totals) {
+    const long long tv = ia::scan_workgroup<long long>(chunk_v, chunk_v, n_chunks);      // (an offset wraps only when the total does,
+    const long long tt = ia::scan_workgroup<long long>(chunk_t, chunk_t, n_chunks);      //  which the caller sees as -1)
+    if (threadIdx.x == 0) {
+        totals[0] = tv <= INT32_MAX ? (int)tv : -1;
+        totals[1] = tt <= INT32_MAX ? (int)tt : -1;
     }
 }
 
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void mc_emit_verts_kernel(McVol m, McOut o)
     int masks[kMcPer] = {0, 0, 0, 0};
     int nv = 0, i = 0, j = 0, k = 0;
     if (n0 < m.N) {
-        unravel(m, n0, i, j, k);
+        ia::unravel((int)n0, m.ny, m.nz, i, j, k);
         int ii = i, jj = j, kk = k;
         for (int q = 0; q < kMcPer && n0 + q < m.N; ++q, step_point(m, ii, jj, kk)) {
             int cfg;
@@ -325,8 +283,8 @@ __global__ __launch_bounds__(kBlock) void mc_emit_verts_kernel(McVol m, McOut o)
             nv += __popc(masks[q]);
         }
     }
-    int ea, eb, ta, tb;
-    block_scan2(nv, 0, ea, eb, ta, tb);
+    int ea, total;
+    block_scan<kBlock>(nv, ea, total);
     if (n0 >= m.N) return;
     int64_t vid = (int64_t)o.chunk_v[blockIdx.x] + ea;
     for (int q = 0; q < kMcPer && n0 + q < m.N; ++q, step_point(m, i, j, k)) {
@@ -359,7 +317,7 @@ __global__ __launch_bounds__(kBlock) void mc_emit_faces_kernel(McVol m, McOut o)
     const int64_t n0 = (int64_t)blockIdx.x * kMcChunk + (int64_t)threadIdx.x * kMcPer;
     int nt = 0, i = 0, j = 0, k = 0;
     if (n0 < m.N) {
-        unravel(m, n0, i, j, k);
+        ia::unravel((int)n0, m.ny, m.nz, i, j, k);
         int ii = i, jj = j, kk = k;
         for (int q = 0; q < kMcPer && n0 + q < m.N; ++q, step_point(m, ii, jj, kk)) {
             int vmask, cfg;
@@ -368,8 +326,8 @@ __global__ __launch_bounds__(kBlock) void mc_emit_faces_kernel(McVol m, McOut o)
             nt += cfg >= 0 ? (int)ia_mc_tri_count[cfg] : 0;
         }
     }
-    int ea, eb, ta, tb;
-    block_scan2(nt, 0, ea, eb, ta, tb);
+    int ea, total;
+    block_scan<kBlock>(nt, ea, total);
     if (n0 >= m.N) return;
     int64_t fid = (int64_t)o.chunk_t[blockIdx.x] + ea;
     for (int q = 0; q < kMcPer && n0 + q < m.N; ++q, step_point(m, i, j, k)) {
@@ -410,19 +368,6 @@ __global__ __launch_bounds__(kBlock) void mc_emit_faces_kernel(McVol m, McOut o)
 
 // ------------------------------------------------------------------ host side
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-int persistent_grid(int64_t work, int per_block) {
-    const int64_t g = ia::ceil_div(work, per_block), cap = (int64_t)ia::kNumCU * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 int check_decoder(const float* planes_cl, const float* w0, const float* b0, const float* w1, const float* b1, int B, int PH, int PW,
                   float box_warp, const char* what) {
     if (!(on_device(planes_cl) && on_device(w0) && on_device(b0) && on_device(w1) && on_device(b1)))
@@ -434,13 +379,6 @@ int check_decoder(const float* planes_cl, const float* w0, const float* b0, cons
 
 DecoderArgs decoder_args(const float* w0, const float* b0, const float* w1, const float* b1, float lr) {
     return DecoderArgs{w0, b0, w1, b1, (float)((double)lr / sqrt((double)kFeat)), (float)((double)lr / sqrt((double)kHidden)), lr};
-}
-
-int check_volume(int nx, int ny, int nz, const char* what) {
-    if (nx < 2 || ny < 2 || nz < 2) return ia::fail(IA_ERR_INVALID_ARG, "%s: every dimension must be >= 2, got %d x %d x %d", what, nx, ny, nz);
-    if ((int64_t)nx * ny * nz >= ((int64_t)1 << 31))
-        return ia::fail(IA_ERR_INVALID_ARG, "%s: %d x %d x %d volume has 2^31 points or more (int32 vertex and point indices)", what, nx, ny, nz);
-    return IA_OK;
 }
 
 int64_t n_chunks(int nx, int ny, int nz) { return ia::ceil_div((int64_t)nx * ny * nz, kMcChunk); }
@@ -464,7 +402,7 @@ extern "C" int ia_query_planes(const float* planes_cl, const float* points, cons
     const DecoderArgs da = decoder_args(w0, b0, w1, b1, lr_multiplier);
     const float scale = (float)(2.0 / (double)box_warp);
     const int flip = (flags & IA_GEOM_FLIP_Z) ? 1 : 0;
-    const int grid = persistent_grid((int64_t)B * M, kBlock);
+    const int grid = streaming_grid((int64_t)B * M, kBlock);
     hipStream_t s = (hipStream_t)stream;
     if (rgb)
         query_planes_kernel<true><<<grid, kBlock, 0, s>>>(planes_cl, points, da, scale, flip, B, M, plane_h, plane_w, sigma, rgb);
@@ -489,7 +427,7 @@ extern "C" int ia_density_grid(const float* planes_cl, const float* w0, const fl
     }
     const DecoderArgs da = decoder_args(w0, b0, w1, b1, lr_multiplier);
     const int64_t tiles = ia::ceil_div(nx, kTileX) * ia::ceil_div(ny, kTileY) * ia::ceil_div(nz, kTileZ) * B;
-    const int grid = persistent_grid(tiles, 1);
+    const int grid = streaming_grid(tiles, 1);
     density_grid_kernel<<<grid, kBlock, 0, (hipStream_t)stream>>>(planes_cl, da, (float)(2.0 / (double)box_warp),
                                                                  (flags & IA_GEOM_FLIP_Z) ? 1 : 0, B, plane_h, plane_w, lat, volume);
     return ia::check_launch("ia_density_grid");

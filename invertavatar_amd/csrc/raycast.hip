@@ -14,9 +14,11 @@
 //   are -g/|g| of the trilinear interpolation of the corners' central-difference gradients (one-sided at the border).
 // ia_volume_gradient: that interpolated gradient at arbitrary points (clamped into the box): vertex normals of the marching-cubes mesh.
 // No atomics and no host synchronisation: every output is a pure function of the inputs.  Every load index is clamped to the lattice.
-#include "ia_common.h"
+#include "geom_common.h"
 
 namespace {
+
+using ia::check_volume; using ia::on_device;
 
 constexpr int kBlock = 256;
 constexpr int kBrick = 8;              // cells per brick edge
@@ -46,11 +48,8 @@ __global__ __launch_bounds__(64) void volume_bricks_kernel(RcVol m, int nbx, int
         lo = fminf(lo, v);                                     // fminf / fmaxf drop a NaN
         hi = fmaxf(hi, v);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
+    lo = ia::wave_min(lo);
+    hi = ia::wave_max(hi);
     if (threadIdx.x == 0) bricks[b] = make_float2(lo, hi);
 }
 
@@ -287,21 +286,6 @@ __global__ __launch_bounds__(kBlock) void raycast_kernel(RcVol m, RcRays R) {
 
 // ------------------------------------------------------------------ host side
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-int check_dims(int nx, int ny, int nz, const char* what) {
-    if (nx < 2 || ny < 2 || nz < 2) return ia::fail(IA_ERR_INVALID_ARG, "%s: every dimension must be >= 2, got %d x %d x %d", what, nx, ny, nz);
-    if ((int64_t)nx * ny * nz >= ((int64_t)1 << 31))
-        return ia::fail(IA_ERR_INVALID_ARG, "%s: %d x %d x %d volume has 2^31 points or more", what, nx, ny, nz);
-    return IA_OK;
-}
-
 void brick_dims(int nx, int ny, int nz, int (&nb)[3]) {
     nb[0] = (int)ia::ceil_div(nx - 1, kBrick);
     nb[1] = (int)ia::ceil_div(ny - 1, kBrick);
@@ -329,14 +313,14 @@ int make_vol(const float* volume, int nx, int ny, int nz, const float* h_lo, con
 }  // namespace
 
 extern "C" int ia_raycast_scratch_bytes(int nx, int ny, int nz, size_t* h_bytes) {
-    if (int st = check_dims(nx, ny, nz, "ia_raycast_scratch_bytes")) return st;
+    if (int st = check_volume(nx, ny, nz, "ia_raycast_scratch_bytes")) return st;
     IA_REQUIRE(h_bytes, "ia_raycast_scratch_bytes: h_bytes must not be NULL");
     *h_bytes = brick_bytes(nx, ny, nz);
     return IA_OK;
 }
 
 extern "C" int ia_volume_bricks(const float* volume, int nx, int ny, int nz, void* bricks, size_t bricks_bytes, void* stream) {
-    if (int st = check_dims(nx, ny, nz, "ia_volume_bricks")) return st;
+    if (int st = check_volume(nx, ny, nz, "ia_volume_bricks")) return st;
     if (!on_device(volume) || !on_device(bricks))
         return ia::fail(IA_ERR_INVALID_ARG, "ia_volume_bricks: volume and bricks must be device pointers");
     if (bricks_bytes < brick_bytes(nx, ny, nz))
@@ -351,7 +335,7 @@ extern "C" int ia_volume_bricks(const float* volume, int nx, int ny, int nz, voi
 extern "C" int ia_raycast_volume(const float* volume, int nx, int ny, int nz, const float* h_lo, const float* h_step, float level,
                                  const void* bricks, size_t bricks_bytes, const float* rays_o, const float* rays_d, int n_rays, float t_min,
                                  float* depth, float* normal, unsigned char* mask, int flags, void* stream) {
-    if (int st = check_dims(nx, ny, nz, "ia_raycast_volume")) return st;
+    if (int st = check_volume(nx, ny, nz, "ia_raycast_volume")) return st;
     IA_REQUIRE(n_rays > 0, "ia_raycast_volume: n_rays must be > 0, got %d", n_rays);
     IA_REQUIRE(!std::isnan(level) && !std::isnan(t_min), "ia_raycast_volume: level and t_min must not be NaN");
     RcVol m;
@@ -376,7 +360,7 @@ extern "C" int ia_raycast_volume(const float* volume, int nx, int ny, int nz, co
 
 extern "C" int ia_volume_gradient(const float* volume, int nx, int ny, int nz, const float* h_lo, const float* h_step, const float* points,
                                   int n, float* grad, void* stream) {
-    if (int st = check_dims(nx, ny, nz, "ia_volume_gradient")) return st;
+    if (int st = check_volume(nx, ny, nz, "ia_volume_gradient")) return st;
     IA_REQUIRE(n >= 0, "ia_volume_gradient: n must be >= 0, got %d", n);
     RcVol m;
     if (int st = make_vol(volume, nx, ny, nz, h_lo, h_step, 0.f, m, "ia_volume_gradient")) return st;

@@ -24,15 +24,16 @@
 //   place      : per output vertex the mean m and, for 'quadric', the minimiser of the summed quadric about m through the truncated
 //                pseudo-inverse (cyclic Jacobi, kSweeps fixed sweeps, double; eigenvalues <= 1e-3 of the largest are dropped), clamped
 //                to the cell.  Plain IEEE double arithmetic (+ - * / sqrt), no fast-math intrinsics.
-#include "ia_common.h"
+#include "geom_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
+using ia::cell_of; using ia::kScanBlock; using ia::on_device; using ia::wave_count; using ia::wave_min;
+
 constexpr int kBlock = 256;
-constexpr int kScanBlock = 1024;
 constexpr int kChunk = 32;
 constexpr int kBoxBlocks = 1024;
 constexpr int kSweeps = 8;
@@ -46,16 +47,6 @@ struct Cells {
     float lo[3], inv[3];
     double cell[3];
 };
-
-__device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
-    return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // ------------------------------------------------------------------ box
 
@@ -114,27 +105,8 @@ __global__ __launch_bounds__(kBlock) void key_heads_kernel(const int64_t* __rest
 
 // One workgroup: out[0 .. n) = exclusive sums of in[0 .. n), out[n] = total.  in == out is allowed.
 __global__ __launch_bounds__(kScanBlock) void scan_kernel(const int* in, int* out, int64_t n) {
-    __shared__ int s[kScanBlock];
-    const int t = threadIdx.x;
-    const int64_t per = (n + kScanBlock - 1) / kScanBlock;
-    const int64_t c0 = min((int64_t)t * per, n), c1 = min(c0 + per, n);
-    int a = 0;
-    for (int64_t c = c0; c < c1; ++c) a += in[c];
-    s[t] = a;
-    __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        const int x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    int run = s[t] - a;
-    for (int64_t c = c0; c < c1; ++c) {
-        const int v = in[c];
-        out[c] = run;
-        run += v;
-    }
-    if (t == kScanBlock - 1) out[n] = s[t];
+    const int total = ia::scan_workgroup<int>(in, out, n);
+    if (threadIdx.x == 0) out[n] = total;
 }
 
 struct ClusterArgs {
@@ -190,11 +162,6 @@ struct ClassifyArgs {
     int* pairs;                  // [3 F] or null
     int* count;                  // usable faces, surviving faces, pairs
 };
-
-__device__ __forceinline__ void wave_count(bool p, int* dst) {
-    const unsigned long long m = __ballot(p);
-    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(dst, __popcll(m));
-}
 
 __global__ __launch_bounds__(kBlock) void classify_kernel(ClassifyArgs u) {
     const int64_t f = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -512,15 +479,7 @@ __global__ __launch_bounds__(kBlock) void means_kernel(const double* __restrict_
 
 // ------------------------------------------------------------------ host side
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-unsigned blocks(int64_t n) { return (unsigned)ia::ceil_div(n < 1 ? 1 : n, kBlock); }
+unsigned blocks(int64_t n) { return ia::blocks(n, kBlock); }
 
 int make_cells(const char* what, const float* lo, const float* inv, const double* cell, const int* dims, Cells& g) {
     IA_REQUIRE(lo && inv && dims, "%s: null pointer (lo, inv_cell, dims)", what);

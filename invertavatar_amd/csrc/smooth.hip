@@ -27,33 +27,26 @@
 //
 // No floating-point atomics; every sum's order is fixed by the sorted layout, so results are bit-equal from run to run.  Plain IEEE
 // double arithmetic (+ - * / sqrt, atan2 for the corner angles), no fast-math intrinsics; the build has -ffp-contract=off.
-#include "ia_common.h"
+#include "geom_common.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
+using ia::kScanBlock; using ia::on_device; using ia::wave_count; using ia::wave_sum;
+
 constexpr int kBlock = 256;
-constexpr int kScanBlock = 1024;
 constexpr int kHeavy = 64;                           // neighbours beyond which a vertex gets a wave of its own
 constexpr int64_t kMaxCount = (int64_t)1 << 28;      // vertices and faces: 6 F entries stay below 2^31, i V + j below 2^56
 constexpr int64_t kNoKey = INT64_MAX;
-
-__device__ __forceinline__ void wave_count(bool p, int* dst) {
-    const unsigned long long m = __ballot(p);
-    if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(dst, __popcll(m));
-}
 
 __device__ __forceinline__ bool finite3(const float* __restrict__ v, int64_t i) {
     return isfinite(v[3 * i]) && isfinite(v[3 * i + 1]) && isfinite(v[3 * i + 2]);
 }
 
-struct D3 { double x, y, z; };
+using D3 = ia::Vec3<double>;                        // sub, dot ((x + y) + z), cross: geom_common.h
 __device__ __forceinline__ D3 load3(const float* __restrict__ v, int64_t i) { return {(double)v[3 * i], (double)v[3 * i + 1], (double)v[3 * i + 2]}; }
-__device__ __forceinline__ D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ double len(D3 a) { return sqrt(dot(a, a)); }
 
 // ------------------------------------------------------------------ keys
@@ -112,27 +105,8 @@ __global__ __launch_bounds__(kBlock) void heads_kernel(const int64_t* __restrict
 
 // One workgroup: out[0 .. n) = exclusive sums of in[0 .. n), out[n] = total.  in == out is allowed.
 __global__ __launch_bounds__(kScanBlock) void scan_kernel(const int* in, int* out, int64_t n) {
-    __shared__ int s[kScanBlock];
-    const int t = threadIdx.x;
-    const int64_t per = (n + kScanBlock - 1) / kScanBlock;
-    const int64_t c0 = min((int64_t)t * per, n), c1 = min(c0 + per, n);
-    int a = 0;
-    for (int64_t c = c0; c < c1; ++c) a += in[c];
-    s[t] = a;
-    __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        const int x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    int run = s[t] - a;
-    for (int64_t c = c0; c < c1; ++c) {
-        const int v = in[c];
-        out[c] = run;
-        run += v;
-    }
-    if (t == kScanBlock - 1) out[n] = s[t];
+    const int total = ia::scan_workgroup<int>(in, out, n);
+    if (threadIdx.x == 0) out[n] = total;
 }
 
 struct CsrArgs {
@@ -201,9 +175,7 @@ __global__ __launch_bounds__(kBlock) void vertices_kernel(const int* __restrict_
         if (deg > kHeavy) heavy[atomicAdd(count + 6, 1)] = (int)v;       // (rare; the order of the list changes no result)
     }
     wave_count(b, count + 4);
-    int m = deg;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
+    const int m = ia::wave_max(deg);
     if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(count + 5, m);
 }
 
@@ -309,12 +281,6 @@ __global__ __launch_bounds__(kBlock) void step_kernel(StepArgs u) {
     move_vertex(u, v, s, wsum);
 }
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);   // every lane adds the same pairs: one order, one result
-    return x;
-}
-
 __global__ __launch_bounds__(64) void step_heavy_kernel(StepArgs u) {
     const int lane = threadIdx.x;
     for (int h = blockIdx.x; h < u.n_heavy; h += gridDim.x) {
@@ -378,15 +344,7 @@ __global__ __launch_bounds__(kBlock) void normals_kernel(NormalArgs u) {
 
 // ------------------------------------------------------------------ host side
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-unsigned blocks(int64_t n) { return (unsigned)ia::ceil_div(n < 1 ? 1 : n, kBlock); }
+unsigned blocks(int64_t n) { return ia::blocks(n, kBlock); }
 
 }  // namespace
 

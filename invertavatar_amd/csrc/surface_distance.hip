@@ -30,15 +30,16 @@
 //   stats  : finite count, sum, sum of squares, max, sum |n_a . n_b|, non-finite count and counts <= t for up to 8 thresholds, in
 //            double per thread, wave and workgroup in a fixed order; a second launch adds the workgroups' slots in index order.  No
 //            floating-point atomics: bit-equal from run to run.
-#include "ia_common.h"
+#include "geom_common.h"
 
 #include <cmath>
 
 namespace {
 
+using ia::blocks; using ia::cell_of; using ia::kScanBlock; using ia::on_device; using ia::wave_max; using ia::wave_sum;
+
 constexpr int kBlock = 256;
 constexpr int kMaxCells = 64;                        // a triangle that covers more cells goes to the oversize list
-constexpr int kScanBlock = 1024;
 constexpr int kMaxAxis = 1024;                       // cells per axis
 constexpr int64_t kMaxGridCells = (int64_t)1 << 26;
 constexpr int64_t kMaxFaces = (int64_t)1 << 25;      // kMaxCells * F entries stay below 2^31
@@ -47,12 +48,7 @@ constexpr int kStatVals = 6 + kMaxThr;               // count, sum, sum sq, max,
 constexpr int kStatBlocks = 1024;
 constexpr int kStatPer = 4;
 
-struct V3 { float x, y, z; };
-
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+using V3 = ia::Vec3<float>;                         // sub, dot ((x + y) + z), cross, finite3: geom_common.h
 
 // Closest point of the segment a + t e, t in [0, 1] (ee = e . e), to the origin; kept if its squared distance is below `best`.
 __device__ __forceinline__ void seg(V3 a, V3 e, float ee, float& best, V3& q) {
@@ -96,10 +92,6 @@ struct Grid {
     float lo[3], inv[3];         // cell of x along an axis: clamp(floor((x - lo) * inv), 0, n - 1)
     int entries, n_over;
 };
-
-__device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
-    return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));     // a NaN lands in cell 0
-}
 
 __device__ __forceinline__ V3 xyz(float4 v) { return {v.x, v.y, v.z}; }
 
@@ -162,28 +154,9 @@ __global__ __launch_bounds__(kBlock) void trigrid_pass_kernel(Grid g, const floa
 }
 
 // One workgroup: counts[0 .. n) -> exclusive offsets in place, counts[n] = total.
-__global__ __launch_bounds__(kScanBlock) void trigrid_scan_kernel(int* __restrict__ counts, int n) {
-    __shared__ int s[kScanBlock];
-    const int t = threadIdx.x;
-    const int per = (n + kScanBlock - 1) / kScanBlock;
-    const int c0 = min(t * per, n), c1 = min(c0 + per, n);
-    int a = 0;
-    for (int c = c0; c < c1; ++c) a += counts[c];
-    s[t] = a;
-    __syncthreads();
-    for (int off = 1; off < kScanBlock; off <<= 1) {
-        const int x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    int run = s[t] - a;
-    for (int c = c0; c < c1; ++c) {
-        const int v = counts[c];
-        counts[c] = run;
-        run += v;
-    }
-    if (t == kScanBlock - 1) counts[n] = s[t];
+__global__ __launch_bounds__(kScanBlock) void trigrid_scan_kernel(int* counts, int n) {
+    const int total = ia::scan_workgroup<int>(counts, counts, n);
+    if (threadIdx.x == 0) counts[n] = total;
 }
 
 struct Query {
@@ -285,18 +258,6 @@ struct StatArgs {
     int blocks;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void stats_kernel(StatArgs s) {
     double acc[kStatVals];
 #pragma unroll
@@ -347,16 +308,6 @@ __global__ __launch_bounds__(64) void stats_final_kernel(const double* __restric
 }
 
 // ------------------------------------------------------------------ host side
-
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t attr;
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type != hipMemoryTypeHost && attr.type != hipMemoryTypeUnregistered;
-}
-
-unsigned blocks(int64_t n, int per) { return (unsigned)ia::ceil_div(n < 1 ? 1 : n, per); }
 
 int stat_blocks(int64_t n) {
     const int64_t b = ia::ceil_div(n < 1 ? 1 : n, (int64_t)kBlock * kStatPer);

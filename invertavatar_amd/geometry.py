@@ -61,6 +61,21 @@ def _vec3(v):
     return (float(v),) * 3 if np.isscalar(v) else tuple(float(x) for x in v)
 
 
+def _np(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def _as_out(x, like, dtype=None):
+    """A NumPy result in the container of ``like``: a CPU torch tensor for a tensor, NumPy otherwise."""
+    x = x.astype(dtype or F32)
+    return torch.from_numpy(x) if isinstance(like, torch.Tensor) else x
+
+
+def _check_volume(volume):
+    if volume.ndim != 3 or min(volume.shape) < 2:
+        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
+
+
 def lattice_axis(n, length, origin):
     """fp32 coordinates of one lattice axis: ``(origin - 0.5 * L) + i * (L / (n - 1))``, each operation rounded to fp32."""
     lo = F32(origin) - F32(0.5) * F32(length)
@@ -191,8 +206,7 @@ def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0
         from . import hipops
         verts, faces = hipops.marching_cubes(volume.float().contiguous(), float(level), org, spc)
         return verts, faces.long()
-    if volume.ndim != 3 or min(volume.shape) < 2:
-        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
+    _check_volume(volume)
     if isinstance(volume, torch.Tensor):
         verts, faces = _mc_numpy(volume.detach().cpu().numpy(), level, org, spc)
         return torch.from_numpy(verts), torch.from_numpy(faces)
@@ -346,12 +360,6 @@ def _raycast_numpy(vol, level, lo, step, ro, rd, t_min):
     return depth, normal, mask
 
 
-def _as_out(x, like, dtype=None):
-    """A NumPy result in the container of ``like``: a CPU torch tensor for a tensor, NumPy otherwise."""
-    x = x.astype(dtype or F32)
-    return torch.from_numpy(x) if isinstance(like, torch.Tensor) else x
-
-
 def raycast(volume, level, origin, spacing, rays_o, rays_d, t_min=0.0, skip=True):
     """First hit of rays [..., 3] with the surface {volume > level} of the trilinear field: {'depth' [...], 'mask' bool [...],
     'normal' [..., 3]}.  ``origin`` / ``spacing`` are the coordinates of point (0,0,0) and the lattice step per axis (the arguments of
@@ -367,8 +375,7 @@ def raycast(volume, level, origin, spacing, rays_o, rays_d, t_min=0.0, skip=True
         depth, normal, mask = hipops.raycast_volume(vol, float(level), org, spc, rays_o.float().reshape(-1, 3).contiguous(),
                                                     rays_d.float().reshape(-1, 3).contiguous(), t_min, bricks)
         return {'depth': depth.reshape(lead), 'mask': mask.reshape(lead), 'normal': normal.reshape(lead + (3,))}
-    if volume.ndim != 3 or min(volume.shape) < 2:
-        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
+    _check_volume(volume)
     depth, normal, mask = _raycast_numpy(_np(volume), level, org, spc, _np(rays_o), _np(rays_d), t_min)
     return {'depth': _as_out(depth.reshape(lead), rays_o), 'mask': _as_out(mask.reshape(lead), rays_o, bool),
             'normal': _as_out(normal.reshape(lead + (3,)), rays_o)}
@@ -469,11 +476,6 @@ def _component_stats_numpy(labels, k):
         np.maximum.at(hi, c, x)
         stats[:, 5 + col] = hi
     return stats
-
-
-def _check_volume(volume):
-    if volume.ndim != 3 or min(volume.shape) < 2:
-        raise ValueError(f'volume must be [nx,ny,nz] with every dimension >= 2, got {tuple(volume.shape)}')
 
 
 def components(volume, level, connectivity=26):
@@ -1525,10 +1527,6 @@ def vertex_colors(planes, decoder, verts, box_warp):
 
 
 # ------------------------------------------------------------------ PLY
-
-def _np(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-
 
 def write_ply(path, verts, faces, colors=None, normals=None):
     """Binary little-endian PLY: float x, y, z (+ float nx, ny, nz) (+ uchar red, green, blue) per vertex, int32 index triples per face."""

@@ -1291,6 +1291,75 @@ def se_gate(v, shortcut, w1, w2):
     return out
 
 
+# ------------------------------------------------------------------ shared by the geometry wrappers below
+
+def _f3(values):
+    return (ctypes.c_float * 3)(*[float(v) for v in values])
+
+
+def _i3(values):
+    return (ctypes.c_int * 3)(*[int(v) for v in values])
+
+
+def _d3(values):
+    return (ctypes.c_double * 3)(*[float(v) for v in values])
+
+
+def _i32c(t, what):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise RuntimeError(f'{what} must be a contiguous int32 device tensor')
+    return t
+
+
+def _volume_checked(volume):
+    _f32c(volume, 'volume')
+    if volume.dim() != 3:
+        raise RuntimeError(f'volume must be [nx,ny,nz], got {tuple(volume.shape)}')
+    return tuple(int(n) for n in volume.shape)
+
+
+def _mesh_checked(verts, faces):
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise RuntimeError(f'a mesh is verts [V,3] and faces [F,3] on one device, got {tuple(verts.shape)} and {tuple(faces.shape)}')
+    return verts.shape[0], faces.shape[0]
+
+
+def _scratch(fn_name, *args, dtype, device, extra=0):
+    """The scratch buffer that the library's ``fn_name(*args, &bytes)`` asks for, rounded up to whole elements of ``dtype`` (plus
+    ``extra`` elements) -> (tensor, its size in bytes)."""
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(getattr(_lib.load(), fn_name)(*args, ctypes.byref(nbytes)), fn_name)
+    t = torch.empty(-(-nbytes.value // dtype.itemsize) + extra, dtype=dtype, device=device)
+    return t, t.numel() * dtype.itemsize
+
+
+SIMPLIFY_TIMES = None        # a dict collects seconds per phase (each phase then ends in a device synchronise): tools/bench_simplify.py
+SMOOTH_TIMES = None          # the same for the smoothing wrappers: tools/bench_smooth.py
+
+
+class _Phase:
+    """Adds the seconds of its block to entry ``name`` of the module-level dict named ``times``, while that is not None."""
+    def __init__(self, name, dev, times):
+        self.name, self.dev, self.times = name, dev, times
+
+    def __enter__(self):
+        if globals()[self.times] is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            self.t0 = time.perf_counter()
+        return self
+
+    def __exit__(self, *exc):
+        acc = globals()[self.times]
+        if acc is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            acc[self.name] = acc.get(self.name, 0.0) + time.perf_counter() - self.t0
+        return False
+
+
 # ------------------------------------------------------------------ avatar geometry (csrc/geometry.hip)
 
 def _decoder_checked(w0, b0, w1, b1):
@@ -1327,10 +1396,6 @@ def query_planes(planes_cl, points, w0, b0, w1, b1, lr_multiplier=1.0, box_warp=
     return sigma, col
 
 
-def _f3(v):
-    return (ctypes.c_float * 3)(*[float(x) for x in v])
-
-
 def density_grid(planes_cl, w0, b0, w1, b1, res, cube_length, origin, lr_multiplier=1.0, box_warp=1.0, flip_z=False):
     """Density on the nx x ny x nz lattice of `cube_length` / `origin` (per-axis triples): [B,nx,ny,nz] (see ia_density_grid)."""
     b, ph, pw = _planes_checked(planes_cl)
@@ -1350,38 +1415,25 @@ def density_grid(planes_cl, w0, b0, w1, b1, res, cube_length, origin, lr_multipl
 def marching_cubes(volume, level, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
     """Mesh of {volume > level} (see ia_mc_count / ia_mc_emit): volume [nx,ny,nz] -> (verts float32 [V,3], faces int32 [F,3]).
     One host synchronisation (the two totals)."""
-    _f32c(volume, 'volume')
-    if volume.dim() != 3:
-        raise RuntimeError(f'volume must be [nx,ny,nz], got {tuple(volume.shape)}')
-    nx, ny, nz = volume.shape
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_mc_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_mc_scratch_bytes')
-    dev = volume.device
-    scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    nx, ny, nz = _volume_checked(volume)
+    lib, dev = _lib.load(), volume.device
+    scratch, nbytes = _scratch('ia_mc_scratch_bytes', nx, ny, nz, dtype=torch.uint8, device=dev)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
     stream = _lib.stream_ptr(dev)
     with torch.cuda.device(dev):
-        with _Timed('mc_count', 0.0, 4.0 * volume.numel() + nbytes.value, f'{nx}x{ny}x{nz}'):
-            st = lib.ia_mc_count(_p(volume), nx, ny, nz, float(level), _p(scratch), nbytes.value, _p(totals), stream)
+        with _Timed('mc_count', 0.0, 4.0 * volume.numel() + nbytes, f'{nx}x{ny}x{nz}'):
+            st = lib.ia_mc_count(_p(volume), nx, ny, nz, float(level), _p(scratch), nbytes, _p(totals), stream)
         _lib.check(st, 'ia_mc_count')
         n_verts, n_faces = (int(v) for v in totals.cpu())
         if n_verts < 0 or n_faces < 0:
             raise RuntimeError(f'marching_cubes: more than 2^31 - 1 vertices or triangles in a {nx}x{ny}x{nz} volume')
         verts = torch.empty(n_verts, 3, device=dev)
         faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
-        with _Timed('mc_emit', 0.0, 4.0 * volume.numel() + nbytes.value + 12.0 * (n_verts + n_faces), f'{nx}x{ny}x{nz}'):
-            st = lib.ia_mc_emit(_p(volume), nx, ny, nz, float(level), _f3(origin), _f3(spacing), _p(scratch), nbytes.value,
+        with _Timed('mc_emit', 0.0, 4.0 * volume.numel() + nbytes + 12.0 * (n_verts + n_faces), f'{nx}x{ny}x{nz}'):
+            st = lib.ia_mc_emit(_p(volume), nx, ny, nz, float(level), _f3(origin), _f3(spacing), _p(scratch), nbytes,
                                 _p(verts), n_verts, _p(faces), n_faces, stream)
         _lib.check(st, 'ia_mc_emit')
     return verts, faces
-
-
-def _volume_checked(volume):
-    _f32c(volume, 'volume')
-    if volume.dim() != 3:
-        raise RuntimeError(f'volume must be [nx,ny,nz], got {tuple(volume.shape)}')
-    return tuple(int(n) for n in volume.shape)
 
 
 def _rays_checked(t, what, device):
@@ -1394,14 +1446,11 @@ def _rays_checked(t, what, device):
 def volume_bricks(volume):
     """{min, max} per brick of 8^3 cells (see ia_volume_bricks): volume [nx,ny,nz] -> [bx,by,bz,2] float32."""
     nx, ny, nz = _volume_checked(volume)
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_raycast_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_raycast_scratch_bytes')
     dev = volume.device
-    bricks = torch.empty((nx + 6) // 8, (ny + 6) // 8, (nz + 6) // 8, 2, device=dev)
-    assert bricks.numel() * 4 == nbytes.value
+    bricks, nbytes = _scratch('ia_raycast_scratch_bytes', nx, ny, nz, dtype=torch.float32, device=dev)
+    bricks = bricks.view((nx + 6) // 8, (ny + 6) // 8, (nz + 6) // 8, 2)
     with torch.cuda.device(dev), _Timed('volume_bricks', 0.0, 4.0 * volume.numel(), f'{nx}x{ny}x{nz}'):
-        st = lib.ia_volume_bricks(_p(volume), nx, ny, nz, _p(bricks), nbytes.value, _lib.stream_ptr(dev))
+        st = _lib.load().ia_volume_bricks(_p(volume), nx, ny, nz, _p(bricks), nbytes, _lib.stream_ptr(dev))
     _lib.check(st, 'ia_volume_bricks')
     return bricks
 
@@ -1443,27 +1492,18 @@ def volume_gradient(volume, lo, step, points):
 
 # ------------------------------------------------------------------ connected components (csrc/components.hip)
 
-def _i32c(t, what):
-    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
-        raise RuntimeError(f'{what} must be a contiguous int32 device tensor')
-    return t
-
-
 def volume_components(volume, level, connectivity=26):
     """Components of {volume > level} (see ia_volume_components): volume [nx,ny,nz] -> (labels int32 [nx,ny,nz], K).  One host
     synchronisation (K)."""
     nx, ny, nz = _volume_checked(volume)
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_components_scratch_bytes(nx, ny, nz, ctypes.byref(nbytes)), 'ia_components_scratch_bytes')
-    dev = volume.device
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=dev)
+    lib, dev = _lib.load(), volume.device
+    scratch, nbytes = _scratch('ia_components_scratch_bytes', nx, ny, nz, dtype=torch.int32, device=dev)
     labels = torch.empty(nx, ny, nz, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         with _Timed('volume_components', 0.0, 4.0 * volume.numel() * 8, f'{nx}x{ny}x{nz} c{connectivity}'):
             st = lib.ia_volume_components(_p(volume), nx, ny, nz, float(level), int(connectivity), _p(labels), _p(scratch),
-                                          scratch.numel() * 4, _p(count), _lib.stream_ptr(dev))
+                                          nbytes, _p(count), _lib.stream_ptr(dev))
         _lib.check(st, 'ia_volume_components')
         return labels, int(count.cpu())
 
@@ -1512,16 +1552,13 @@ def mesh_components(faces, n_verts):
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise RuntimeError(f'faces must be [F,3], got {tuple(faces.shape)}')
     v, f = int(n_verts), faces.shape[0]
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_mesh_components_scratch_bytes(v, ctypes.byref(nbytes)), 'ia_mesh_components_scratch_bytes')
-    dev = faces.device
-    scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.int32, device=dev)
+    lib, dev = _lib.load(), faces.device
+    scratch, nbytes = _scratch('ia_mesh_components_scratch_bytes', v, dtype=torch.int32, device=dev)
     labels = torch.empty(v, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         with _Timed('mesh_components', 0.0, 12.0 * f + 32.0 * v, f'F={f} V={v}'):
-            st = lib.ia_mesh_components(_p(faces), f, v, _p(labels), _p(scratch), scratch.numel() * 4, _p(count), _lib.stream_ptr(dev))
+            st = lib.ia_mesh_components(_p(faces), f, v, _p(labels), _p(scratch), nbytes, _p(count), _lib.stream_ptr(dev))
         _lib.check(st, 'ia_mesh_components')
         return labels, int(count.cpu())
 
@@ -1553,16 +1590,13 @@ def image_metrics(a, b, data_range, levels=5):
         layout, (n, h, w, c) = IMAGE_LAYOUT_U8_NHWC, a.shape
     else:
         layout, (n, c, h, w) = IMAGE_LAYOUT_F32_NCHW, a.shape
-    lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_image_metrics_scratch_bytes(n, c, h, w, int(levels), ctypes.byref(nbytes)), 'ia_image_metrics_scratch_bytes')
-    dev = a.device
-    scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    lib, dev = _lib.load(), a.device
+    scratch, nbytes = _scratch('ia_image_metrics_scratch_bytes', n, c, h, w, int(levels), dtype=torch.float64, device=dev)
     out = torch.empty(n, 5 + 2 * int(levels), device=dev)
     pixels = float(a.numel())
     with torch.cuda.device(dev), _Timed('image_metrics', 400.0 * pixels, 2.0 * a.element_size() * pixels * (1.0 + 1.0 / 3.0 if levels > 1 else 1.0),
                                         f'{n}x{c}x{h}x{w} levels={levels}'):
-        st = lib.ia_image_metrics(_p(a), _p(b), layout, n, c, h, w, float(data_range), int(levels), _p(scratch), scratch.numel() * 8,
+        st = lib.ia_image_metrics(_p(a), _p(b), layout, n, c, h, w, float(data_range), int(levels), _p(scratch), nbytes,
                                   _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_image_metrics')
     return out
@@ -1570,20 +1604,9 @@ def image_metrics(a, b, data_range, levels=5):
 
 # ------------------------------------------------------------------ surface distance (csrc/surface_distance.hip)
 
-def _f3(values):
-    return (ctypes.c_float * 3)(*[float(v) for v in values])
-
-
-def _i3(values):
-    return (ctypes.c_int * 3)(*[int(v) for v in values])
-
-
 def tri_pack(verts, faces):
     """Packed triangles (see ia_tri_pack): verts float32 [V,3], faces int32 [F,3] -> float32 [F,3,4]."""
-    _f32c(verts, 'verts')
-    _i32c(faces, 'faces')
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
-        raise RuntimeError(f'verts [V,3] and faces [F,3] on one device, got {tuple(verts.shape)} and {tuple(faces.shape)}')
+    _mesh_checked(verts, faces)
     dev = verts.device
     tris = torch.empty(faces.shape[0], 3, 4, device=dev)
     with torch.cuda.device(dev), _Timed('tri_pack', 0.0, 84.0 * faces.shape[0], f'F={faces.shape[0]}'):
@@ -1667,45 +1690,17 @@ def distance_stats(dist, thresholds=(), face=None, normals_a=None, normals_b=Non
         if face.numel() != n or tuple(normals_a.shape) != (n, 3) or normals_b.dim() != 2 or normals_b.shape[1] != 3:
             raise RuntimeError('face [N], normals_a [N,3] and normals_b [Fb,3] do not match the distances')
     lib = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_distance_stats_scratch_bytes(n, ctypes.byref(nbytes)), 'ia_distance_stats_scratch_bytes')
-    scratch = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    scratch, nbytes = _scratch('ia_distance_stats_scratch_bytes', n, dtype=torch.float64, device=dev)
     out = torch.empty(14, dtype=torch.float64, device=dev)
     thr = (ctypes.c_float * max(len(thresholds), 1))(*thresholds)
     with torch.cuda.device(dev), _Timed('distance_stats', 0.0, (32.0 if with_normals else 4.0) * n, f'N={n}'):
         st = lib.ia_distance_stats(_p(dist), n, thr, len(thresholds), _p(face), _p(normals_a), _p(normals_b),
-                                   normals_b.shape[0] if with_normals else 0, _p(scratch), scratch.numel() * 8, _p(out), _lib.stream_ptr(dev))
+                                   normals_b.shape[0] if with_normals else 0, _p(scratch), nbytes, _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_distance_stats')
     return out
 
 
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
-
-SIMPLIFY_TIMES = None        # a dict collects seconds per phase (each phase then ends in a device synchronise): tools/bench_simplify.py
-
-
-class _Phase:
-    def __init__(self, name, dev):
-        self.name, self.dev = name, dev
-
-    def __enter__(self):
-        if SIMPLIFY_TIMES is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            self.t0 = time.perf_counter()
-        return self
-
-    def __exit__(self, *exc):
-        if SIMPLIFY_TIMES is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            SIMPLIFY_TIMES[self.name] = SIMPLIFY_TIMES.get(self.name, 0.0) + time.perf_counter() - self.t0
-        return False
-
-
-def _d3(values):
-    return (ctypes.c_double * 3)(*[float(v) for v in values])
-
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):
     """Grid of the clustering (host arithmetic, see ia_simplify_plan): -> (dims, inv_cell, cell)."""
@@ -1722,7 +1717,7 @@ def simplify_box(verts):
     dev = verts.device
     scratch = torch.empty(6 * 1024, device=dev)
     box = torch.empty(6, device=dev)
-    with torch.cuda.device(dev), _Phase('keys', dev):
+    with torch.cuda.device(dev), _Phase('keys', dev, 'SIMPLIFY_TIMES'):
         st = _lib.load().ia_simplify_box(_p(verts), verts.shape[0], _p(scratch), scratch.numel() * 4, _p(box), _lib.stream_ptr(dev))
         _lib.check(st, 'ia_simplify_box')
         b = box.cpu().tolist()
@@ -1736,7 +1731,7 @@ def simplify_keys(verts, lo, inv_cell, dims):
     _f32c(verts, 'verts')
     dev = verts.device
     keys = torch.empty(verts.shape[0], dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev), _Phase('keys', dev):
+    with torch.cuda.device(dev), _Phase('keys', dev, 'SIMPLIFY_TIMES'):
         st = _lib.load().ia_simplify_keys(_p(verts), verts.shape[0], _f3(lo), _f3(inv_cell), _i3(dims), _p(keys), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_simplify_keys')
     return keys
@@ -1756,9 +1751,9 @@ def simplify_topology(keys, faces, full=True, pairs=False):
     s = {'V': v, 'F': f}
     with torch.cuda.device(dev):
         stream = _lib.stream_ptr(dev)
-        with _Phase('sorts', dev):
+        with _Phase('sorts', dev, 'SIMPLIFY_TIMES'):
             skeys, order = torch.sort(keys, stable=True)
-        with _Phase('keys', dev):
+        with _Phase('keys', dev, 'SIMPLIFY_TIMES'):
             vcluster, vseg = torch.empty(v, **i32), torch.empty(v, **i32)
             cstart, ckey = torch.empty(v + 1, **i32), torch.empty(max(v, 1), dtype=torch.int64, device=dev)
             scratch, count = torch.empty(v + 1, **i32), torch.empty(2, **i32)
@@ -1766,18 +1761,18 @@ def simplify_topology(keys, faces, full=True, pairs=False):
                                           scratch.numel() * 4, _p(count), stream)
             _lib.check(st, 'ia_simplify_clusters')
             k, n_valid = (int(x) for x in count.cpu())
-        with _Phase('faces', dev):
+        with _Phase('faces', dev, 'SIMPLIFY_TIMES'):
             tri, key = torch.empty(max(f, 1), 3, **i32), torch.empty(max(f, 1), dtype=torch.int64, device=dev)
             ref = torch.empty(max(k, 1), **i32) if full else None
             pr = torch.empty(max(3 * f, 1), **i32) if pairs else None
             fcount = torch.empty(3, **i32)
             st = lib.ia_simplify_classify(_p(faces), f, v, _p(vcluster), k, _p(tri), _p(key), _p(ref), _p(pr), _p(fcount), stream)
             _lib.check(st, 'ia_simplify_classify')
-        with _Phase('sorts', dev):
+        with _Phase('sorts', dev, 'SIMPLIFY_TIMES'):
             perm = torch.sort(key[:f], stable=True)[1]
             if float(k) ** 3 >= 9.0e18:                                   # the key holds (b, c) only: a second, stable sort by a
                 perm = perm[torch.sort(tri[:f, 0][perm], stable=True)[1]].contiguous()
-        with _Phase('faces', dev):
+        with _Phase('faces', dev, 'SIMPLIFY_TIMES'):
             fpos = torch.empty(f + 1, **i32)
             _lib.check(lib.ia_simplify_face_heads(_p(tri), _p(perm), f, _p(fpos), stream), 'ia_simplify_face_heads')
             outidx = None
@@ -1800,7 +1795,7 @@ def simplify_outputs(s):
     ocl = torch.empty(nv, dtype=torch.int32, device=dev)
     csize = torch.empty(nv, dtype=torch.int64, device=dev)
     faces_out = torch.empty(nf, 3, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev), _Phase('faces', dev):
+    with torch.cuda.device(dev), _Phase('faces', dev, 'SIMPLIFY_TIMES'):
         stream = _lib.stream_ptr(dev)
         st = lib.ia_simplify_outputs(_p(s['vcluster']), v, _p(s['ref']), _p(s['outidx']), _p(s['cstart']), k, _p(vertex_map), _p(ocl),
                                      _p(csize), nv, stream)
@@ -1808,12 +1803,6 @@ def simplify_outputs(s):
         st = lib.ia_simplify_faces(_p(s['tri']), _p(s['perm']), _p(s['fpos']), f, _p(s['outidx']), k, _p(faces_out), nf, stream)
         _lib.check(st, 'ia_simplify_faces')
     return faces_out, vertex_map, csize, ocl
-
-
-def _acc_scratch(lib, n, width, dev):
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.ia_simplify_accumulate_scratch_bytes(n, width, ctypes.byref(nbytes)), 'ia_simplify_accumulate_scratch_bytes')
-    return torch.empty((nbytes.value + 7) // 8 + 1, dtype=torch.float64, device=dev)
 
 
 def simplify_vertex_sums(s, cols):
@@ -1826,13 +1815,13 @@ def simplify_vertex_sums(s, cols):
     out = torch.zeros(k, c, dtype=torch.float64, device=dev)
     if k == 0 or c == 0:
         return out
-    scratch = _acc_scratch(lib, s['n_valid'], 4, dev)
-    with torch.cuda.device(dev), _Phase('accumulate', dev):
+    scratch, nbytes = _scratch('ia_simplify_accumulate_scratch_bytes', s['n_valid'], 4, dtype=torch.float64, device=dev, extra=1)
+    with torch.cuda.device(dev), _Phase('accumulate', dev, 'SIMPLIFY_TIMES'):
         for c0 in range(0, c, 4):
             nc = min(4, c - c0)
             sums = torch.empty(k, 4, dtype=torch.float64, device=dev)
             st = lib.ia_simplify_accumulate_verts(_p(cols), c, c0, nc, _p(s['order']), _p(s['vseg']), s['n_valid'], s['V'], k, _p(sums),
-                                                  _p(scratch), scratch.numel() * 8, _lib.stream_ptr(dev))
+                                                  _p(scratch), nbytes, _lib.stream_ptr(dev))
             _lib.check(st, 'ia_simplify_accumulate_verts')
             out[:, c0:c0 + nc] = sums[:, :nc]
     return out
@@ -1848,12 +1837,12 @@ def simplify_quadric_sums(s, verts, lo, inv_cell, cell, dims):
     if k == 0:
         return sums
     with torch.cuda.device(dev):
-        with _Phase('sorts', dev):
+        with _Phase('sorts', dev, 'SIMPLIFY_TIMES'):
             spairs, porder = torch.sort(s['pairs'][:3 * f], stable=True)
-        scratch = _acc_scratch(lib, n, 9, dev)
-        with _Phase('accumulate', dev):
+        scratch, nbytes = _scratch('ia_simplify_accumulate_scratch_bytes', n, 9, dtype=torch.float64, device=dev, extra=1)
+        with _Phase('accumulate', dev, 'SIMPLIFY_TIMES'):
             st = lib.ia_simplify_accumulate_faces(_p(verts), s['V'], _p(s['faces']), f, _p(porder), _p(spairs), n, _p(s['ckey']), k, _f3(lo),
-                                                  _f3(inv_cell), _d3(cell), _i3(dims), _p(sums), _p(scratch), scratch.numel() * 8,
+                                                  _f3(inv_cell), _d3(cell), _i3(dims), _p(sums), _p(scratch), nbytes,
                                                   _lib.stream_ptr(dev))
         _lib.check(st, 'ia_simplify_accumulate_faces')
     return sums
@@ -1865,7 +1854,7 @@ def simplify_place(s, ocl, vsum, qsum, lo, inv_cell, cell, dims):
     nv = ocl.numel()
     out = torch.empty(nv, 3, device=dev)
     vs = vsum if vsum.shape[1] == 4 else torch.nn.functional.pad(vsum, (0, 4 - vsum.shape[1]))
-    with torch.cuda.device(dev), _Phase('place', dev):
+    with torch.cuda.device(dev), _Phase('place', dev, 'SIMPLIFY_TIMES'):
         st = lib.ia_simplify_place(_p(vs.contiguous()), _p(qsum), _p(ocl), _p(s['cstart']), _p(s['ckey']), s['K'], nv, _f3(lo), _f3(inv_cell),
                                    _d3(cell), _i3(dims), _p(out), nv, _lib.stream_ptr(dev))
     _lib.check(st, 'ia_simplify_place')
@@ -1877,7 +1866,7 @@ def simplify_means(s, ocl, sums):
     lib, dev = _lib.load(), ocl.device
     nv, c = ocl.numel(), sums.shape[1]
     out = torch.empty(nv, c, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev), _Phase('place', dev):
+    with torch.cuda.device(dev), _Phase('place', dev, 'SIMPLIFY_TIMES'):
         for c0 in range(0, c, 4):
             nc = min(4, c - c0)
             block = torch.zeros(max(s['K'], 1), 4, dtype=torch.float64, device=dev)
@@ -1889,52 +1878,27 @@ def simplify_means(s, ocl, sums):
 
 # ------------------------------------------------------------------ mesh smoothing and mesh normals (csrc/smooth.hip)
 
-SMOOTH_TIMES = None          # a dict collects seconds per phase (each phase then ends in a device synchronise): tools/bench_smooth.py
-
-
-class _SmoothPhase(_Phase):
-    def __enter__(self):
-        if SMOOTH_TIMES is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            self.t0 = time.perf_counter()
-        return self
-
-    def __exit__(self, *exc):
-        if SMOOTH_TIMES is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            SMOOTH_TIMES[self.name] = SMOOTH_TIMES.get(self.name, 0.0) + time.perf_counter() - self.t0
-        return False
-
-
 def mesh_adjacency(verts, faces):
     """The neighbourhood structure of a mesh (verts float32 [V,3], faces int32 [F,3]) as a dict of device arrays: 'offsets',
     'neighbors', 'edge_faces', 'boundary', 'face_offsets', 'face_ids' (see geometry.MeshAdjacency), the host dict 'info', the flag
     'out_of_range' and what ``mesh_cotangent`` and ``smooth_steps`` need (ia_mesh_edge_keys, _edge_heads, _csr; the two key sorts are
     torch.sort).  Two host synchronisations."""
-    _f32c(verts, 'verts')
-    _i32c(faces, 'faces')
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
-        raise RuntimeError('a mesh is verts [V,3] and faces [F,3] on one device')
+    v, f = _mesh_checked(verts, faces)
     lib, dev = _lib.load(), verts.device
-    v, f = verts.shape[0], faces.shape[0]
     i32 = dict(dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         stream = _lib.stream_ptr(dev)
         count = torch.empty(8, **i32)
-        with _SmoothPhase('keys', dev):
+        with _Phase('keys', dev, 'SMOOTH_TIMES'):
             ekeys, vkeys = torch.empty(6 * f, dtype=torch.int64, device=dev), torch.empty(3 * f, dtype=torch.int64, device=dev)
             _lib.check(lib.ia_mesh_edge_keys(_p(verts), v, _p(faces), f, _p(ekeys), _p(vkeys), _p(count), stream), 'ia_mesh_edge_keys')
-        with _SmoothPhase('sorts', dev):
+        with _Phase('sorts', dev, 'SMOOTH_TIMES'):
             skeys, order = torch.sort(ekeys, stable=True)
             svkeys, vorder = torch.sort(vkeys, stable=True)
             del ekeys, vkeys
-        with _SmoothPhase('csr', dev):
-            nbytes = ctypes.c_size_t(0)
-            _lib.check(lib.ia_mesh_edge_heads_scratch_bytes(f, ctypes.byref(nbytes)), 'ia_mesh_edge_heads_scratch_bytes')
-            scratch = torch.empty(nbytes.value // 4, **i32)
-            _lib.check(lib.ia_mesh_edge_heads(_p(skeys), f, _p(scratch), nbytes.value, _p(count), stream), 'ia_mesh_edge_heads')
+        with _Phase('csr', dev, 'SMOOTH_TIMES'):
+            scratch, nbytes = _scratch('ia_mesh_edge_heads_scratch_bytes', f, **i32)
+            _lib.check(lib.ia_mesh_edge_heads(_p(skeys), f, _p(scratch), nbytes, _p(count), stream), 'ia_mesh_edge_heads')
             head = count.cpu().tolist()
             usable, oob, e = head[0], bool(head[1]), head[7]
             s = {'V': v, 'F': f, 'E': e, 'out_of_range': oob, 'order': order}
@@ -1962,7 +1926,7 @@ def mesh_cotangent(s, verts, faces):
     _i32c(faces, 'faces')
     dev = verts.device
     w = torch.empty(s['E'], device=dev)
-    with torch.cuda.device(dev), _SmoothPhase('cotangent', dev):
+    with torch.cuda.device(dev), _Phase('cotangent', dev, 'SMOOTH_TIMES'):
         st = _lib.load().ia_mesh_cotangent(_p(verts), s['V'], _p(faces), s['F'], _p(s['order']), _p(s['slot_keys']), _p(s['run_start']),
                                            _p(s['edge_faces']), s['E'], _p(w), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_mesh_cotangent')
@@ -1995,7 +1959,7 @@ def smooth_steps(s, verts, weights, pinned, factors):
     if n == 0 or s['V'] == 0:
         return a
     fac = (ctypes.c_double * n)(*[float(x) for x in factors])
-    with torch.cuda.device(dev), _SmoothPhase('steps', dev):
+    with torch.cuda.device(dev), _Phase('steps', dev, 'SMOOTH_TIMES'):
         st = _lib.load().ia_smooth_steps(_p(a), _p(b), s['V'], _p(s['offsets']), _p(s['neighbors']), _p(weights), _p(pinned), _p(s['heavy']),
                                          s['n_heavy'], fac, n, _lib.stream_ptr(dev))
     _lib.check(st, 'ia_smooth_steps')
@@ -2008,7 +1972,7 @@ def mesh_normals(s, verts, faces, angle=False):
     _i32c(faces, 'faces')
     dev = verts.device
     out = torch.empty(s['V'], 3, device=dev)
-    with torch.cuda.device(dev), _SmoothPhase('normals', dev):
+    with torch.cuda.device(dev), _Phase('normals', dev, 'SMOOTH_TIMES'):
         st = _lib.load().ia_mesh_normals(_p(verts), s['V'], _p(faces), s['F'], _p(s['face_offsets']), _p(s['face_ids']), int(bool(angle)),
                                          _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_mesh_normals')

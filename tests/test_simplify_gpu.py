@@ -214,3 +214,19 @@ def test_cli_writes_a_readable_simplified_ply(tmp_path):
     meta = json.load(open(os.path.join(tmp_path, ply[0][:-4] + '_geometry.json')))
     chk = meta['simplify']['check']
     assert chk['simplified_to_full'] <= chk['cell_diagonal'] * (1 + 1e-5) + 1e-5
+
+
+def test_scan_sizes():
+    """The one-workgroup exclusive scan that every compacted count goes through (scan_workgroup in csrc/geom_common.h), called
+    directly as ia_simplify_refs: empty input, fewer items than the 1024 threads, one item per thread and one over, a ragged last
+    slice and several items per thread.  Exact against an int64 cumsum; nothing is written past out[K]."""
+    from invertavatar_amd import _lib
+    lib = _lib.load()
+    for k in (0, 1, 2, 1023, 1024, 1025, 2047, 2049, 7171, 100003):
+        for ref in (np.random.RandomState(k).randint(0, 2, size=k).astype(np.int32), np.ones(k, dtype=np.int32)):
+            tref, = dev(ref)
+            out = torch.full((k + 2,), -7, dtype=torch.int32, device=DEV)
+            _lib.check(lib.ia_simplify_refs(tref.data_ptr(), k, out.data_ptr(), _lib.stream_ptr(out.device)), 'ia_simplify_refs')
+            got = to_np(out).astype(np.int64)
+            assert np.array_equal(got[:k + 1], np.concatenate([[0], np.cumsum(ref, dtype=np.int64)])), k
+            assert got[k + 1] == -7, k

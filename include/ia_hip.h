@@ -1076,6 +1076,32 @@ int ia_smooth_steps(float* verts_a, float* verts_b, int64_t V, const int* offset
 int ia_mesh_normals(const float* verts, int64_t V, const int* faces, int64_t F, const int* face_offsets, const int* face_ids, int angle,
                     float* normals, void* stream);
 
+/* Z-buffer rasteriser for indexed meshes (csrc/mesh_raster.hip; definition: geometry.rasterize_mesh and its NumPy restatement;
+ * DESIGN.md 4.18).  verts float32 [V,3], faces int32 [F,3], cams float32 [N,25] on the device (cam2world 4x4, K 3x3 normalised; rows 0
+ * and 1 of K are scaled by W and H), V, F <= 2^28, N <= 65535, H, W <= 16384, N F, N V and N H W below 2^31.  Pixel centres are at
+ * integer coordinates (column i, row j of RaySampler_zxc).  All launches go to `stream`.
+ *
+ * ia_mesh_project: proj = N V records of 16 bytes {int32 U, V (screen coordinates in 1/256 pixel), float z (camera depth), int32
+ * usable}; a vertex is unusable if a value is not finite, z <= near, or |u| or |v| >= 2^20 pixels.  Reads the N camera labels back once
+ * before its launch: a K whose last row is not [0, 0, 1] is IA_ERR_INVALID_ARG.
+ * ia_mesh_raster: vis uint64 [N,H,W] = per pixel the least key float_bits(z) << 32 | face over the triangles that cover its centre
+ * (integer edge functions, top-left rule; all ones where none does); culled int32 [N] = triangles with an unusable vertex.  Zero-area
+ * triangles are skipped, nothing is clipped at the near plane.  cull_back: draw only triangles that face the camera (negative screen
+ * area).  A triangle whose viewport-clamped bounding box holds more than oversize_pixels pixels is drawn by a wave of its own; both
+ * paths give the same buffer.  scratch: ia_mesh_raster_scratch_bytes(N, F) bytes (not needed when oversize_pixels >= H W).
+ * ia_mesh_resolve: per pixel mask uint8, face int32 (-1 on a miss), bary float32 [3] (perspective-correct), depth (ray parameter of the
+ * pixel's unit ray, 0 on a miss), normal float32 [3] (unit normal of the winding, or with normals float32 [V,3] their normalised
+ * barycentric mix; 0 on a miss) and, with attributes float32 [V,C], C <= 8, their barycentric mix attr_out float32 [N,H,W,C].
+ * cull_back as given to ia_mesh_raster.
+ */
+int ia_mesh_project(const float* verts, int64_t V, const float* cams, int N, int H, int W, float near, void* proj, void* stream);
+int ia_mesh_raster_scratch_bytes(int N, int64_t F, size_t* h_bytes);
+int ia_mesh_raster(const void* proj, int64_t V, const int* faces, int64_t F, int N, int H, int W, int cull_back, int64_t oversize_pixels,
+                   unsigned long long* vis, int* culled, void* scratch, size_t scratch_bytes, void* stream);
+int ia_mesh_resolve(const unsigned long long* vis, const void* proj, const float* verts, int64_t V, const int* faces, int64_t F,
+                    const float* cams, int N, int H, int W, int cull_back, const float* normals, const float* attributes, int C,
+                    unsigned char* mask, int* face, float* bary, float* depth, float* normal, float* attr_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,12 @@ _SIGNATURES = {
     'ia_smooth_steps': [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_double),
                         c_int, c_void_p],
     'ia_mesh_normals': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    'ia_mesh_project': [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
+    'ia_mesh_raster_scratch_bytes': [c_int, c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_mesh_raster': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                       ctypes.c_size_t, c_void_p],
+    'ia_mesh_resolve': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -18,7 +18,11 @@ Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geo
 Taubin pairs (``geometry.smooth_mesh``, after ``--keep`` and ``--simplify``; ``--smooth-lambda``, ``--smooth-mu`` (``none``: plain Laplacian
 steps) and ``--smooth-weights`` set its arguments; normals then come from the mesh) and prints the boundary and non-manifold edge counts;
 ``--smooth-check`` prints the signed volume before and after and both directed Hausdorff distances between the smoothed and the
-unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  Runs on the device when there is one."""
+unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  ``--mesh-views N`` renders the FINAL mesh (after ``--keep``,
+``--simplify`` and ``--smooth``) from the same orbit through ``geometry.rasterize_mesh`` and writes the shaded views as
+``seed%04d_meshview%02d.png``, the coloured ones as ``seed%04d_meshrgb%02d.png`` (unless ``--no-colors``) and, with ``--compare
+--error-ply``, the error-coloured mesh as ``seed%04d_errorview%02d.png``; ``--save-depth`` adds ``seed%04d_meshdepth.npy``; a line per
+seed reports the surface pixels and the culled triangles (``--views`` keeps rendering the volume).  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -85,6 +89,7 @@ def main(argv=None):
     ap.add_argument('--no-colors', action='store_true')
     ap.add_argument('--normals', action='store_true', help='write vertex normals into the PLY')
     ap.add_argument('--views', type=int, default=0, help='also render N shaded views of the surface (yaw orbit) as PNGs')
+    ap.add_argument('--mesh-views', type=int, default=0, help='also render N views of the final mesh (rasterised; same orbit) as PNGs')
     ap.add_argument('--render-res', type=int, default=512, help='pixels per side of the rendered views')
     ap.add_argument('--save-depth', action='store_true', help='with --views: also write the depth maps as .npy')
     ap.add_argument('--keep', type=parse_keep, default=None, help="'largest' or N: keep only the N largest connected components of the shape")
@@ -187,6 +192,28 @@ def main(argv=None):
                 np.save(os.path.join(args.outdir, f'seed{seed:04d}_depth.npy'), views['depth'][0, :, 0].cpu().numpy())
             out['views'] = views
             print(f'seed {seed}: {args.views} views at {args.render_res}^2, {int(views["mask"].sum())} surface pixels')
+        if args.mesh_views > 0:
+            from PIL import Image
+            cams = orbit_cameras(G, args.mesh_views, device=args.device)
+            to8 = lambda x: (x.clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
+            views = G.render_mesh(out['verts'], out['faces'], cams, resolution=args.render_res, normals=out.get('normals'), colors=out.get('colors'))
+            shaded = to8(views['shaded'][:, 0])
+            rgb = to8(views['rgb'].permute(0, 2, 3, 1)) if 'rgb' in views else None
+            err_rgb = None
+            if args.compare and args.error_ply:
+                err_cols = torch.from_numpy(geometry.read_ply(os.path.join(args.outdir, f'seed{seed:04d}_error.ply'))[2]).to(out['verts'].device)
+                err_rgb = to8(G.render_mesh(out['verts'], out['faces'], cams, resolution=args.render_res, colors=err_cols)['rgb'].permute(0, 2, 3, 1))
+            for k in range(args.mesh_views):
+                Image.fromarray(shaded[k], mode='L').save(os.path.join(args.outdir, f'seed{seed:04d}_meshview{k:02d}.png'))
+                if rgb is not None:
+                    Image.fromarray(rgb[k], mode='RGB').save(os.path.join(args.outdir, f'seed{seed:04d}_meshrgb{k:02d}.png'))
+                if err_rgb is not None:
+                    Image.fromarray(err_rgb[k], mode='RGB').save(os.path.join(args.outdir, f'seed{seed:04d}_errorview{k:02d}.png'))
+            if args.save_depth:
+                np.save(os.path.join(args.outdir, f'seed{seed:04d}_meshdepth.npy'), views['depth'][:, 0].cpu().numpy())
+            out['mesh_views'] = views
+            print(f'seed {seed}: {args.mesh_views} mesh views at {args.render_res}^2, {int(views["mask"].sum())} surface pixels, '
+                  f'{int(views["culled"].sum())} culled triangles')
         results.append((path, out))
     return results
 

@@ -29,7 +29,15 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   weights, pinned boundary) and vertex normals from the mesh itself.  Device tensors go to the kernels of csrc/smooth.hip (``ia_mesh_*``,
   ``ia_smooth_*``; the two sorts of integer keys are ``torch.sort``); CPU tensors and NumPy arrays take the NumPy restatement that is the
   definition (float64 sums, positions rounded to float32 once per step).
+- ``rasterize_mesh``: z-buffer rasteriser of an indexed mesh from N cameras: mask, face, perspective-correct barycentrics, depth,
+  normals and interpolated vertex attributes per pixel.  Device tensors go to ``ia_mesh_project`` + ``ia_mesh_raster`` +
+  ``ia_mesh_resolve`` (csrc/mesh_raster.hip); CPU tensors and NumPy arrays take the NumPy restatement that is the definition (integer
+  coverage on coordinates snapped to 1/256 pixel, float32 operations in the kernel's order, or float64 with ``dtype=``).
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
+
+Rasteriser: pixel centres are at integer coordinates, column i and row j of ``RaySampler_zxc`` (ray ``K_res^-1 [i, j, 1]``), so its images
+align with ``raycast`` on that sampler's rays; a pixel is covered under the top-left rule and goes to the nearest triangle, the lower
+face index at equal depth; triangles with a vertex at or behind ``near`` are dropped, not clipped.
 
 Lattice (used by the kernel, ``lattice_points`` and the mesh coordinates alike): point ``(i, j, k)`` of an ``nx x ny x nz`` lattice is, per
 axis and in fp32 with every operation rounded on its own, ``lo + i * step`` with ``lo = origin - 0.5 * L`` and ``step = L / (n - 1)``,
@@ -1506,6 +1514,227 @@ def signed_volume(verts, faces):
     a, b, c = (v[f[:, k]] for k in range(3))
     t = _dot3(a, _cross3(b, c))
     return float(t[np.isfinite(t)].sum() / 6)
+
+
+# ------------------------------------------------------------------ mesh rasteriser
+
+_CULL = ('none', 'back')
+RASTER_SUBPIXEL = 256           # snapped screen units per pixel (csrc/mesh_raster.hip: U = rintf(u * 256))
+RASTER_MAX_SCREEN = 1 << 20     # a vertex at |u| or |v| >= 2^20 pixels is unusable
+RASTER_MAX_CHANNELS = 8
+RASTER_OVERSIZE = 256           # default ``oversize_pixels``: a larger clamped box gets a wave of its own on the device
+_RASTER_PAIRS = 1 << 21         # face-pixel pairs per NumPy chunk
+
+
+def _hw(resolution):
+    h, w = (int(resolution),) * 2 if np.isscalar(resolution) else (int(r) for r in resolution)
+    if h < 1 or w < 1:
+        raise ValueError(f'resolution must be >= 1, got {resolution}')
+    return h, w
+
+
+def _camera_numpy(cam32, H, W, dtype):
+    """Of float32 labels [N,25], in ``dtype``: rotation [N,3,3], origin [N,3], rows 0 and 1 of K_res [N,6] (row 0 times W, row 1 times H)."""
+    c = cam32.astype(dtype)
+    m = c[:, :16].reshape(-1, 4, 4)
+    return m[:, :3, :3], m[:, :3, 3], np.concatenate([c[:, 16:19] * dtype(W), c[:, 19:22] * dtype(H)], 1)
+
+
+def _project_numpy(v32, cam32, H, W, near, dtype=F32):
+    """The project stage: {'U', 'V'} int64 [N,V] (snapped screen coordinates, always from the float32 run), 'usable' bool [N,V]
+    (likewise) and 'z' [N,V] in ``dtype``."""
+    def run(T):
+        R, o, k = _camera_numpy(cam32, H, W, T)
+        d = v32.astype(T)[None] - o[:, None]
+        xc = [(R[:, None, 0, a] * d[..., 0] + R[:, None, 1, a] * d[..., 1]) + R[:, None, 2, a] * d[..., 2] for a in range(3)]
+        px = (k[:, None, 0] * xc[0] + k[:, None, 1] * xc[1]) + k[:, None, 2] * xc[2]
+        py = (k[:, None, 3] * xc[0] + k[:, None, 4] * xc[1]) + k[:, None, 5] * xc[2]
+        return px / xc[2], py / xc[2], xc[2]
+    with np.errstate(all='ignore'):
+        u, v, z = run(F32)
+        usable = (np.isfinite(u) & np.isfinite(v) & np.isfinite(z) & ~(z <= F32(near)) & (np.abs(u) < F32(RASTER_MAX_SCREEN))
+                  & (np.abs(v) < F32(RASTER_MAX_SCREEN)))
+        U = np.where(usable, np.rint(u * F32(RASTER_SUBPIXEL)), F32(0)).astype(np.int64)
+        V = np.where(usable, np.rint(v * F32(RASTER_SUBPIXEL)), F32(0)).astype(np.int64)
+        if dtype is not F32:
+            z = run(dtype)[2]
+    return {'U': U, 'V': V, 'z': np.where(usable, z, dtype(0)), 'usable': usable}
+
+
+def _edge_values_numpy(U3, V3, s, X, Y):
+    """int64 edge values [e_0, e_1, e_2] of the points (X, Y) (e_k: the edge from vertex k + 1 to k + 2, times the area's sign ``s``, so
+    inside is >= 0 and the sum is |area|) and the coverage under the top-left rule: e_k > 0, or e_k = 0 on an edge with A > 0 or
+    (A = 0 and B > 0), A = -s (V_b - V_a), B = s (U_b - U_a), which is where a point moved right by an infinitesimal (and down by a
+    smaller one) would be inside."""
+    e, cover = [], True
+    for k in range(3):
+        a, b = (k + 1) % 3, (k + 2) % 3
+        ek = s * ((U3[a] - X) * (V3[b] - Y) - (V3[a] - Y) * (U3[b] - X))
+        A, B = -s * (V3[b] - V3[a]), s * (U3[b] - U3[a])
+        cover = cover & ((ek > 0) | ((ek == 0) & ((A > 0) | ((A == 0) & (B > 0)))))
+        e.append(ek)
+    return e, cover
+
+
+def _weights_numpy(e, dtype):
+    area = ((e[0] + e[1]) + e[2]).astype(dtype)
+    return [ek.astype(dtype) / area for ek in e]
+
+
+def _raster_faces_numpy(proj, n, faces, H, W, cull='none', dtype=F32):
+    """The raster stage for view ``n`` and the faces int64 [F,3]: (cover bool [F,H,W], z [F,H,W] in ``dtype`` (inf where not covered),
+    unusable bool [F])."""
+    U, V, z, usable = (proj[k][n] for k in ('U', 'V', 'z', 'usable'))
+    ok = usable[faces].all(1)
+    U3, V3, z3 = ([a[faces[:, k]][:, None, None] for k in range(3)] for a in (U, V, z))
+    area = (U3[1] - U3[0]) * (V3[2] - V3[0]) - (V3[1] - V3[0]) * (U3[2] - U3[0])
+    draw = ok[:, None, None] & (area != 0) & ((area < 0) | (cull != 'back'))
+    X = (np.arange(W, dtype=np.int64) * RASTER_SUBPIXEL)[None, None, :]
+    Y = (np.arange(H, dtype=np.int64) * RASTER_SUBPIXEL)[None, :, None]
+    e, cover = _edge_values_numpy(U3, V3, np.sign(area), X, Y)
+    cover = cover & draw
+    with np.errstate(all='ignore'):
+        lam = _weights_numpy(e, dtype)
+        zp = dtype(1) / ((lam[0] / z3[0] + lam[1] / z3[1]) + lam[2] / z3[2])
+    return cover, np.where(cover, zp, dtype(np.inf)), ~ok
+
+
+def _visibility_numpy(proj, n, faces, H, W, cull, dtype):
+    """Per pixel of view ``n`` the least (z, face) over the covering triangles, the order of the packed keys float_bits(z) << 32 | face
+    (z >= 0): (z [H,W], face int64 [H,W], -1 on a miss, culled count)."""
+    best_z, best_f, culled = np.full((H, W), np.inf, dtype=dtype), np.full((H, W), -1, dtype=np.int64), 0
+    chunk = max(1, _RASTER_PAIRS // (H * W))
+    for c0 in range(0, faces.shape[0], chunk):
+        cover, zc, bad = _raster_faces_numpy(proj, n, faces[c0:c0 + chunk], H, W, cull, dtype)
+        culled += int(bad.sum())
+        a = zc.argmin(0)                                              # (the first of equal depths: the lower face)
+        za = np.take_along_axis(zc, a[None], 0)[0]
+        better = np.take_along_axis(cover, a[None], 0)[0] & (za < best_z)
+        best_z, best_f = np.where(better, za, best_z), np.where(better, a + c0, best_f)
+    return best_z, best_f, culled
+
+
+def _unit_rows(v, dtype):
+    with np.errstate(all='ignore'):
+        l = np.sqrt(_dot3(v, v))
+        ok = (l > 0) & np.isfinite(l)
+        return np.where(ok[..., None], v / np.where(ok, l, dtype(1))[..., None], dtype(0))
+
+
+def _resolve_numpy(proj, n, z, face, v32, faces, cam32, H, W, normals=None, attributes=None, dtype=F32):
+    """The resolve stage for view ``n``: dict of mask, face, bary [H,W,3], depth, normal [H,W,3], attributes [H,W,C] or None."""
+    hit = face >= 0
+    out = {'mask': hit, 'face': face.astype(np.int32), 'bary': np.zeros((H, W, 3), dtype), 'depth': np.zeros((H, W), dtype),
+           'normal': np.zeros((H, W, 3), dtype), 'attributes': None if attributes is None else np.zeros((H, W, attributes.shape[1]), dtype)}
+    if not hit.any():
+        return out
+    idx = faces[np.where(hit, face, 0)]                               # [H,W,3]
+    U3, V3, z3 = ([proj[k][n][idx[..., c]] for c in range(3)] for k in ('U', 'V', 'z'))
+    area = (U3[1] - U3[0]) * (V3[2] - V3[0]) - (V3[1] - V3[0]) * (U3[2] - U3[0])
+    X = (np.arange(W, dtype=np.int64) * RASTER_SUBPIXEL)[None, :]
+    Y = (np.arange(H, dtype=np.int64) * RASTER_SUBPIXEL)[:, None]
+    e, _ = _edge_values_numpy(U3, V3, np.sign(area), X, Y)
+    k = _camera_numpy(cam32, H, W, dtype)[2][n]
+    with np.errstate(all='ignore'):
+        lam = _weights_numpy(e, dtype)
+        b = np.stack([(lam[c] / z3[c]) * z for c in range(3)], -1)
+        xs, ys = np.arange(W, dtype=dtype)[None, :] - k[2], np.arange(H, dtype=dtype)[:, None] - k[5]
+        det = k[0] * k[4] - k[1] * k[3]
+        dx, dy = (k[4] * xs - k[1] * ys) / det, (k[0] * ys - k[3] * xs) / det
+        depth = z * np.sqrt((dx * dx + dy * dy) + dtype(1))
+        mix = lambda a: (b[..., 0, None] * a[idx[..., 0]] + b[..., 1, None] * a[idx[..., 1]]) + b[..., 2, None] * a[idx[..., 2]]
+        if normals is None:
+            p = v32.astype(dtype)
+            A = p[idx[..., 0]]
+            nrm = _cross3(p[idx[..., 1]] - A, p[idx[..., 2]] - A)
+        else:
+            nrm = mix(normals.astype(dtype))
+        out['normal'] = np.where(hit[..., None], _unit_rows(nrm, dtype), dtype(0))
+        if attributes is not None:
+            out['attributes'] = np.where(hit[..., None], mix(attributes.astype(dtype)), dtype(0))
+    out['bary'], out['depth'] = np.where(hit[..., None], b, dtype(0)), np.where(hit, depth, dtype(0))
+    return out
+
+
+def _rasterize_numpy(v32, faces, cam32, H, W, normals, attributes, cull, near, dtype):
+    proj = _project_numpy(v32, cam32, H, W, near, dtype)
+    views, culled = [], []
+    for n in range(cam32.shape[0]):
+        z, face, bad = _visibility_numpy(proj, n, faces, H, W, cull, dtype)
+        views.append(_resolve_numpy(proj, n, z, face, v32, faces, cam32, H, W, normals, attributes, dtype))
+        culled.append(bad)
+    out = {k: None if views[0][k] is None else np.stack([v[k] for v in views]) for k in views[0]}
+    out['culled'] = np.array(culled, dtype=np.int32)
+    return out
+
+
+def rasterize_mesh(verts, faces, cameras, resolution, normals=None, attributes=None, cull='none', near=1e-6, oversize_pixels=None,
+                   dtype=np.float32):
+    """Z-buffer rasteriser: the mesh (verts float32 [V,3], faces [F,3]) seen from the cameras [N,25] (cam2world 4x4, K 3x3 normalised,
+    the labels of the generator) at ``resolution`` (an int, or (H, W) with row 0 of K scaled by W and row 1 by H).  Returns a dict with
+    leading shape [N,H,W]: 'mask' bool, 'face' int32 (-1 on a miss), 'bary' [..., 3] (perspective-correct), 'depth' (the ray parameter of
+    the pixel's unit ray, the quantity ``raycast`` returns; 0 on a miss), 'normal' [..., 3] (the unit normal (B - A) x (C - A) of the
+    winding, or with ``normals`` [V,3] their normalised barycentric mix; 0 on a miss), 'attributes' [..., C] (the barycentric mix of
+    ``attributes`` float [V,C], C <= 8; None without) and 'culled' int32 [N].  Pixel centres are at INTEGER coordinates (column i, row j,
+    as in ``RaySampler_zxc``), so an image aligns pixel for pixel with ``raycast`` on that sampler's rays.  The definition:
+
+    1. Project, float32, every operation rounded on its own: d = X - o, xc = R^T d as ``(R_0a d_x + R_1a d_y) + R_2a d_z``,
+       p = K_res xc as ``(k0 x + k1 y) + k2 z``, u = p_x / xc_z, v = p_y / xc_z, z = xc_z; U = rint(256 u), V = rint(256 v).  A vertex is
+       unusable if u, v or z is not finite, z <= ``near``, or |u| or |v| >= 2^20.  The last row of K must be [0, 0, 1].
+    2. A triangle with an unusable vertex is culled and counted in 'culled'; one with zero snapped area is culled; nothing is clipped at
+       the near plane (a triangle that crosses it disappears).  ``cull='back'`` draws only triangles that face the camera (negative
+       snapped area: x right, y down, outward winding), ``'none'`` both windings.
+    3. Pixel (i, j) is the point (256 i, 256 j).  It is covered where the three int64 edge functions, oriented by the area's sign, are
+       >= 0, with the top-left rule where one is 0 (``_edge_values_numpy``).  lambda_k = E_k / (E_0 + E_1 + E_2),
+       z = 1 / ((lambda_0 / z_0 + lambda_1 / z_1) + lambda_2 / z_2); the pixel goes to the triangle of least (z, face index).
+    4. bary_k = (lambda_k / z_k) z; depth = z sqrt((dx dx + dy dy) + 1) with x' = i - k2, y' = j - k5, det = k0 k4 - k1 k3,
+       dx = (k4 x' - k1 y') / det, dy = (k0 y' - k3 x') / det; mixes are ``(b_0 a_0 + b_1 a_1) + b_2 a_2``.
+
+    Device tensors run on ia_mesh_project + ia_mesh_raster + ia_mesh_resolve (csrc/mesh_raster.hip: a 64-bit atomicMin of the key
+    float_bits(z) << 32 | face, whose result does not depend on the order of evaluation; ``oversize_pixels``: triangles whose clamped
+    bounding box holds more pixels are drawn by one wave each, which changes no result) and give the bits of the float32 restatement.
+    CPU tensors and NumPy arrays take the NumPy restatement; ``dtype=np.float64`` evaluates its floating-point part (z, the weights,
+    depth, normals, mixes) in double on the same snapped integers, and then returns float64 arrays."""
+    _mesh_args(verts, faces)
+    if cull not in _CULL:
+        raise ValueError(f'cull must be one of {_CULL}, got {cull!r}')
+    H, W = _hw(resolution)
+    near = float(near)
+    if not near >= 0:
+        raise ValueError(f'near must be >= 0, got {near!r}')
+    if cameras.ndim != 2 or cameras.shape[1] != 25 or cameras.shape[0] < 1:
+        raise ValueError(f'cameras must be [N,25] with N >= 1, got {tuple(cameras.shape)}')
+    nv = int(verts.shape[0])
+    for name, a, width in (('normals', normals, 3), ('attributes', attributes, None)):
+        if a is not None and (a.ndim != 2 or a.shape[0] != nv or (width and a.shape[1] != width)):
+            raise ValueError(f'{name} must be [{nv},{width or "C"}], got {tuple(a.shape)}')
+    if attributes is not None and not 1 <= attributes.shape[1] <= RASTER_MAX_CHANNELS:
+        raise ValueError(f'attributes must have 1 .. {RASTER_MAX_CHANNELS} channels, got {attributes.shape[1]}')
+    oversize = RASTER_OVERSIZE if oversize_pixels is None else int(oversize_pixels)
+    if oversize < 0:
+        raise ValueError(f'oversize_pixels must be >= 0, got {oversize_pixels}')
+    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+        from . import hipops
+        if dtype not in (np.float32, torch.float32):
+            raise ValueError('the device path is float32')
+        dev = verts.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+        f = torch.as_tensor(faces).to(device=dev, dtype=torch.int32).contiguous()
+        _faces_in_range(f, nv)
+        return hipops.rasterize_mesh(verts.detach().float().contiguous(), f, f32(cameras), H, W, f32(normals), f32(attributes), cull == 'back',
+                                     near, oversize)
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise ValueError(f'dtype must be float32 or float64, got {dtype}')
+    f = _np(faces).astype(np.int64)
+    _faces_in_range(f, nv)
+    cam32 = np.ascontiguousarray(_np(cameras), dtype=F32)
+    if cam32.shape[0] and not (cam32[:, 22:25] == np.array([0, 0, 1], dtype=F32)).all():
+        raise ValueError('the last row of K must be [0, 0, 1]')
+    as32 = lambda a: None if a is None else np.ascontiguousarray(_np(a), dtype=F32)
+    out = _rasterize_numpy(as32(verts), f, cam32, H, W, as32(normals), as32(attributes), cull, near, dtype)
+    kinds = {'mask': bool, 'face': np.int32, 'culled': np.int32}
+    return {k: None if x is None else _as_out(x, verts, kinds.get(k, dtype)) for k, x in out.items()}
 
 
 # ------------------------------------------------------------------ generator-level helpers

@@ -1977,3 +1977,83 @@ def mesh_normals(s, verts, faces, angle=False):
                                          _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_mesh_normals')
     return out
+
+
+# ------------------------------------------------------------------ mesh rasteriser (csrc/mesh_raster.hip)
+
+MESH_RASTER_TIMES = None     # a dict collects seconds per stage, as SMOOTH_TIMES does: tools/bench_mesh_raster.py
+
+
+def _views_checked(cams, resolution):
+    _f32c(cams, 'cameras')
+    if cams.dim() != 2 or cams.shape[1] != 25:
+        raise RuntimeError(f'cameras must be [N,25], got {tuple(cams.shape)}')
+    h, w = resolution
+    return cams.shape[0], int(h), int(w)
+
+
+def mesh_project(verts, cams, resolution, near=1e-6):
+    """int32 [N,V,4]: per view and vertex the snapped screen coordinates U, V (1/256 pixel), the bits of the camera depth z and the
+    usable flag (ia_mesh_project; reads the camera labels back once to check K)."""
+    _f32c(verts, 'verts')
+    n, h, w = _views_checked(cams, resolution)
+    dev = verts.device
+    proj = torch.empty(n, verts.shape[0], 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _Phase('project', dev, 'MESH_RASTER_TIMES'):
+        st = _lib.load().ia_mesh_project(_p(verts), verts.shape[0], _p(cams), n, h, w, float(near), _p(proj), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_project')
+    return proj
+
+
+def mesh_raster(proj, faces, resolution, cull_back=False, oversize_pixels=256):
+    """(vis int64 [N,H,W] holding the uint64 keys float_bits(z) << 32 | face, all ones on a miss; culled int32 [N]) (ia_mesh_raster)."""
+    _i32c(proj, 'proj')
+    _i32c(faces, 'faces')
+    n, v = proj.shape[:2]
+    h, w = (int(r) for r in resolution)
+    f, dev = faces.shape[0], proj.device
+    vis = torch.empty(n, h, w, dtype=torch.int64, device=dev)
+    culled = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _Phase('raster', dev, 'MESH_RASTER_TIMES'):
+        scratch, nbytes = (None, 0)
+        if f and oversize_pixels < h * w:
+            scratch, nbytes = _scratch('ia_mesh_raster_scratch_bytes', n, f, dtype=torch.int32, device=dev)
+        st = _lib.load().ia_mesh_raster(_p(proj), v, _p(faces), f, n, h, w, int(bool(cull_back)), int(oversize_pixels), _p(vis), _p(culled),
+                                        _p(scratch), nbytes, _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_raster')
+    return vis, culled
+
+
+def mesh_resolve(vis, proj, verts, faces, cams, normals=None, attributes=None, cull_back=False):
+    """dict of 'mask' bool, 'face' int32, 'bary' [..,3], 'depth', 'normal' [..,3], 'attributes' [..,C] or None, leading shape [N,H,W]
+    (ia_mesh_resolve)."""
+    _f32c(verts, 'verts')
+    _i32c(faces, 'faces')
+    n, h, w = vis.shape
+    _views_checked(cams, (h, w))
+    dev = verts.device
+    c = 0
+    if normals is not None:
+        _f32c(normals, 'normals')
+    if attributes is not None:
+        _f32c(attributes, 'attributes')
+        c = attributes.shape[1]
+    out = {'mask': torch.empty(n, h, w, dtype=torch.bool, device=dev), 'face': torch.empty(n, h, w, dtype=torch.int32, device=dev),
+           'bary': torch.empty(n, h, w, 3, device=dev), 'depth': torch.empty(n, h, w, device=dev), 'normal': torch.empty(n, h, w, 3, device=dev),
+           'attributes': torch.empty(n, h, w, c, device=dev) if c else None}
+    with torch.cuda.device(dev), _Phase('resolve', dev, 'MESH_RASTER_TIMES'):
+        st = _lib.load().ia_mesh_resolve(_p(vis), _p(proj), _p(verts), verts.shape[0], _p(faces), faces.shape[0], _p(cams), n, h, w,
+                                         int(bool(cull_back)), _p(normals), _p(attributes), c, _p(out['mask']), _p(out['face']), _p(out['bary']),
+                                         _p(out['depth']), _p(out['normal']), _p(out['attributes']), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_mesh_resolve')
+    return out
+
+
+def rasterize_mesh(verts, faces, cams, h, w, normals=None, attributes=None, cull_back=False, near=1e-6, oversize_pixels=256):
+    """The three stages of geometry.rasterize_mesh on the current stream; no host read after the camera check of the first."""
+    _mesh_checked(verts, faces)
+    proj = mesh_project(verts, cams, (h, w), near)
+    vis, culled = mesh_raster(proj, faces, (h, w), cull_back, oversize_pixels)
+    out = mesh_resolve(vis, proj, verts, faces, cams, normals, attributes, cull_back)
+    out['culled'] = culled
+    return out

@@ -636,6 +636,31 @@ class TriPlaneGenerator(torch.nn.Module):
             out[k] = x.reshape(lead + x.shape[1:])
         return out
 
+    def render_mesh(self, verts, faces, c, resolution=512, normals=None, colors=None, cull='none'):
+        """Renders of one triangle mesh (verts [V,3], faces [F,3]: an extracted, simplified or smoothed mesh, or one read with
+        ``read_ply``) from the cameras ``c`` ([V,25] or [B,V,25]) through ``geometry.rasterize_mesh``; pixels align with
+        ``render_geometry`` and ``image_depth`` at the same resolution.  Returns the NCHW dictionary of ``render_geometry``: 'depth'
+        [(B,)V,1,H,W] (ray parameter; 0 on a miss), 'mask' bool, 'normal' [(B,)V,3,H,W] (the face normal of the winding, or with
+        ``normals`` [V,3] their interpolation), 'shaded' (headlight Lambert, ``geometry.shade`` with the rays of the generator's ray
+        sampler) and, with ``colors`` ([V,3], uint8 or float in [0, 1]), 'rgb' [(B,)V,3,H,W] (0 on a miss); besides these 'culled'
+        int32 [(B,)V], the triangles dropped per view for a vertex at or behind the near plane (nothing is clipped)."""
+        from .. import geometry
+        lead = tuple(c.shape[:-1])
+        cam = c.reshape(-1, 25).float()
+        attrs = None
+        if colors is not None:
+            attrs = colors.float() / 255 if colors.dtype == torch.uint8 else colors.float()
+        hit = geometry.rasterize_mesh(verts, faces, cam, resolution, normals=normals, attributes=attrs, cull=cull)
+        _, rays_d = self.ray_sampler(cam[:, :16].view(-1, 4, 4), cam[:, 16:25].view(-1, 3, 3), resolution)
+        rays_d = rays_d.reshape(-1, resolution, resolution, 3)
+        out = {'depth': hit['depth'][..., None], 'mask': hit['mask'][..., None], 'normal': hit['normal'],
+               'shaded': geometry.shade(hit['normal'], rays_d, hit['mask'])}
+        if colors is not None:
+            out['rgb'] = hit['attributes']
+        out = {k: x.permute(0, 3, 1, 2).reshape(lead + (x.shape[3], resolution, resolution)) for k, x in out.items()}
+        out['culled'] = hit['culled'].reshape(lead)
+        return out
+
     def forward(self, z, c, v, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None, update_emas=False,
                 cache_backbone=False, use_cached_backbone=False, **synthesis_kwargs):
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)

@@ -1102,6 +1102,32 @@ int ia_mesh_resolve(const unsigned long long* vis, const void* proj, const float
                     const float* cams, int N, int H, int W, int cull_back, const float* normals, const float* attributes, int C,
                     unsigned char* mask, int* face, float* bary, float* depth, float* normal, float* attr_out, void* stream);
 
+/*
+ * Alignment of a point set to a triangle mesh (csrc/align.hip; no counterpart in the reference; definition: geometry.align_mesh and
+ * its NumPy restatement).  The two kernels around ia_closest_point in one ICP iteration.  Additive entry points: the ABI
+ * version is unchanged.
+ *
+ * ia_transform_points: out float32 [N,3] = fp32(M) x for points float32 [N,3]; h_m12 = 12 doubles on the host, the rows of [s R | t],
+ * rounded to fp32 here.  Per row ((m0 x + m1 y) + m2 z) + t, every operation rounded on its own.  A non-finite input gives a
+ * non-finite output.  out may be points.
+ *
+ * ia_align_sums: the sums of one iteration over the pairs (src[i], dst[i]) that count: dist[i] finite, face[i] >= 0,
+ * dist[i] <= h_max_dist (fp32 compare; +inf: no threshold) and, for mode 1, face[i] < Fb with a finite, non-zero face_normals[face[i]].
+ * With p = src[i] - centre and q = dst[i] - centre in double (h_centre: 3 doubles on the host), out is
+ *   mode 0 (point), double [20]: n, sum p (3), sum q (3), sum p q^T (9, row-major), sum |p|^2, sum |q|^2, sum |p - q|^2, and in the
+ *                                last slot the number of pairs that do not count;
+ *   mode 1 (plane), double [56]: the same 19 sums, then with a = (p x n, n, p . n) and b = (q - p) . n the upper triangle of
+ *                                sum a a^T (28, row-major), sum a b (7), sum b^2, and in the last slot the pairs that do not count.
+ * src, dst float32 [N,3], dist float32 [N], face int32 [N], face_normals float32 [Fb,3] (ignored for mode 0).  A thread sums a
+ * contiguous slice in index order, wave and workgroup combine in a fixed order and a second launch adds the workgroups in a fixed order:
+ * no floating-point atomics, bit-equal run to run.  scratch: ia_align_sums_scratch_bytes(N, mode) bytes, 8-byte aligned.
+ */
+int ia_transform_points(const float* points, int64_t N, const double* h_m12, float* out, void* stream);
+int ia_align_sums_scratch_bytes(int64_t N, int mode, size_t* h_bytes);
+int ia_align_sums(const float* src, const float* dst, const float* dist, const int* face, int64_t N, const float* face_normals,
+                  int64_t Fb, const double* h_centre, float h_max_dist, int mode, void* scratch, size_t scratch_bytes, double* out,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

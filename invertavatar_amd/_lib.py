@@ -160,6 +160,10 @@ _SIGNATURES = {
                        ctypes.c_size_t, c_void_p],
     'ia_mesh_resolve': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_transform_points': [c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), c_void_p, c_void_p],
+    'ia_align_sums_scratch_bytes': [c_int64, c_int, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_align_sums': [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), c_float, c_int,
+                      c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
 }
 
 

@@ -11,7 +11,9 @@ volume first, so the PLY, the views and the saved depth show the N largest only;
 than M lattice points; a line per seed reports how many components there were and the sizes of the kept ones.  ``--compare REF.ply``
 prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh against ``REF.ply`` and writes them as
 ``seed%04d_geometry.json`` (``geometry_metrics.compare_meshes``); ``--error-ply`` also writes ``seed%04d_error.ply``, the mesh coloured by
-its distance to the reference.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
+its distance to the reference; ``--align rigid|similarity`` (with ``--align-metric``, ``--align-iterations``, ``--align-trim``, ``--align-init``,
+as in ``geometry_metrics``) first moves the extracted mesh onto ``REF.ply`` with ``geometry.align_mesh``, prints the scale, the rotation angle,
+|t| and the rms before and after, and scores, colours and (``--mesh-views``) renders the error of the moved mesh.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
 clustering; the line per seed then shows the triangle counts before and after), ``--simplify-cells C`` to a grid of C cells along the
 longest axis; ``--simplify-check`` scores the simplified mesh against the full one (``geometry.surface_distance``), prints both directed
 Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  ``--smooth N`` smooths the mesh with N
@@ -96,6 +98,7 @@ def main(argv=None):
     ap.add_argument('--min-voxels', type=int, default=0, help='with --keep: also drop kept components of fewer lattice points')
     ap.add_argument('--compare', default=None, metavar='REF.ply', help='score the extracted mesh against this mesh (Chamfer, Hausdorff, F-score)')
     ap.add_argument('--error-ply', action='store_true', help='with --compare: also write the mesh coloured by its distance to REF.ply')
+    geometry_metrics.add_align_arguments(ap)
     grp = ap.add_mutually_exclusive_group()
     grp.add_argument('--simplify', type=int, default=None, metavar='N', help='simplify the mesh to at most N triangles')
     grp.add_argument('--simplify-cells', type=int, default=None, metavar='C', help='simplify on a grid of C cells along the longest axis')
@@ -117,6 +120,8 @@ def main(argv=None):
         ap.error('--simplify-check needs --simplify or --simplify-cells')
     if args.smooth_check and args.smooth is None:
         ap.error('--smooth-check needs --smooth')
+    if args.align and not args.compare:
+        ap.error('--align needs --compare')
     smooth = None if args.smooth is None else {'iterations': args.smooth, 'lam': args.smooth_lambda, 'mu': args.smooth_mu,
                                                'weights': args.smooth_weights}
     for seed, w in zip(args.seeds, ws):
@@ -176,9 +181,15 @@ def main(argv=None):
             rv, rf, _ = geometry.read_ply(args.compare)
             rv, rf = torch.from_numpy(rv).to(out['verts'].device), torch.from_numpy(rf).to(out['verts'].device)
             err = os.path.join(args.outdir, f'seed{seed:04d}_error.ply') if args.error_ply else None
-            out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err)
+            extra = {}
+            if args.align:
+                out['aligned'] = {}
+                extra = {'align': args.align, 'align_options': geometry_metrics.align_options_of(args), 'aligned': out['aligned']}
+            out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err, **extra)
             with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
                 json.dump(dict(out['metrics'], **{k: out[k] for k in ('simplify', 'smooth') if k in out}), fh, indent=1)
+            if args.align:
+                print(f'seed {seed}: {geometry_metrics.alignment_summary(out["metrics"]["alignment"])}')
             print(f'seed {seed}: against {args.compare}: {geometry_metrics.summary(out["metrics"])}')
         if args.views > 0:
             from PIL import Image
@@ -202,7 +213,8 @@ def main(argv=None):
             err_rgb = None
             if args.compare and args.error_ply:
                 err_cols = torch.from_numpy(geometry.read_ply(os.path.join(args.outdir, f'seed{seed:04d}_error.ply'))[2]).to(out['verts'].device)
-                err_rgb = to8(G.render_mesh(out['verts'], out['faces'], cams, resolution=args.render_res, colors=err_cols)['rgb'].permute(0, 2, 3, 1))
+                err_verts = out['aligned']['verts'] if args.align else out['verts']
+                err_rgb = to8(G.render_mesh(err_verts, out['faces'], cams, resolution=args.render_res, colors=err_cols)['rgb'].permute(0, 2, 3, 1))
             for k in range(args.mesh_views):
                 Image.fromarray(shaded[k], mode='L').save(os.path.join(args.outdir, f'seed{seed:04d}_meshview{k:02d}.png'))
                 if rgb is not None:

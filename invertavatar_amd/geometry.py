@@ -33,6 +33,10 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   normals and interpolated vertex attributes per pixel.  Device tensors go to ``ia_mesh_project`` + ``ia_mesh_raster`` +
   ``ia_mesh_resolve`` (csrc/mesh_raster.hip); CPU tensors and NumPy arrays take the NumPy restatement that is the definition (integer
   coverage on coordinates snapped to 1/256 pixel, float32 operations in the kernel's order, or float64 with ``dtype=``).
+- ``align_mesh`` / ``fit_transform`` / ``transform_points``: rigid or similarity alignment of points to a mesh by iterated closest
+  points (point-to-point or point-to-plane, trimmed), the closed form for given correspondences, and the transform itself.  Device
+  tensors go to ``ia_transform_points`` + ``ia_closest_point`` + ``ia_align_sums`` (csrc/align.hip) with the step solved on the host in
+  float64; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Rasteriser: pixel centres are at integer coordinates, column i and row j of ``RaySampler_zxc`` (ray ``K_res^-1 [i, j, 1]``), so its images
@@ -903,6 +907,326 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     if na is not None and nb is not None and s_ab[0] + s_ba[0] > 0:
         res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
     return res
+
+
+# ------------------------------------------------------------------ alignment
+
+EPS32 = float(np.finfo(np.float32).eps)
+_ALIGN_MIN = {'point': 3, 'plane': 6}
+_LSTSQ_RCOND = 1e-12         # singular values of the plane system below this share of the largest are directions that do not move
+
+
+def _matrix44(M):
+    m = np.asarray(_np(M), dtype=np.float64)
+    if m.shape == (3, 4):
+        m = np.concatenate([m, [[0.0, 0.0, 0.0, 1.0]]])
+    if m.shape != (4, 4) or not np.isfinite(m).all():
+        raise ValueError(f'a transform is a finite 4x4 (or 3x4) matrix, got shape {m.shape}')
+    return m
+
+
+def _transform_numpy(x, M, dtype=F32):
+    """NumPy restatement of ia_transform_points: ``((m0 x + m1 y) + m2 z) + t`` per row in ``dtype`` with ``M`` rounded to it."""
+    x = np.asarray(x, dtype=F32).reshape(-1, 3).astype(dtype)
+    m = _matrix44(M).astype(dtype)
+    with np.errstate(invalid='ignore', over='ignore'):
+        return np.stack([((m[r, 0] * x[:, 0] + m[r, 1] * x[:, 1]) + m[r, 2] * x[:, 2]) + m[r, 3] for r in range(3)], -1).astype(dtype)
+
+
+def transform_points(points, M):
+    """``y = M x`` for points [..., 3] and a 4x4 (or 3x4) transform ``M = [s R | t]`` given as floats on the host: float32 arithmetic
+    with ``M`` rounded to float32, per row ``((m0 x + m1 y) + m2 z) + t``.  Device tensors run on ia_transform_points, CPU tensors
+    and NumPy arrays on the NumPy restatement of it (the same operations in the same order)."""
+    m = _matrix44(M)
+    if points.shape[-1] != 3:
+        raise ValueError(f'points must be [..., 3], got {tuple(points.shape)}')
+    if isinstance(points, torch.Tensor) and points.is_cuda:
+        from . import hipops
+        return hipops.transform_points(points.detach().float().reshape(-1, 3).contiguous(), m).reshape(points.shape)
+    return _as_out(_transform_numpy(_np(points), m).reshape(tuple(points.shape)), points)
+
+
+def _rodrigues(w):
+    """The rotation about ``w`` by ``|w|``."""
+    th = float(np.linalg.norm(w))
+    if th == 0.0:
+        return np.eye(3)
+    k = np.asarray(w, dtype=np.float64) / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+
+
+def _about(A, t, c):
+    """4x4 of ``y = c + A (x - c) + t``."""
+    M = np.eye(4)
+    M[:3, :3] = A
+    M[:3, 3] = c + t - A @ c
+    return M
+
+
+def _align_terms_numpy(p, q, dist, face, normals, centre, max_dist, metric):
+    """The terms of ia_align_sums in float64: ``(terms [m, 19 or 55], rejected)``, one row per pair that counts, in index order.
+    ``max_dist``: the one effective threshold (compared in float32), +inf for none."""
+    p, q = np.asarray(p, dtype=np.float64).reshape(-1, 3), np.asarray(q, dtype=np.float64).reshape(-1, 3)
+    d, f = np.asarray(dist).astype(F32).reshape(-1), np.asarray(face).astype(np.int64).reshape(-1)
+    with np.errstate(invalid='ignore'):
+        ok = np.isfinite(d) & (f >= 0) & (d <= F32(max_dist))
+    if metric == 'plane':
+        nrm = np.asarray(normals, dtype=F32).reshape(-1, 3)
+        ok &= f < nrm.shape[0]
+        n_all = nrm[np.where(ok, f, 0)] if nrm.shape[0] else np.zeros((f.size, 3), dtype=F32)
+        ok &= np.isfinite(n_all).all(1) & (n_all != 0).any(1)
+    c = np.asarray(centre, dtype=np.float64)
+    p, q = p[ok] - c, q[ok] - c
+    e = p - q
+    cols = [np.ones(p.shape[0]), p[:, 0], p[:, 1], p[:, 2], q[:, 0], q[:, 1], q[:, 2]]
+    cols += [p[:, i] * q[:, j] for i in range(3) for j in range(3)]
+    cols += [_dot3(p, p), _dot3(q, q), _dot3(e, e)]
+    if metric == 'plane':
+        n = n_all[ok].astype(np.float64)
+        a = np.concatenate([_cross3(p, n), n, _dot3(p, n)[:, None]], 1)
+        b = _dot3(q - p, n)
+        cols += [a[:, i] * a[:, j] for i in range(7) for j in range(i, 7)]
+        cols += [a[:, i] * b for i in range(7)] + [b * b]
+    return np.stack(cols, 1), int(ok.size - np.count_nonzero(ok))
+
+
+def _column_sums(terms):
+    """The correctly rounded sum of every column (``math.fsum``): the restatement's sums do not depend on the order of the rows."""
+    import math
+    return np.array([math.fsum(col) for col in np.asarray(terms, dtype=np.float64).T.tolist()], dtype=np.float64).reshape(terms.shape[1])
+
+
+def _align_sums_numpy(p, q, dist, face, normals, centre, max_dist, metric):
+    """NumPy restatement of ia_align_sums: float64 [20] (point) or [56] (plane), the last slot the pairs left out."""
+    terms, rejected = _align_terms_numpy(p, q, dist, face, normals, centre, max_dist, metric)
+    return np.concatenate([_column_sums(terms), [float(rejected)]])
+
+
+def _solve_point(S, scale, centre, floor=0.0):
+    """Umeyama / Horn from the 19 point sums (taken about ``centre``): the 4x4 that maps p onto q in the least-squares sense."""
+    n = S[0]
+    pm, qm = S[1:4] / n, S[4:7] / n
+    H = S[7:16].reshape(3, 3) - n * np.outer(pm, qm)
+    var = S[16] - n * float(pm @ pm)
+    if not np.isfinite(H).all() or not var > floor:
+        raise ValueError('the source points coincide (or are not finite): no transform is determined')
+    U, sig, Vt = np.linalg.svd(H)
+    D = np.diag([1.0, 1.0, float(np.sign(np.linalg.det(Vt.T @ U.T))) or 1.0])
+    R = Vt.T @ D @ U.T
+    s = float((sig * np.diag(D)).sum() / var) if scale else 1.0
+    if not s > 0:
+        raise ValueError('the correspondences determine no positive scale')
+    return _about(s * R, qm - s * R @ pm, np.asarray(centre, dtype=np.float64))
+
+
+def _solve_plane(S, scale, centre):
+    """One Gauss-Newton step of the point-to-plane objective from the 55 plane sums: minimum-norm solution of the 6x6 (7x7 with scale)
+    normal equations, the rotation taken exactly (Rodrigues), acting about ``centre``."""
+    k = 7 if scale else 6
+    A = np.zeros((7, 7))
+    A[np.triu_indices(7)] = S[19:47]
+    A = A + np.triu(A, 1).T
+    x = np.linalg.lstsq(A[:k, :k], S[47:47 + k], rcond=_LSTSQ_RCOND)[0]
+    s = 1.0 + (float(x[6]) if scale else 0.0)
+    if not s > 0:
+        raise ValueError('the step would make the scale non-positive: the start is too far from the target')
+    return _about(s * _rodrigues(x[:3]), x[3:6], np.asarray(centre, dtype=np.float64))
+
+
+def _align_residual(S, metric):
+    """(rms of the pairs that count, their number) from the sums of one pairing."""
+    n = int(S[0])
+    if n < _ALIGN_MIN[metric]:
+        raise ValueError(f"align_mesh: {n} pairs count, metric '{metric}' needs at least {_ALIGN_MIN[metric]}")
+    return float(np.sqrt(max(S[18], 0.0) / n)), n
+
+
+def _align_solve(S, metric, scale, centre):
+    """The increment (float64 4x4) from the sums of one pairing; shared by the device path and the restatement."""
+    return _solve_point(S, scale, centre) if metric == 'point' else _solve_plane(S, scale, centre)
+
+
+def fit_transform(src, dst, scale=False, weights=None):
+    """The transform ``y = s R x + t`` (float64 4x4, ``M[:3,:3] = s R``) that maps points ``src`` [N,3] onto their correspondences ``dst``
+    [N,3] in the least-squares sense (Umeyama / Horn, optionally weighted): ``H = sum w (p - pm)(q - qm)^T = U S V^T``,
+    ``R = V diag(1, 1, det(V U^T)) U^T`` (a proper rotation also for a mirrored target), ``s = tr(S D) / sum w |p - pm|^2`` with
+    ``scale=True`` and 1 otherwise, ``t = qm - s R pm``.  A plain float64 host solve for landmarks, e.g. to start ``align_mesh``.  Fewer
+    than 3 pairs, or source points that coincide, raise ValueError."""
+    p, q = np.asarray(_np(src), dtype=np.float64).reshape(-1, 3), np.asarray(_np(dst), dtype=np.float64).reshape(-1, 3)
+    if p.shape != q.shape:
+        raise ValueError(f'src and dst must both be [N,3], got {p.shape} and {q.shape}')
+    w = np.ones(p.shape[0]) if weights is None else np.asarray(_np(weights), dtype=np.float64).reshape(-1)
+    if w.shape[0] != p.shape[0] or not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError('weights must be N finite numbers >= 0')
+    use = w > 0
+    if np.count_nonzero(use) < 3:
+        raise ValueError(f'fit_transform needs at least 3 pairs, got {np.count_nonzero(use)}')
+    if not (np.isfinite(p[use]).all() and np.isfinite(q[use]).all()):
+        raise ValueError('fit_transform: the points must be finite')
+    p, q, w = p[use], q[use], w[use]
+    c = (w[:, None] * p).sum(0) / w.sum()
+    pc, qc = p - c, q - c
+    S = np.concatenate([[w.sum()], (w[:, None] * pc).sum(0), (w[:, None] * qc).sum(0),
+                        ((w[:, None] * pc)[:, :, None] * qc[:, None, :]).sum(0).reshape(-1),
+                        [(w * _dot3(pc, pc)).sum(), (w * _dot3(qc, qc)).sum(), (w * _dot3(pc - qc, pc - qc)).sum()]])
+    floor = w.sum() * (16 * np.finfo(np.float64).eps * max(float(np.abs(p).max()), np.finfo(np.float64).tiny)) ** 2
+    return _solve_point(S, scale, c, floor)
+
+
+def _finite_rows(x):
+    return x[np.isfinite(x).all(1)]
+
+
+def _centroid_init(src, verts, scale):
+    """Centroid of the finite source points onto the centroid of the finite target vertices; with ``scale`` also rms radius onto rms radius."""
+    a, b = _finite_rows(np.asarray(src, dtype=np.float64)), _finite_rows(np.asarray(verts, dtype=np.float64))
+    if not a.shape[0] or not b.shape[0]:
+        raise ValueError("init='centroid' needs finite source points and target vertices")
+    ca, cb = a.mean(0), b.mean(0)
+    s = 1.0
+    if scale:
+        ra, rb = np.sqrt(((a - ca) ** 2).sum(1).mean()), np.sqrt(((b - cb) ** 2).sum(1).mean())
+        if not (ra > 0 and rb > 0):
+            raise ValueError("init='centroid' with scale needs point sets with an extent")
+        s = float(rb / ra)
+    M = np.eye(4)
+    M[:3, :3] *= s
+    M[:3, 3] = cb - s * ca
+    return M
+
+
+def _trim_threshold_numpy(dist, face, max_dist, trim):
+    """The one effective threshold ``min(max_dist, tau)`` as float32; tau: the ``ceil(trim n_finite)``-th smallest finite distance."""
+    thr = F32(np.inf) if max_dist is None else F32(max_dist)
+    if trim < 1.0:
+        d = np.asarray(dist).astype(F32)
+        fin = d[np.isfinite(d) & (np.asarray(face) >= 0)]
+        if fin.size:
+            k = max(int(np.ceil(trim * float(fin.size))), 1)
+            thr = min(thr, np.partition(fin, k - 1)[k - 1])
+    return float(thr)
+
+
+def _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol):
+    """Steps 1 to 6 of ``align_mesh`` around ``pair(M) -> sums`` (float64 [20] or [56])."""
+    M, hist, steps, converged, n = M0, [], 0, False, 0
+    for k in range(iterations + 1):
+        S = np.asarray(pair(M), dtype=np.float64)
+        rms, n = _align_residual(S, metric)
+        hist.append(rms)
+        if rms <= EPS32 * extent or (k > 0 and abs(hist[k - 1] - rms) <= tol * hist[k - 1]):
+            converged = True
+            break
+        if k == iterations:
+            break
+        M = _align_solve(S, metric, scale, centre) @ M
+        steps += 1
+    A = M[:3, :3]
+    s = float(np.cbrt(np.linalg.det(A)))
+    return {'matrix': M, 'scale': s, 'rotation': A / s, 'translation': M[:3, 3].copy(), 'rms': hist[-1], 'rms_history': hist,
+            'inliers': n, 'iterations': steps, 'converged': converged}
+
+
+def _align_numpy(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, dtype=np.float64):
+    """The NumPy restatement of ``align_mesh`` (the definition); ``dtype``: the precision of the closest-point search."""
+    src, verts, faces = np.asarray(src, dtype=F32).reshape(-1, 3), np.asarray(verts, dtype=F32), np.asarray(faces, dtype=np.int64)
+    fin = _finite_rows(verts)
+    if not faces.shape[0] or not fin.shape[0]:
+        raise ValueError('align_mesh: the target mesh is empty')
+    lo, hi = fin.min(0).astype(np.float64), fin.max(0).astype(np.float64)
+    centre, extent = (lo + hi) / 2, float(max(np.abs(lo).max(), np.abs(hi).max()))
+    normals = face_normals(verts, faces) if metric == 'plane' else None
+
+    def pair(M):
+        p = _transform_numpy(src, M)
+        dist, face, q = _closest_numpy(p, verts, faces, dtype)
+        return _align_sums_numpy(p, q, dist, face, normals, centre, _trim_threshold_numpy(dist, face, max_dist, trim), metric)
+    return _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol)
+
+
+def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, grid):
+    from . import hipops
+    if not faces.shape[0] or not verts.shape[0]:
+        raise ValueError('align_mesh: the target mesh is empty')
+    if grid is None:
+        grid = TriangleGrid(verts, faces)
+    dev = grid.verts.device
+    src = src.detach().to(dev).float().reshape(-1, 3).contiguous()
+    centre = [(float(a) + float(b)) / 2 for a, b in zip(grid.lo, grid.hi)]
+    normals = face_normals(grid.verts, grid.faces).float().contiguous() if metric == 'plane' else None
+    base = float('inf') if max_dist is None else float(F32(max_dist))
+
+    def pair(M):
+        p = hipops.transform_points(src, M)
+        r = grid.closest(p)
+        dist, face = r['dist'], r['face'].int()
+        thr = base
+        if trim < 1.0:                                                    # one more host synchronisation, for tau
+            d = torch.where(torch.isfinite(dist) & (face >= 0), dist, torch.full_like(dist, float('inf'))).sort().values
+            n_fin = torch.isfinite(d).sum()
+            k = torch.ceil(trim * n_fin.double()).long().clamp(1, max(d.numel(), 1))
+            if d.numel():
+                thr = min(base, float(d[k - 1]))
+        return hipops.align_sums(p, r['point'].contiguous(), dist.contiguous(), face.contiguous(), centre, thr, metric, normals).cpu().numpy()
+    return _align_loop(pair, np.asarray(centre), float(grid.extent), M0, metric, scale, iterations, tol)
+
+
+def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30, tol=1e-6, max_dist=None, trim=1.0, init='identity',
+               grid=None):
+    """Align ``source`` (points [N,3], or a ``(verts, faces)`` pair whose vertices are used) to the triangle mesh ``(verts, faces)`` by
+    iterated closest points: the rigid (``scale=False``) or similarity transform ``y = s R x + t`` that brings the points onto the
+    surface, as a float64 4x4 ``M`` with ``M[:3,:3] = s R``, ``M[:3,3] = t``.  ICP finds the local optimum nearest to the start, so the
+    start matters (``init``: 'identity', 'centroid' = centroid onto centroid and, with ``scale``, rms radius onto rms radius, or a 4x4,
+    e.g. from ``fit_transform`` on landmarks); a symmetric target leaves the pose undetermined.  One iteration, given ``M_k``:
+
+    1. ``p_i = fp32(M_k) x_i`` in float32 from the original points (``transform_points``);
+    2. ``(d_i, f_i, q_i)``: the closest point of the target mesh (``closest_point``);
+    3. pair i counts iff ``d_i`` is finite and ``f_i >= 0``, ``d_i <= max_dist`` if given, ``d_i <= tau`` if ``trim < 1`` (tau: the
+       ``ceil(trim n_finite)``-th smallest finite distance; ties stay in) and, for ``metric='plane'``, the normal of face ``f_i`` is not 0;
+    4. float64 sums over these pairs, p and q taken relative to the middle of the target's bounding box (see ia_align_sums);
+    5. the step, solved on the host in float64: ``'point'``: Umeyama / Horn on the pairs (``fit_transform``); ``'plane'``: the
+       minimum-norm solution of the 6x6 (7x7 with ``scale``) normal equations of ``sum ((p + w x p + u + z p - q) . n)^2``, applied as
+       the exact rotation about ``w`` by ``|w|``, the scale ``1 + z`` and the shift ``u`` (a planar target slides nowhere);
+    6. ``M_{k+1} = step M_k``; ``rms_k = sqrt(sum |p - q|^2 / n)`` is the residual before the step.  The loop ends after ``iterations``
+       steps, or earlier when ``|rms_{k-1} - rms_k| <= tol rms_{k-1}`` or ``rms_k <= eps32 extent`` (``converged``); the last pairing
+       follows the last step and gives ``rms``.
+
+    Returns ``{'matrix', 'scale', 'rotation' [3,3], 'translation' [3], 'rms', 'rms_history' (one entry per pairing), 'inliers' (pairs
+    that counted in the last pairing), 'iterations' (steps taken), 'converged'}``.  Fewer than 3 (``'point'``) or 6 (``'plane'``) pairs
+    that count, or an empty target, raise ValueError.  Device tensors run on the kernels (one ``TriangleGrid`` for all iterations,
+    ``grid`` if given; one host synchronisation per iteration for the sums, one more for tau when ``trim < 1``); CPU tensors and NumPy
+    arrays take the NumPy restatement, which is the definition."""
+    if metric not in _ALIGN_MIN:
+        raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
+    if isinstance(source, (tuple, list)) and len(source) == 2 and getattr(source[0], 'ndim', 0) == 2:
+        source = source[0]
+    _mesh_args(verts, faces)
+    if source.ndim != 2 or source.shape[1] != 3:
+        raise ValueError(f'source must be points [N,3] or a (verts, faces) pair, got {tuple(source.shape)}')
+    if not 0.0 < float(trim) <= 1.0:
+        raise ValueError(f'trim must be in (0, 1], got {trim}')
+    if max_dist is not None and not float(max_dist) >= 0:
+        raise ValueError(f'max_dist must be >= 0, got {max_dist}')
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f'iterations must be >= 0, got {iterations}')
+    on_dev = isinstance(verts, torch.Tensor) and verts.is_cuda
+    if isinstance(init, str):
+        if init == 'identity':
+            M0 = np.eye(4)
+        elif init == 'centroid':
+            if not faces.shape[0] or not verts.shape[0]:
+                raise ValueError('align_mesh: the target mesh is empty')
+            M0 = _centroid_init(_np(source), _np(verts), scale)
+        else:
+            raise ValueError(f"init must be 'identity', 'centroid' or a 4x4 matrix, got {init!r}")
+    else:
+        M0 = _matrix44(init)
+    args = (M0, metric, bool(scale), iterations, float(tol), max_dist, float(trim))
+    if on_dev:
+        return _align_device(torch.as_tensor(source), verts, faces, *args, grid)
+    return _align_numpy(_np(source), _np(verts), _np(faces), *args)
 
 
 # ------------------------------------------------------------------ simplification

@@ -3,9 +3,15 @@
 Reads two PLY meshes (``geometry.read_ply``), computes ``geometry.surface_distance(pred, gt)`` (Chamfer and Hausdorff distance, F-score
 at the thresholds, normal consistency with ``--samples``; definitions in that function's docstring; precision is about the predicted
 mesh, recall about the ground truth) and writes the numbers as JSON.  ``--error-ply E.ply`` also writes the predicted mesh coloured by
-the distance of its vertices to the ground truth (black = 0, red = the largest threshold or more).  Runs on the device when there is one."""
+the distance of its vertices to the ground truth (black = 0, red = the largest threshold or more).  ``--align rigid`` (or
+``similarity``) first moves the predicted mesh onto the ground truth with ``geometry.align_mesh`` (``--align-metric``, ``--align-iterations``,
+``--align-trim``, ``--align-init centroid`` set its arguments; the source points are the ``--samples`` area-weighted samples of the
+prediction when given, else its vertices), scores the moved mesh, adds an ``alignment`` block to the JSON and, with ``--save-aligned
+OUT.ply``, writes the moved mesh.  ICP finds the nearest local optimum: a prediction far from the ground truth needs ``--align-init
+centroid`` or a pose from landmarks (``geometry.fit_transform``).  Runs on the device when there is one."""
 import argparse
 import json
+import math
 
 import numpy as np
 import torch
@@ -23,16 +29,69 @@ def error_colors(dist, scale):
     return col
 
 
-def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None):
-    """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance."""
+ALIGN_MODES = ('rigid', 'similarity')
+
+
+def align_prediction(verts, faces, ref_verts, ref_faces, align, samples=None, seed=0, options=None):
+    """Move the mesh onto the reference with ``geometry.align_mesh`` (``align``: 'rigid' or 'similarity'; ``options``: its other
+    arguments): ``(moved vertices, align_mesh's result)``.  The source points are ``samples`` area-weighted samples, else the vertices."""
+    if align not in ALIGN_MODES:
+        raise ValueError(f"align must be None, 'rigid' or 'similarity', got {align!r}")
+    source = verts if samples is None else geometry.sample_surface(verts, faces, samples, seed)[0]
+    fit = geometry.align_mesh(source, ref_verts, ref_faces, scale=align == 'similarity', **dict(options or {}))
+    return geometry.transform_points(verts, fit['matrix']), fit
+
+
+def alignment_block(fit):
+    """The JSON form of an ``align_mesh`` result."""
+    cos = min(1.0, max(-1.0, (float(np.trace(fit['rotation'])) - 1.0) / 2.0))
+    return {'matrix': [[float(x) for x in row] for row in fit['matrix']], 'scale': float(fit['scale']), 'angle_deg': math.degrees(math.acos(cos)),
+            'shift': float(np.linalg.norm(fit['translation'])), 'rms_before': float(fit['rms_history'][0]), 'rms_after': float(fit['rms']),
+            'iterations': int(fit['iterations']), 'converged': bool(fit['converged']), 'inliers': int(fit['inliers'])}
+
+
+def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None, align=None, align_options=None,
+                   save_aligned=None, aligned=None):
+    """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance.
+    ``align``: 'rigid' or 'similarity' moves the mesh onto the reference first (``align_prediction`` with ``align_options``); the moved
+    mesh is scored (and coloured), the result gains ``alignment`` (``alignment_block``), ``save_aligned`` is a PLY path for the moved mesh
+    and ``aligned``, a dict, receives its ``verts`` and the ``matrix``."""
+    alignment = None
+    if align is not None:
+        verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, align_options)
+        alignment = alignment_block(fit)
+        if save_aligned:
+            geometry.write_ply(save_aligned, verts, faces)
+        if aligned is not None:
+            aligned.update(verts=verts, matrix=fit['matrix'])
     res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds)
     res.update(pred_vertices=int(verts.shape[0]), pred_faces=int(faces.shape[0]), gt_vertices=int(ref_verts.shape[0]),
                gt_faces=int(ref_faces.shape[0]))
+    if alignment is not None:
+        res['alignment'] = alignment
     if error_ply:
         dist = geometry.closest_point(verts, ref_verts, ref_faces)['dist']
         scale = res['thresholds'][-1] if res['thresholds'] else 1.0
         geometry.write_ply(error_ply, verts, faces, error_colors(geometry._np(dist), scale))
     return res
+
+
+def add_align_arguments(ap):
+    """The ``--align`` family of flags, shared with extract_geometry."""
+    ap.add_argument('--align', default=None, choices=ALIGN_MODES, help='move the predicted mesh onto the reference first (ICP)')
+    ap.add_argument('--align-metric', default='plane', choices=['point', 'plane'])
+    ap.add_argument('--align-iterations', type=int, default=30)
+    ap.add_argument('--align-trim', type=float, default=1.0, help='share of the closest pairs that count (1: all)')
+    ap.add_argument('--align-init', default='identity', choices=['identity', 'centroid'])
+
+
+def align_options_of(args):
+    return {'metric': args.align_metric, 'iterations': args.align_iterations, 'trim': args.align_trim, 'init': args.align_init}
+
+
+def alignment_summary(a):
+    return (f'aligned: scale {a["scale"]:.6g}, rotation {a["angle_deg"]:.4g} deg, |t| {a["shift"]:.6g}, rms {a["rms_before"]:.6g} -> '
+            f'{a["rms_after"]:.6g} in {a["iterations"]} steps{"" if a["converged"] else " (not converged)"}')
 
 
 def summary(res):
@@ -49,15 +108,22 @@ def main(argv=None):
     ap.add_argument('--thresholds', type=float, nargs='+', default=None, help='F-score thresholds (at most 8); default 0.5, 1, 2 %% of the diagonal')
     ap.add_argument('--error-ply', default=None, help='write the predicted mesh coloured by its distance to the ground truth')
     ap.add_argument('--out', required=True, help='JSON file for the numbers')
+    add_align_arguments(ap)
+    ap.add_argument('--save-aligned', default=None, metavar='OUT.ply', help='with --align: write the moved predicted mesh')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     meshes = []
     for path in (args.pred, args.gt):
         v, f, _ = geometry.read_ply(path)
         meshes += [torch.from_numpy(v).to(args.device), torch.from_numpy(f).to(args.device)]
-    res = compare_meshes(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, error_ply=args.error_ply)
+    if args.save_aligned and not args.align:
+        ap.error('--save-aligned needs --align')
+    extra = {'align': args.align, 'align_options': align_options_of(args), 'save_aligned': args.save_aligned} if args.align else {}
+    res = compare_meshes(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, error_ply=args.error_ply, **extra)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
+    if args.align:
+        print(alignment_summary(res['alignment']))
     print(summary(res))
     return res
 

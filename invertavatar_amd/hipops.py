@@ -1700,6 +1700,52 @@ def distance_stats(dist, thresholds=(), face=None, normals_a=None, normals_b=Non
     return out
 
 
+# ------------------------------------------------------------------ alignment (csrc/align.hip)
+
+def transform_points(points, matrix):
+    """``fp32(M) x`` per point (see ia_transform_points): points float32 [N,3], matrix 4x4 (or 3x4) of floats on the host -> [N,3]."""
+    _f32c(points, 'points')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points must be [N,3], got {tuple(points.shape)}')
+    m12 = (ctypes.c_double * 12)(*[float(matrix[r][c]) for r in range(3) for c in range(4)])
+    n, dev = points.shape[0], points.device
+    out = torch.empty_like(points)
+    with torch.cuda.device(dev), _Timed('transform_points', 18.0 * n, 24.0 * n, f'N={n}'):
+        st = _lib.load().ia_transform_points(_p(points), n, m12, _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_transform_points')
+    return out
+
+
+ALIGN_MODES = {'point': 0, 'plane': 1}
+
+
+def align_sums(src, dst, dist, face, centre, max_dist=float('inf'), metric='point', face_normals=None):
+    """The sums of one alignment iteration (see ia_align_sums): src, dst float32 [N,3], dist float32 [N], face int32 [N], centre three
+    floats, face_normals float32 [Fb,3] for ``metric='plane'`` -> float64 device tensor [20] (point) or [56] (plane)."""
+    if metric not in ALIGN_MODES:
+        raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
+    mode = ALIGN_MODES[metric]
+    for t, what in ((src, 'src'), (dst, 'dst'), (dist, 'dist')):
+        _f32c(t, what)
+    _i32c(face, 'face')
+    n, dev = dist.numel(), dist.device
+    if tuple(src.shape) != (n, 3) or tuple(dst.shape) != (n, 3) or face.numel() != n or not (src.device == dst.device == face.device == dev):
+        raise RuntimeError('src [N,3], dst [N,3], dist [N] and face [N] must match and share a device')
+    fb = 0
+    if mode:
+        _f32c(face_normals, 'face_normals')
+        if face_normals.dim() != 2 or face_normals.shape[1] != 3 or face_normals.device != dev:
+            raise RuntimeError(f'face_normals must be [Fb,3] on the device of the points, got {tuple(face_normals.shape)}')
+        fb = face_normals.shape[0]
+    scratch, nbytes = _scratch('ia_align_sums_scratch_bytes', n, mode, dtype=torch.float64, device=dev)
+    out = torch.empty(56 if mode else 20, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _Timed('align_sums', 0.0, (32.0 + 12.0 * mode) * n, f'N={n} {metric}'):
+        st = _lib.load().ia_align_sums(_p(src), _p(dst), _p(dist), _p(face), n, _p(face_normals) if mode else None, fb, _d3(centre),
+                                       float(max_dist), mode, _p(scratch), nbytes, _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_align_sums')
+    return out
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

@@ -1128,6 +1128,27 @@ int ia_align_sums(const float* src, const float* dst, const float* dist, const i
                   int64_t Fb, const double* h_centre, float h_max_dist, int mode, void* scratch, size_t scratch_bytes, double* out,
                   void* stream);
 
+/*
+ * Generalised winding number of points with respect to a triangle soup (csrc/winding.hip; no counterpart in the reference;
+ * definition: geometry.winding_number and its NumPy restatement): 1 inside a closed outward-wound mesh, 0 outside,
+ * in between for an open one.  Additive entry points: the ABI version is unchanged.
+ *
+ * ia_winding_number: out double [N] for points float32 [N,3] and tris = the F packed triangles of ia_tri_pack (three float4 per
+ * triangle; A.w = 0: skipped).  Per pair, in fp32 with every operation rounded on its own, relative to the query (a = A - p, ...):
+ * omega = 2 atan2f(a . ((b - a) x (c - a)), (((|a| |b|) |c| + (a . b) |c|) + (b . c) |a|) + (c . a) |b|).  The faces are cut into
+ * chunks of `chunk` faces (ia_winding_layout); a chunk's omegas are added in double in face order, the chunk sums in chunk order, and
+ * the total is divided by 4 pi.  The result for a point therefore depends on the point and the mesh alone, not on N, the order of the
+ * points, how a caller cuts them into calls, or the run; no floating-point atomics.  A non-finite point gives NaN; F = 0 or no usable
+ * triangle gives 0.  The cost is N F pairs.  scratch: ia_winding_number_scratch_bytes(N, F) bytes = 8 N ceil(F / chunk), 8-byte
+ * aligned; a caller that must bound it cuts the points into several calls.  N >= 0 with 3 N < 2^31, 0 <= F <= 2^25.
+ * ia_winding_layout (host only): triangles per LDS tile, faces per chunk and points per workgroup of the kernel, the sizes at which
+ * it changes path.
+ */
+int ia_winding_layout(int* h_tile, int* h_chunk, int* h_points);
+int ia_winding_number_scratch_bytes(int64_t N, int64_t F, size_t* h_bytes);
+int ia_winding_number(const float* points, int64_t N, const void* tris, int64_t F, void* scratch, size_t scratch_bytes, double* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh ag
 ``seed%04d_geometry.json`` (``geometry_metrics.compare_meshes``); ``--error-ply`` also writes ``seed%04d_error.ply``, the mesh coloured by
 its distance to the reference; ``--align rigid|similarity`` (with ``--align-metric``, ``--align-iterations``, ``--align-trim``, ``--align-init``,
 as in ``geometry_metrics``) first moves the extracted mesh onto ``REF.ply`` with ``geometry.align_mesh``, prints the scale, the rotation angle,
-|t| and the rms before and after, and scores, colours and (``--mesh-views``) renders the error of the moved mesh.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
+|t| and the rms before and after, and scores, colours and (``--mesh-views``) renders the error of the moved mesh; ``--signed`` and ``--iou RES`` (as in ``geometry_metrics``) add the signed distances (with a
+diverging ``--error-ply``) and the volumetric IoU against ``REF.ply``.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
 clustering; the line per seed then shows the triangle counts before and after), ``--simplify-cells C`` to a grid of C cells along the
 longest axis; ``--simplify-check`` scores the simplified mesh against the full one (``geometry.surface_distance``), prints both directed
 Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  ``--smooth N`` smooths the mesh with N
@@ -99,6 +100,7 @@ def main(argv=None):
     ap.add_argument('--compare', default=None, metavar='REF.ply', help='score the extracted mesh against this mesh (Chamfer, Hausdorff, F-score)')
     ap.add_argument('--error-ply', action='store_true', help='with --compare: also write the mesh coloured by its distance to REF.ply')
     geometry_metrics.add_align_arguments(ap)
+    geometry_metrics.add_sign_arguments(ap)
     grp = ap.add_mutually_exclusive_group()
     grp.add_argument('--simplify', type=int, default=None, metavar='N', help='simplify the mesh to at most N triangles')
     grp.add_argument('--simplify-cells', type=int, default=None, metavar='C', help='simplify on a grid of C cells along the longest axis')
@@ -122,6 +124,8 @@ def main(argv=None):
         ap.error('--smooth-check needs --smooth')
     if args.align and not args.compare:
         ap.error('--align needs --compare')
+    if (args.signed or args.iou is not None) and not args.compare:
+        ap.error('--signed and --iou need --compare')
     smooth = None if args.smooth is None else {'iterations': args.smooth, 'lam': args.smooth_lambda, 'mu': args.smooth_mu,
                                                'weights': args.smooth_weights}
     for seed, w in zip(args.seeds, ws):
@@ -185,6 +189,7 @@ def main(argv=None):
             if args.align:
                 out['aligned'] = {}
                 extra = {'align': args.align, 'align_options': geometry_metrics.align_options_of(args), 'aligned': out['aligned']}
+            extra.update(geometry_metrics.sign_options_of(args))
             out['metrics'] = geometry_metrics.compare_meshes(out['verts'], out['faces'], rv, rf, error_ply=err, **extra)
             with open(os.path.join(args.outdir, f'seed{seed:04d}_geometry.json'), 'w') as fh:
                 json.dump(dict(out['metrics'], **{k: out[k] for k in ('simplify', 'smooth') if k in out}), fh, indent=1)

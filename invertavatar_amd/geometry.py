@@ -37,6 +37,11 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   points (point-to-point or point-to-plane, trimmed), the closed form for given correspondences, and the transform itself.  Device
   tensors go to ``ia_transform_points`` + ``ia_closest_point`` + ``ia_align_sums`` (csrc/align.hip) with the step solved on the host in
   float64; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.
+- ``winding_number`` / ``inside`` / ``signed_distance`` / ``mesh_to_volume`` / ``volume_iou``: which side of a mesh a point is on (the
+  generalised winding number: 1 inside a closed outward-wound mesh, 0 outside, smooth for open meshes), the signed distance made of
+  it and ``closest_point``, a mesh as an SDF / occupancy lattice and the volumetric IoU of two meshes.  Device tensors go to
+  ``ia_winding_number`` (csrc/winding.hip: the all-pairs sum, double sums in a fixed order) + ``ia_closest_point`` +
+  ``ia_volume_components``; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Rasteriser: pixel centres are at integer coordinates, column i and row j of ``RaySampler_zxc`` (ray ``K_res^-1 [i, j, 1]``), so its images
@@ -837,7 +842,8 @@ def _sample_set(verts, faces, samples, seed, points):
     return pts, nrm[idx]
 
 
-def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None):
+def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None,
+                     signed=False):
     """How far surface a is from surface b.  The sample set of each mesh is its vertices (``samples=None``), ``samples`` area-weighted
     points (``sample_surface`` with ``seed`` for a and ``seed + 1`` for b) or the points given (``points_a`` / ``points_b``).  With
     ``d_ab`` the exact distances of a's samples to mesh b and ``d_ba`` those of b's samples to mesh a (``closest_point``; non-finite
@@ -850,7 +856,11 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
       ``fscore[k] = 2 P R / (P + R)`` (0 when ``P + R = 0``);
     - ``normal_consistency``: mean over both directions of ``|n . n'|`` between the normal of the sample's own face and the normal of
       the closest face of the other mesh; it needs samples that know their face, so it is None unless ``samples`` is given;
-    - ``n_a``, ``n_b``: the numbers of samples.
+    - ``n_a``, ``n_b``: the numbers of samples;
+    - with ``signed=True`` also ``mean_signed_ab`` / ``mean_signed_ba``: the mean of ``signed_distance`` of the samples of one mesh
+      against the other (negative inside; positive ``mean_signed_ab``: a lies outside b, it is inflated against it), and
+      ``inside_share_ab`` / ``inside_share_ba``: the share of those samples whose winding number is at least 0.5.  Both are over the
+      samples with a finite distance (NaN when there is none).  This costs n_a F_b + n_b F_a pairs (``winding_number``).
 
     Device meshes run on the kernels (one ``TriangleGrid`` per mesh, ia_distance_stats for the sums); CPU tensors and NumPy arrays take
     the NumPy restatements."""
@@ -875,9 +885,11 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     if on_dev:
         from . import hipops
         grid_a, grid_b = TriangleGrid(verts_a, faces_a), TriangleGrid(verts_b, faces_b)
-        stats = []
+        stats, sides = [], []
         for pts, nrm, grid, fn in ((pa, na, grid_b, fn_b), (pb, nb, grid_a, fn_a)):
             r = grid.closest(pts)
+            if signed:
+                sides.append((r['dist'], _winding_device(pts, None, None, grid)))
             if nrm is not None:
                 s = hipops.distance_stats(r['dist'], thresholds, r['face'].int(), nrm.float().contiguous(), fn.float().contiguous())
             else:
@@ -885,9 +897,11 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
             stats.append(s)
         s_ab, s_ba = torch.stack(stats).cpu().numpy()
     else:
-        out = []
+        out, sides = [], []
         for pts, nrm, v, f, fn in ((pa, na, verts_b, faces_b, fn_b), (pb, nb, verts_a, faces_a, fn_a)):
             r = closest_point(_np(pts), _np(v), _np(f))
+            if signed:
+                sides.append((r['dist'], _winding_numpy(_np(pts), _np(v), _np(f))[0]))
             out.append(_stats_numpy(r['dist'], thresholds, *((r['face'], _np(nrm), _np(fn)) if nrm is not None else ())))
         s_ab, s_ba = out
 
@@ -906,6 +920,13 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
            'skipped_ab': int(s_ab[5]), 'skipped_ba': int(s_ba[5])}
     if na is not None and nb is not None and s_ab[0] + s_ba[0] > 0:
         res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
+    if signed:
+        for tag, (dist, w) in zip(('ab', 'ba'), sides):
+            d, w = _np(dist).astype(np.float64).reshape(-1), _np(w).reshape(-1)
+            ok = np.isfinite(d)
+            neg = w[ok] >= 0.5
+            res[f'mean_signed_{tag}'] = float(np.where(neg, -d[ok], d[ok]).mean()) if ok.any() else float('nan')
+            res[f'inside_share_{tag}'] = float(neg.mean()) if ok.any() else float('nan')
     return res
 
 
@@ -1227,6 +1248,275 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
     if on_dev:
         return _align_device(torch.as_tensor(source), verts, faces, *args, grid)
     return _align_numpy(_np(source), _np(verts), _np(faces), *args)
+
+
+# ------------------------------------------------------------------ winding number, signed distance, mesh -> volume
+
+WINDING_CHUNK = 2048         # faces per partial sum (csrc/winding.hip kChunk = hipops.WINDING_CHUNK): part of the results
+_SIGN_MODES = ('auto', 'regions', 'winding')
+
+
+def _solid_angle(p, A, B, C, dtype):
+    """The per-pair function (csrc/winding.hip solid_angle) in ``dtype`` on broadcastable [..., 3] arrays: the signed solid angle of
+    triangle A B C seen from p, ``2 atan2(a . ((b - a) x (c - a)), (((|a| |b|) |c| + (a . b) |c|) + (b . c) |a|) + (c . a) |b|)`` in
+    coordinates relative to p; every operation rounded on its own, dot products ``(x + y) + z``."""
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        a, b, c = np.broadcast_arrays(A - p, B - p, C - p)
+        num = _dot3(a, _cross3(b - a, c - a))
+        la, lb, lc = np.sqrt(_dot3(a, a)), np.sqrt(_dot3(b, b)), np.sqrt(_dot3(c, c))
+        den = (((la * lb) * lc + _dot3(a, b) * lc) + _dot3(b, c) * la) + _dot3(c, a) * lb
+        return (dtype(2) * np.arctan2(num, den)).astype(dtype)
+
+
+def _winding_numpy(points, verts, faces, dtype=np.float64, pairs=1 << 20):
+    """NumPy restatement of ia_winding_number with the per-pair function in ``dtype``: ``(w float64 [N], A float64 [N])`` with
+    ``w = sum omega / 4 pi`` and ``A = sum |omega| / 4 pi`` (the size of the terms, for tolerances).  The sum has the kernel's
+    association: chunks of ``WINDING_CHUNK`` faces of the face list as given, a chunk added in double in face order (``cumsum``), the
+    chunk sums added in chunk order.  A face with an index out of range or a non-finite vertex is left out (it adds nothing); a
+    non-finite point gives NaN; ``pairs`` point-triangle pairs are evaluated at a time."""
+    p = np.asarray(points, dtype=F32).reshape(-1, 3).astype(dtype)
+    v = np.asarray(verts, dtype=F32).reshape(-1, 3).astype(dtype)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    n = p.shape[0]
+    in_range = ((f >= 0) & (f < v.shape[0])).all(1)
+    tri = v[np.where(in_range[:, None], f, 0)] if v.shape[0] else np.zeros((f.shape[0], 3, 3), dtype=dtype)
+    usable = in_range & np.isfinite(tri).all((1, 2))
+    total, size = np.zeros(n), np.zeros(n)
+    ok = np.isfinite(p).all(1)
+    rows = np.flatnonzero(ok)
+    for c0 in range(0, f.shape[0], WINDING_CHUNK):
+        t = tri[c0:c0 + WINDING_CHUNK][usable[c0:c0 + WINDING_CHUNK]]
+        if not t.shape[0]:
+            continue
+        step = max(1, pairs // t.shape[0])
+        for s in range(0, rows.size, step):
+            r = rows[s:s + step]
+            om = _solid_angle(p[r, None, :], t[None, :, 0], t[None, :, 1], t[None, :, 2], dtype).astype(np.float64)
+            total[r] += np.cumsum(om, axis=1)[:, -1]                               # cumsum adds in face order
+            size[r] += np.cumsum(np.abs(om), axis=1)[:, -1]
+    w, big = total / (4.0 * np.pi), size / (4.0 * np.pi)
+    w[~ok] = np.nan
+    big[~ok] = np.nan
+    return w, big
+
+
+def _is_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _winding_device(points, verts, faces, grid):
+    from . import hipops
+    if grid is not None:
+        tris, dev = grid.tris, grid.verts.device
+    else:
+        dev = verts.device
+        tris = hipops.tri_pack(verts.detach().float().contiguous(), faces.to(device=dev, dtype=torch.int32).contiguous())
+    pts = torch.as_tensor(points).detach().to(dev).float().reshape(-1, 3).contiguous()
+    return hipops.winding_number(pts, tris)
+
+
+def winding_number(points, verts, faces, grid=None):
+    """Generalised winding number of points [..., 3] with respect to the triangle soup (verts float32 [V,3], faces [F,3]): float64
+    [...].  ``w(p) = (1 / 4 pi) sum_f omega_f(p)`` with ``omega_f`` the signed solid angle of triangle f seen from p (``_solid_angle``,
+    float32): 1 inside a closed mesh wound outward (the winding of ``marching_cubes``), 0 outside, k where k such surfaces nest, and a
+    smooth value in between for an open mesh (a head scan open at the neck: above 0.5 well inside, below it outside).  A triangle
+    without area contributes 0, one with an index out of range or a non-finite vertex is ignored; a non-finite point gives NaN; a mesh
+    without usable triangles 0.  The terms are added in double in a fixed order (``_winding_numpy``), so a point's value does not depend
+    on the other points of the call.  The cost is N F pairs.  Device tensors run on ia_winding_number (``grid``: a ``TriangleGrid`` of
+    this mesh whose packed triangles are reused); CPU tensors and NumPy arrays take the NumPy restatement (float64 per pair)."""
+    _mesh_args(verts, faces)
+    lead = tuple(points.shape[:-1])
+    if _is_device(verts):
+        return _winding_device(points, verts, faces, grid).reshape(lead)
+    w, _ = _winding_numpy(_np(points), _np(verts), _np(faces))
+    return _as_out(w.reshape(lead), points, np.float64)
+
+
+def inside(points, verts, faces, threshold=0.5):
+    """bool [...]: ``winding_number(points) >= threshold`` (a non-finite point is not inside)."""
+    return winding_number(points, verts, faces) >= threshold
+
+
+def signed_distance(points, verts, faces, grid=None, threshold=0.5):
+    """Signed distance of points to a mesh: ``{'sdf', 'dist', 'face', 'point', 'winding'}``.  ``dist``, ``face`` and ``point`` are the
+    results of ``closest_point`` (the same bits), ``winding`` (float64) is ``winding_number`` and ``sdf`` is ``-dist`` where
+    ``winding >= threshold``, else ``+dist``: negative inside.  ``grid``: a ``TriangleGrid`` of the mesh (device), used by both."""
+    _mesh_args(verts, faces)
+    if _is_device(verts) and grid is None:
+        grid = TriangleGrid(verts, faces)
+    r = closest_point(points, verts, faces, grid=grid)
+    w = winding_number(points, verts, faces, grid=grid).reshape(r['dist'].shape)
+    neg = w >= threshold
+    sdf = torch.where(neg, -r['dist'], r['dist']) if isinstance(neg, torch.Tensor) else np.where(neg, -r['dist'], r['dist'])
+    return {'sdf': sdf, 'dist': r['dist'], 'face': r['face'], 'point': r['point'], 'winding': w}
+
+
+def _finite_box(*vert_sets):
+    """(lo, hi) float64 [3] of the finite rows of the vertex arrays given, or None when there is none."""
+    rows = []
+    for v in vert_sets:
+        if _is_device(v):
+            x = v.detach().float()
+            x = x[torch.isfinite(x).all(1)]
+            if x.shape[0]:
+                rows.append(torch.stack([x.amin(0), x.amax(0)]).cpu().numpy().astype(np.float64))
+        else:
+            x = np.asarray(_np(v), dtype=np.float64).reshape(-1, 3)
+            x = x[np.isfinite(x).all(1)]
+            if x.shape[0]:
+                rows.append(np.stack([x.min(0), x.max(0)]))
+    if not rows:
+        return None
+    box = np.stack(rows)
+    return box[:, 0].min(0), box[:, 1].max(0)
+
+
+def _volume_lattice(box, resolution, origin, spacing, padding):
+    """The lattice of ``mesh_to_volume``: ``((nx, ny, nz), origin, spacing)``, point (i, j, k) at ``origin + index * spacing``."""
+    padding = int(padding)
+    if padding < 0:
+        raise ValueError(f'padding must be >= 0, got {padding}')
+    if (origin is None) != (spacing is None):
+        raise ValueError('origin and spacing are given together or not at all')
+    if origin is not None:
+        dims, org, spc = _res3(resolution), _vec3(origin), _vec3(spacing)
+        if not all(np.isfinite(s) and s > 0 for s in spc) or not all(np.isfinite(o) for o in org):
+            raise ValueError(f'origin must be finite and spacing positive, got {origin} and {spacing}')
+        return dims, org, spc
+    if box is None or not (box[1] - box[0]).max() > 0:
+        raise ValueError('mesh_to_volume: the mesh has no extent; give origin and spacing')
+    lo, hi = box
+    size = hi - lo
+    if np.isscalar(resolution):
+        cells = int(resolution) - 1 - 2 * padding
+        if cells < 1:
+            raise ValueError(f'resolution {resolution} leaves no cell between {padding} padding cells on each side')
+        h = float(size.max()) / cells
+        dims = tuple(int(resolution) if a == int(np.argmax(size)) else int(np.ceil(size[a] / h - 1e-9)) + 1 + 2 * padding for a in range(3))
+        dims = tuple(max(d, 2) for d in dims)
+        mid = (lo + hi) / 2
+        return dims, tuple(float(mid[a] - (dims[a] - 1) * h / 2) for a in range(3)), (h,) * 3
+    dims = _res3(resolution)
+    spc = []
+    for a in range(3):
+        cells = dims[a] - 1 - 2 * padding
+        if cells < 1:
+            raise ValueError(f'resolution {resolution} leaves no cell between {padding} padding cells on each side')
+        spc.append(float(size[a]) / cells if size[a] > 0 else float(size.max()) / cells)
+    mid = (lo + hi) / 2
+    return dims, tuple(float(mid[a] - (dims[a] - 1) * spc[a] / 2) for a in range(3)), tuple(spc)
+
+
+def _lattice_axes(dims, origin, spacing):
+    """fp32 coordinates per axis: ``origin + i * spacing``, each operation rounded to fp32 (the vertices of ``marching_cubes``)."""
+    return [(F32(origin[a]) + np.arange(dims[a], dtype=F32) * F32(spacing[a])).astype(F32) for a in range(3)]
+
+
+def _mesh_is_closed(verts, faces):
+    try:
+        info = MeshAdjacency(verts, faces).info
+    except ValueError:
+        return False
+    return int(info['boundary_edges']) == 0 and int(info['nonmanifold_edges']) == 0
+
+
+def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=2, sign='auto', threshold=0.5):
+    """A triangle mesh as a signed distance lattice: ``{'sdf' float32 [nx,ny,nz] (negative inside), 'inside' bool [nx,ny,nz],
+    'origin', 'spacing', 'info'}``.  The lattice is that of ``marching_cubes``: point (i, j, k) at ``origin + index * spacing`` in fp32,
+    volumes indexed [i, j, k] with z fastest, so ``marching_cubes(-sdf, 0, origin, spacing)`` remeshes the surface.  With ``origin``
+    and ``spacing`` None the lattice is fitted to the box of the finite vertices: an int ``resolution`` gives cubic cells with
+    ``resolution`` points along the longest axis, the box enlarged by ``padding`` cells on every side; a triple gives that many points
+    per axis, each axis with its own spacing.
+
+    The magnitude is ``closest_point`` at every lattice point.  The sign is the winding number against ``threshold``:
+
+    - ``sign='winding'`` evaluates it at every lattice point: exact for any soup, robust for open meshes, N F pairs;
+    - ``sign='regions'``, for closed meshes: with h the largest spacing and ``tau = h / 2 + 64 eps32 extent`` (the slack of the
+      closest-point search), two 6-neighbours that are both farther than tau from the mesh have no surface between them, so the
+      winding number is constant on each 6-connected component of ``{dist > tau}`` (``components``).  It is evaluated once per
+      component, at its smallest-index point, and at every point of the band ``{dist <= tau}``;
+    - ``sign='auto'``: ``'regions'`` when ``MeshAdjacency(...).info`` has no boundary and no non-manifold edge, else ``'winding'``.
+      (The test is on edges, not on orientation: the faces of a closed mesh must be wound consistently.)
+
+    ``info``: ``{'mode', 'regions', 'band', 'evaluations'}``: the mode taken, the number of components, the points of the band and
+    the number of winding-number evaluations.  Device tensors run on the kernels; CPU tensors and NumPy arrays take the restatements."""
+    _mesh_args(verts, faces)
+    if sign not in _SIGN_MODES:
+        raise ValueError(f'sign must be one of {_SIGN_MODES}, got {sign!r}')
+    on_dev = _is_device(verts)
+    box = _finite_box(verts)
+    dims, org, spc = _volume_lattice(box, resolution, origin, spacing, padding)
+    n = dims[0] * dims[1] * dims[2]
+    if n >= 1 << 31:
+        raise ValueError(f'a lattice of {dims} has 2^31 points or more')
+    axes = _lattice_axes(dims, org, spc)
+    mode = sign if sign != 'auto' else ('regions' if _mesh_is_closed(verts, faces) else 'winding')
+    extent = max([float(np.abs(ax).max()) for ax in axes] + ([float(np.abs(box[0]).max()), float(np.abs(box[1]).max())] if box else []))
+    tau = float(F32(max(spc) / 2 + 64 * EPS32 * extent))
+    if on_dev:
+        dev = verts.device
+        grid = TriangleGrid(verts, faces)
+        pts = torch.stack(torch.meshgrid(*[torch.from_numpy(ax).to(dev) for ax in axes], indexing='ij'), -1).reshape(-1, 3).contiguous()
+        dist = grid.closest(pts)['dist']
+
+        def wind(idx):
+            return _winding_device(pts if idx is None else pts[idx], None, None, grid) >= threshold
+    else:
+        grid = None
+        v_np, f_np = _np(verts), _np(faces)
+        pts = np.ascontiguousarray(np.stack(np.meshgrid(*axes, indexing='ij'), -1).reshape(-1, 3))
+        dist = _closest_numpy(pts, v_np, f_np)[0].astype(F32)
+
+        def wind(idx):
+            return _winding_numpy(pts if idx is None else pts[idx], v_np, f_np)[0] >= threshold
+    info = {'mode': mode, 'regions': 0, 'band': n, 'evaluations': n}
+    if mode == 'winding':
+        neg = wind(None)
+    else:
+        labels, stats = components(dist.reshape(dims), tau, connectivity=6)
+        k = int(stats.shape[0])
+        lab = labels.reshape(-1)
+        if on_dev:
+            band = torch.nonzero(lab == 0).reshape(-1)
+            idx = torch.cat([stats[:, 1].long(), band])
+            flag = wind(idx)
+            neg = torch.cat([torch.zeros(1, dtype=torch.bool, device=dev), flag[:k]])[lab.long()]
+            neg[band] = flag[k:]
+        else:
+            lab, st = _np(lab), _np(stats)
+            band = np.flatnonzero(lab == 0)
+            idx = np.concatenate([st[:, 1].astype(np.int64), band])
+            flag = wind(idx)
+            neg = np.concatenate([[False], flag[:k]])[lab]
+            neg[band] = flag[k:]
+        info.update(regions=k, band=int(band.shape[0]), evaluations=int(idx.shape[0]))
+    if on_dev:
+        sdf = torch.where(neg, -dist, dist).reshape(dims)
+        neg = neg.reshape(dims)
+    else:
+        sdf = _as_out(np.where(neg, -dist, dist).reshape(dims), verts)
+        neg = _as_out(neg.reshape(dims), verts, bool)
+    return {'sdf': sdf, 'inside': neg, 'origin': org, 'spacing': spc, 'info': info}
+
+
+def volume_iou(verts_a, faces_a, verts_b, faces_b, resolution=128, **kwargs):
+    """Volumetric intersection over union of two meshes: both go through ``mesh_to_volume`` (``kwargs``: its arguments) on ONE lattice
+    over the box of the finite vertices of both (or on the ``origin`` / ``spacing`` given).  Returns ``{'iou', 'intersection', 'union',
+    'volume_a', 'volume_b'}``: numbers of inside lattice points times the cell volume, ``iou = intersection / union`` (NaN when both
+    are empty), plus ``'resolution'`` (points per axis), ``'spacing'`` and ``'origin'``."""
+    _mesh_args(verts_a, faces_a)
+    _mesh_args(verts_b, faces_b)
+    if _is_device(verts_a) != _is_device(verts_b):
+        raise ValueError('volume_iou: both meshes must be on the device or both on the host')
+    kwargs = dict(kwargs)
+    dims, org, spc = _volume_lattice(_finite_box(verts_a, verts_b), resolution, kwargs.pop('origin', None), kwargs.pop('spacing', None),
+                                     kwargs.get('padding', 2))
+    ia = mesh_to_volume(verts_a, faces_a, dims, origin=org, spacing=spc, **kwargs)['inside']
+    ib = mesh_to_volume(verts_b, faces_b, dims, origin=org, spacing=spc, **kwargs)['inside']
+    cell = float(spc[0]) * float(spc[1]) * float(spc[2])
+    both, either, na, nb = (int(x.sum()) for x in (ia & ib, ia | ib, ia, ib))
+    return {'iou': both / either if either else float('nan'), 'intersection': both * cell, 'union': either * cell, 'volume_a': na * cell,
+            'volume_b': nb * cell, 'resolution': list(dims), 'spacing': list(spc), 'origin': list(org)}
 
 
 # ------------------------------------------------------------------ simplification

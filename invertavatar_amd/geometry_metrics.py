@@ -8,7 +8,11 @@ the distance of its vertices to the ground truth (black = 0, red = the largest t
 ``--align-trim``, ``--align-init centroid`` set its arguments; the source points are the ``--samples`` area-weighted samples of the
 prediction when given, else its vertices), scores the moved mesh, adds an ``alignment`` block to the JSON and, with ``--save-aligned
 OUT.ply``, writes the moved mesh.  ICP finds the nearest local optimum: a prediction far from the ground truth needs ``--align-init
-centroid`` or a pose from landmarks (``geometry.fit_transform``).  Runs on the device when there is one."""
+centroid`` or a pose from landmarks (``geometry.fit_transform``).  ``--signed`` adds the signed numbers of
+``surface_distance(signed=True)`` (mean signed distance and inside share per direction: is the prediction inflated or deflated?) and
+colours ``--error-ply`` with a diverging map (blue inside the ground truth, red outside, white on it).  ``--iou RES`` adds a
+``volume_iou`` block: the volumetric IoU of the two meshes on a lattice of ``RES`` points along the longest axis.  Without these flags
+the outputs are what they were.  Runs on the device when there is one."""
 import argparse
 import json
 import math
@@ -26,6 +30,20 @@ def error_colors(dist, scale):
     col = np.zeros((d.size, 3), dtype=np.uint8)
     col[:, 0] = np.round(255 * x)
     col[~np.isfinite(d)] = (0, 0, 255)
+    return col
+
+
+def signed_error_colors(sdf, scale):
+    """uint8 [V,3], diverging: white at signed distance 0, to red at ``+scale`` or more (outside the reference) and to blue at
+    ``-scale`` or less (inside it); a non-finite distance is green."""
+    d = np.asarray(sdf, dtype=np.float64)
+    x = np.clip(np.where(np.isfinite(d), d, 0.0) / max(float(scale), 1e-30), -1.0, 1.0)
+    fade = np.round(255 * (1.0 - np.abs(x)))
+    col = np.empty((d.size, 3), dtype=np.uint8)
+    col[:, 0] = np.where(x >= 0, 255, fade)
+    col[:, 1] = fade
+    col[:, 2] = np.where(x <= 0, 255, fade)
+    col[~np.isfinite(d)] = (0, 255, 0)
     return col
 
 
@@ -51,11 +69,13 @@ def alignment_block(fit):
 
 
 def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None, align=None, align_options=None,
-                   save_aligned=None, aligned=None):
+                   save_aligned=None, aligned=None, signed=False, iou=None):
     """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance.
     ``align``: 'rigid' or 'similarity' moves the mesh onto the reference first (``align_prediction`` with ``align_options``); the moved
     mesh is scored (and coloured), the result gains ``alignment`` (``alignment_block``), ``save_aligned`` is a PLY path for the moved mesh
-    and ``aligned``, a dict, receives its ``verts`` and the ``matrix``."""
+    and ``aligned``, a dict, receives its ``verts`` and the ``matrix``.  ``signed``: the signed keys of ``surface_distance`` and a
+    diverging ``error_ply`` (``signed_error_colors``); ``iou``: a lattice resolution, adds ``volume_iou`` of the (moved) mesh and the
+    reference."""
     alignment = None
     if align is not None:
         verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, align_options)
@@ -64,16 +84,34 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
             geometry.write_ply(save_aligned, verts, faces)
         if aligned is not None:
             aligned.update(verts=verts, matrix=fit['matrix'])
-    res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds)
+    res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds,
+                                    **({'signed': True} if signed else {}))
     res.update(pred_vertices=int(verts.shape[0]), pred_faces=int(faces.shape[0]), gt_vertices=int(ref_verts.shape[0]),
                gt_faces=int(ref_faces.shape[0]))
     if alignment is not None:
         res['alignment'] = alignment
+    if iou is not None:
+        res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou))
     if error_ply:
-        dist = geometry.closest_point(verts, ref_verts, ref_faces)['dist']
         scale = res['thresholds'][-1] if res['thresholds'] else 1.0
-        geometry.write_ply(error_ply, verts, faces, error_colors(geometry._np(dist), scale))
+        if signed:
+            sdf = geometry.signed_distance(verts, ref_verts, ref_faces)['sdf']
+            geometry.write_ply(error_ply, verts, faces, signed_error_colors(geometry._np(sdf), scale))
+        else:
+            dist = geometry.closest_point(verts, ref_verts, ref_faces)['dist']
+            geometry.write_ply(error_ply, verts, faces, error_colors(geometry._np(dist), scale))
     return res
+
+
+def add_sign_arguments(ap):
+    """``--signed`` and ``--iou``, shared with extract_geometry."""
+    ap.add_argument('--signed', action='store_true', help='add signed distances (negative inside the reference); diverging --error-ply')
+    ap.add_argument('--iou', type=int, default=None, metavar='RES', help='add the volumetric IoU on a lattice of RES points along the longest axis')
+
+
+def sign_options_of(args):
+    """The keyword arguments of ``compare_meshes`` for ``--signed`` / ``--iou``; empty without them."""
+    return {**({'signed': True} if args.signed else {}), **({'iou': args.iou} if args.iou is not None else {})}
 
 
 def add_align_arguments(ap):
@@ -96,7 +134,13 @@ def alignment_summary(a):
 
 def summary(res):
     f = ', '.join(f'F@{t:.4g} = {v:.4f}' for t, v in zip(res['thresholds'], res['fscore']))
-    return f'chamfer {res["chamfer"]:.6g}, hausdorff {res["hausdorff"]:.6g}, {f}'
+    line = f'chamfer {res["chamfer"]:.6g}, hausdorff {res["hausdorff"]:.6g}, {f}'
+    if 'mean_signed_ab' in res:
+        line += (f', signed mean {res["mean_signed_ab"]:.6g} / {res["mean_signed_ba"]:.6g}, inside share {res["inside_share_ab"]:.4f} / '
+                 f'{res["inside_share_ba"]:.4f}')
+    if 'volume_iou' in res:
+        line += f', volume IoU {res["volume_iou"]["iou"]:.4f} at {res["volume_iou"]["resolution"]}'
+    return line
 
 
 def main(argv=None):
@@ -109,6 +153,7 @@ def main(argv=None):
     ap.add_argument('--error-ply', default=None, help='write the predicted mesh coloured by its distance to the ground truth')
     ap.add_argument('--out', required=True, help='JSON file for the numbers')
     add_align_arguments(ap)
+    add_sign_arguments(ap)
     ap.add_argument('--save-aligned', default=None, metavar='OUT.ply', help='with --align: write the moved predicted mesh')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
@@ -119,6 +164,7 @@ def main(argv=None):
     if args.save_aligned and not args.align:
         ap.error('--save-aligned needs --align')
     extra = {'align': args.align, 'align_options': align_options_of(args), 'save_aligned': args.save_aligned} if args.align else {}
+    extra.update(sign_options_of(args))
     res = compare_meshes(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, error_ply=args.error_ply, **extra)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)

@@ -1746,6 +1746,47 @@ def align_sums(src, dst, dist, face, centre, max_dist=float('inf'), metric='poin
     return out
 
 
+# ------------------------------------------------------------------ winding number (csrc/winding.hip)
+
+WINDING_TILE = 256           # triangles per LDS tile (csrc/winding.hip kTile)
+WINDING_CHUNK = 2048         # faces per partial sum (kChunk): part of the results, geometry._winding_numpy uses the same
+WINDING_POINTS = 512         # points per workgroup (kPoints)
+WINDING_WORKSPACE = 256 << 20
+
+
+def winding_layout():
+    """(tile, chunk, points per workgroup) as the library reports them (ia_winding_layout; host only)."""
+    vals = [ctypes.c_int(0) for _ in range(3)]
+    _lib.check(_lib.load().ia_winding_layout(*[ctypes.byref(v) for v in vals]), 'ia_winding_layout')
+    return tuple(v.value for v in vals)
+
+
+def winding_number(points, tris, workspace_bytes=WINDING_WORKSPACE):
+    """Generalised winding number per point (see ia_winding_number): points float32 [N,3], tris from ``tri_pack`` -> float64 [N].  The
+    partial sums take 8 N ceil(F / WINDING_CHUNK) bytes; the points are cut into slabs so that one call's workspace stays within
+    ``workspace_bytes`` (at least one point per slab).  A point's result does not depend on the slab it is in."""
+    _f32c(points, 'points')
+    _f32c(tris, 'tris')
+    if points.dim() != 2 or points.shape[1] != 3 or points.device != tris.device:
+        raise RuntimeError(f'points must be [N,3] on the device of the triangles, got {tuple(points.shape)} on {points.device}')
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 4):
+        raise RuntimeError(f'tris must be the [F,3,4] tensor of tri_pack, got {tuple(tris.shape)}')
+    n, f, dev = points.shape[0], tris.shape[0], points.device
+    chunks = -(-f // WINDING_CHUNK)
+    slab = n if chunks == 0 else max(1, min(n, int(workspace_bytes) // (8 * chunks)))
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    scratch = torch.empty(max(slab * chunks, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _Timed('winding_number', 75.0 * n * f, 48.0 * f * -(-n // WINDING_POINTS) + 16.0 * n * chunks,
+                                        f'N={n} F={f} slab={slab}'):
+        for s in range(0, n, max(slab, 1)):
+            m = min(slab, n - s)
+            st = lib.ia_winding_number(_p(points[s:s + m]), m, _p(tris), f, _p(scratch), scratch.numel() * 8, _p(out[s:s + m]),
+                                       _lib.stream_ptr(dev))
+            _lib.check(st, 'ia_winding_number')
+    return out
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

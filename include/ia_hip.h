@@ -1149,6 +1149,46 @@ int ia_winding_number_scratch_bytes(int64_t N, int64_t F, size_t* h_bytes);
 int ia_winding_number(const float* points, int64_t N, const void* tris, int64_t F, void* scratch, size_t scratch_bytes, double* out,
                       void* stream);
 
+/*
+ * Fast winding numbers: an implicit cluster tree over the triangles with a far-field expansion per node (csrc/winding_tree.hip; no
+ * counterpart in the reference; definition: geometry.WindingTree and its NumPy restatement).  ia_winding_number stays
+ * the exact sum these are held to.  Additive entry points: the ABI version is unchanged.
+ *
+ * ia_winding_tree_layout (host only): faces per leaf L, children per upper node B, floats per node row (20 = 5 float4) and the largest
+ * number of levels.  L and B are part of the results.
+ * ia_winding_tree_face_keys: keys int32 [F] of the packed triangles of ia_tri_pack: the 30-bit Morton key of the centroid, 10 bits per
+ * axis (x lowest), cell = clamp(floor((c - lo) * scale), 0, 1023) in fp32 with c = ((A + B) + C) * fp32(1 / 3); 2^30 for a triangle
+ * with A.w = 0.  h_lo: the low corner of the box of the finite vertices, h_scale = fp32(1024) / (its longest side), 0 without extent.
+ * ia_winding_tree_point_keys: the same key for points float32 [N,3]; 2^30 for a non-finite point.  (Sorting queries by it brings
+ * neighbours into one wave; it changes no result.)
+ * ia_winding_tree_gather: sorted[s] = tris[order[s]] for order int32 [F], the stable ascending sort of the face keys (the caller's).
+ * ia_winding_tree_plan (host only): for F_usable faces (keys below 2^30) the number of levels, the nodes per level (h_counts: int
+ * [max levels], leaves first: ceil(F_usable / L), then ceil(previous / B) down to 1), their total and the bytes of scratch that
+ * ia_winding_tree_nodes needs.  F_usable = 0: no level, no node.
+ * ia_winding_tree_nodes: nodes float32 [n_nodes, 20], level by level with the leaves first: (c.x, c.y, c.z, r) (D.x, D.y, D.z, A)
+ * (Q00 Q01 Q02 Q10) (Q11 Q12 Q20 Q21) (Q22, 0, 0, 0) with A = sum a_t, D = sum a_t n_t, c = sum a_t c_t / A (the mean of the centroids
+ * c_t when A = 0), Q = sum (c_t - c) (x) a_t n_t, r = the largest distance of a vertex from c.  Leaf i holds sorted faces [i L,
+ * min((i + 1) L, F_usable)) and is summed in double in face order; an upper node is formed in double from its children in child order
+ * (Q = sum Q_k + (c_k - c) (x) D_k, r = max |c_k - c| + r_k); every entry is rounded to fp32 once.  No atomics: bit-equal run to run.
+ * scratch: the double rows, 8-byte aligned.
+ * ia_winding_tree_query: out double [N].  Per point q, depth first from the root, children in index order; at a node, in fp32 with
+ * every operation rounded on its own, x = c - q, d2 = (x.x^2 + x.y^2) + x.z^2, far = d2 > (beta r)(beta r).  A far node adds
+ * ((D . x + tr Q) - 3 (x^T Q x) / d2) / (d2 sqrt(d2)), a near leaf the solid angles of ia_winding_number of its faces in sorted order,
+ * a near upper node is descended.  Terms are fp32, the running sum is double in visiting order, out = sum / 4 pi; NaN for a non-finite
+ * point.  A pure function of point, mesh and beta: independent of N, the order of the points and the run.  beta > 1, or +inf (never
+ * far: the exact terms).  bound (double [N], or NULL): sum over the far nodes of 3 A r^2 / (4 pi (d - r)^4), which bounds the
+ * truncation error.  counts (int32 [N,2], or NULL): far terms and exact pairs of the point.
+ */
+int ia_winding_tree_layout(int* h_leaf, int* h_branch, int* h_row_floats, int* h_max_levels);
+int ia_winding_tree_plan(int64_t F_usable, int* h_levels, int* h_counts, int64_t* h_nodes, size_t* h_scratch_bytes);
+int ia_winding_tree_face_keys(const void* tris, int64_t F, const float* h_lo, float h_scale, int* keys, void* stream);
+int ia_winding_tree_point_keys(const float* points, int64_t N, const float* h_lo, float h_scale, int* keys, void* stream);
+int ia_winding_tree_gather(const void* tris, int64_t F, const int* order, void* sorted, void* stream);
+int ia_winding_tree_nodes(const void* sorted, int64_t F_usable, void* scratch, size_t scratch_bytes, void* nodes, int64_t n_nodes,
+                          void* stream);
+int ia_winding_tree_query(const float* points, int64_t N, const void* sorted, int64_t F_usable, const void* nodes, int64_t n_nodes,
+                          float beta, double* out, double* bound, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

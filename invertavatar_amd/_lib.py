@@ -167,6 +167,13 @@ _SIGNATURES = {
     'ia_winding_layout': [ctypes.POINTER(c_int)] * 3,
     'ia_winding_number_scratch_bytes': [c_int64, c_int64, ctypes.POINTER(ctypes.c_size_t)],
     'ia_winding_number': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_winding_tree_layout': [ctypes.POINTER(c_int)] * 4,
+    'ia_winding_tree_plan': [c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int), _i64p, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_winding_tree_face_keys': [c_void_p, c_int64, _f32p, c_float, c_void_p, c_void_p],
+    'ia_winding_tree_point_keys': [c_void_p, c_int64, _f32p, c_float, c_void_p, c_void_p],
+    'ia_winding_tree_gather': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    'ia_winding_tree_nodes': [c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_int64, c_void_p],
+    'ia_winding_tree_query': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -103,6 +103,16 @@ template <class T> __device__ __forceinline__ Vec3<T> cross(Vec3<T> a, Vec3<T> b
 }
 template <class T> __device__ __forceinline__ bool finite3(Vec3<T> a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
+// Signed solid angle of triangle A B C seen from p (the per-pair function of the winding number, winding.hip): relative to the query,
+// the numerator from the edges; every operation rounded on its own.  A triangle without area gives atan2f(0, den >= 0) = 0.
+__device__ __forceinline__ float solid_angle(Vec3<float> p, Vec3<float> A, Vec3<float> B, Vec3<float> C) {
+    const Vec3<float> a = sub(A, p), b = sub(B, p), c = sub(C, p);
+    const float num = dot(a, cross(sub(b, a), sub(c, a)));
+    const float la = sqrtf(dot(a, a)), lb = sqrtf(dot(b, b)), lc = sqrtf(dot(c, c));
+    const float den = (((la * lb) * lc + dot(a, b) * lc) + dot(b, c) * la) + dot(c, a) * lb;
+    return 2.f * atan2f(num, den);
+}
+
 // Cell of coordinate x along an axis of n cells that starts at lo, inv = 1 / cell size; a NaN lands in cell 0.
 __device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
     return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));

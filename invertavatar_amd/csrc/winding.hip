@@ -33,15 +33,7 @@ constexpr int kChunk = 2048;                         // faces per partial sum (a
 constexpr int64_t kMaxFaces = (int64_t)1 << 25;      // the limit of ia_tri_pack: at most 2^14 chunks (gridDim.y)
 static_assert(kChunk % kTile == 0, "a chunk is whole tiles");
 
-using V3 = ia::Vec3<float>;
-
-__device__ __forceinline__ float solid_angle(V3 p, V3 A, V3 B, V3 C) {
-    const V3 a = sub(A, p), b = sub(B, p), c = sub(C, p);
-    const float num = dot(a, cross(sub(b, a), sub(c, a)));
-    const float la = sqrtf(dot(a, a)), lb = sqrtf(dot(b, b)), lc = sqrtf(dot(c, c));
-    const float den = (((la * lb) * lc + dot(a, b) * lc) + dot(b, c) * la) + dot(c, a) * lb;
-    return 2.f * atan2f(num, den);
-}
+using V3 = ia::Vec3<float>;                       // (solid_angle: geom_common.h, shared with winding_tree.hip)
 
 // grid (point blocks, chunks).  part[chunk * N + i] = sum of omega over the chunk's faces, in face order.
 __global__ __launch_bounds__(kBlock) void winding_partial_kernel(const float* __restrict__ pts, int64_t N, const float4* __restrict__ tris,

@@ -41,7 +41,9 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   generalised winding number: 1 inside a closed outward-wound mesh, 0 outside, smooth for open meshes), the signed distance made of
   it and ``closest_point``, a mesh as an SDF / occupancy lattice and the volumetric IoU of two meshes.  Device tensors go to
   ``ia_winding_number`` (csrc/winding.hip: the all-pairs sum, double sums in a fixed order) + ``ia_closest_point`` +
-  ``ia_volume_components``; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.
+  ``ia_volume_components``; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.  ``WindingTree`` and
+  ``method='tree'`` / ``winding='tree'`` are the approximation for large meshes (csrc/winding_tree.hip: a Morton-sorted cluster tree
+  whose far nodes are a dipole and its first derivative); the exact sum stays the default and what the tree is held to.
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Rasteriser: pixel centres are at integer coordinates, column i and row j of ``RaySampler_zxc`` (ray ``K_res^-1 [i, j, 1]``), so its images
@@ -843,7 +845,7 @@ def _sample_set(verts, faces, samples, seed, points):
 
 
 def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None,
-                     signed=False):
+                     signed=False, winding='exact', beta=2.0):
     """How far surface a is from surface b.  The sample set of each mesh is its vertices (``samples=None``), ``samples`` area-weighted
     points (``sample_surface`` with ``seed`` for a and ``seed + 1`` for b) or the points given (``points_a`` / ``points_b``).  With
     ``d_ab`` the exact distances of a's samples to mesh b and ``d_ba`` those of b's samples to mesh a (``closest_point``; non-finite
@@ -860,12 +862,17 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     - with ``signed=True`` also ``mean_signed_ab`` / ``mean_signed_ba``: the mean of ``signed_distance`` of the samples of one mesh
       against the other (negative inside; positive ``mean_signed_ab``: a lies outside b, it is inflated against it), and
       ``inside_share_ab`` / ``inside_share_ba``: the share of those samples whose winding number is at least 0.5.  Both are over the
-      samples with a finite distance (NaN when there is none).  This costs n_a F_b + n_b F_a pairs (``winding_number``).
+      samples with a finite distance (NaN when there is none).  This costs n_a F_b + n_b F_a pairs (``winding_number``);
+      ``winding='tree'`` takes ``winding_number(method='tree', beta=beta)`` instead, one ``WindingTree`` per mesh.
 
     Device meshes run on the kernels (one ``TriangleGrid`` per mesh, ia_distance_stats for the sums); CPU tensors and NumPy arrays take
     the NumPy restatements."""
     _mesh_args(verts_a, faces_a)
     _mesh_args(verts_b, faces_b)
+    _winding_method(winding, 'winding')
+    if winding == 'tree':
+        _winding_beta(beta)
+    use_tree = bool(signed) and winding == 'tree'
     on_dev = isinstance(verts_a, torch.Tensor) and verts_a.is_cuda
     if thresholds is None:
         diag = 0.0
@@ -889,7 +896,7 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
         for pts, nrm, grid, fn in ((pa, na, grid_b, fn_b), (pb, nb, grid_a, fn_a)):
             r = grid.closest(pts)
             if signed:
-                sides.append((r['dist'], _winding_device(pts, None, None, grid)))
+                sides.append((r['dist'], WindingTree.from_grid(grid).query(pts, beta) if use_tree else _winding_device(pts, None, None, grid)))
             if nrm is not None:
                 s = hipops.distance_stats(r['dist'], thresholds, r['face'].int(), nrm.float().contiguous(), fn.float().contiguous())
             else:
@@ -901,7 +908,8 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
         for pts, nrm, v, f, fn in ((pa, na, verts_b, faces_b, fn_b), (pb, nb, verts_a, faces_a, fn_a)):
             r = closest_point(_np(pts), _np(v), _np(f))
             if signed:
-                sides.append((r['dist'], _winding_numpy(_np(pts), _np(v), _np(f))[0]))
+                sides.append((r['dist'], WindingTree(_np(v), _np(f)).query(_np(pts), beta) if use_tree
+                              else _winding_numpy(_np(pts), _np(v), _np(f))[0]))
             out.append(_stats_numpy(r['dist'], thresholds, *((r['face'], _np(nrm), _np(fn)) if nrm is not None else ())))
         s_ab, s_ba = out
 
@@ -1315,7 +1323,262 @@ def _winding_device(points, verts, faces, grid):
     return hipops.winding_number(pts, tris)
 
 
-def winding_number(points, verts, faces, grid=None):
+# ---- the cluster tree with a far-field expansion (csrc/winding_tree.hip)
+
+WINDING_LEAF = 32            # faces per leaf (csrc/winding_tree.hip kLeaf = hipops.WINDING_LEAF): part of the results
+WINDING_BRANCH = 8           # children per upper node (kBranch): part of the results
+_WINDING_NO_KEY = 1 << 30
+_WINDING_METHODS = ('exact', 'tree')
+
+
+def _winding_beta(beta):
+    """``beta`` as the fp32 the traversal compares with: finite and greater than 1, or inf (never far)."""
+    try:
+        b = F32(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f'beta must be a number greater than 1 or inf, got {beta!r}') from None
+    if not b > 1:
+        raise ValueError(f'beta must be greater than 1 (as float32) or inf, got {beta!r}')
+    return b
+
+
+def _winding_method(method, name='method'):
+    if method not in _WINDING_METHODS:
+        raise ValueError(f'{name} must be one of {_WINDING_METHODS}, got {method!r}')
+    return method
+
+
+def _winding_levels(n_usable):
+    """Nodes per level, leaves first: ceil(n / LEAF), then ceil(previous / BRANCH) down to one root; [] without a usable face."""
+    counts = []
+    if n_usable > 0:
+        c = -(-int(n_usable) // WINDING_LEAF)
+        while True:
+            counts.append(c)
+            if c == 1:
+                break
+            c = -(-c // WINDING_BRANCH)
+    return counts
+
+
+def _morton_cube(lo, hi):
+    """(lo float32 [3], scale float32) of the key cube: ``scale = fp32(1024) / (longest side of the box, fp32)``, 0 without extent."""
+    lo32, hi32 = np.asarray(lo, dtype=F32), np.asarray(hi, dtype=F32)
+    side = (hi32 - lo32).max()
+    with np.errstate(over='ignore'):
+        scale = F32(1024) / side if side > 0 else F32(0)
+    return lo32, (scale if np.isfinite(scale) else F32(0))
+
+
+def _spread10(x):
+    x = x.astype(np.uint32)
+    x = (x | (x << 16)) & 0x030000FF
+    x = (x | (x << 8)) & 0x0300F00F
+    x = (x | (x << 4)) & 0x030C30C3
+    x = (x | (x << 2)) & 0x09249249
+    return x
+
+
+def _morton_keys_numpy(xyz, lo, scale):
+    """30-bit Morton keys of float32 rows [n,3]: per axis ``clamp(floor((x - lo) * scale), 0, 1023)`` in fp32 (a NaN lands in cell 0),
+    x the lowest bit of a triple."""
+    with np.errstate(invalid='ignore', over='ignore'):
+        cell = np.fmin(np.fmax(np.floor((np.asarray(xyz, dtype=F32) - lo) * scale), F32(0)), F32(1023)).astype(np.int64)
+    return (_spread10(cell[:, 0]) | (_spread10(cell[:, 1]) << 1) | (_spread10(cell[:, 2]) << 2)).astype(np.int64)
+
+
+def _winding_tree_numpy(verts, faces):
+    """NumPy restatement of the tree build (ia_winding_tree_face_keys + the stable sort + ia_winding_tree_nodes): ``{'order' int64
+    [F], 'tris' float32 [F_usable,3,3] in sorted order, 'nodes64' float64 [n,20], 'counts', 'usable', 'lo', 'scale'}``.  The rows are
+    (c, r, D, A, Q row-major, 0 0 0) in float64; the table the queries read is their rounding to float32."""
+    v32 = np.asarray(verts, dtype=F32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    in_range = ((f >= 0) & (f < v32.shape[0])).all(1)
+    tri = v32[np.where(in_range[:, None], f, 0)] if v32.shape[0] else np.zeros((f.shape[0], 3, 3), dtype=F32)
+    usable = in_range & np.isfinite(tri).all((1, 2))
+    fin = v32[np.isfinite(v32).all(1)]
+    lo, scale = _morton_cube(fin.min(0), fin.max(0)) if fin.shape[0] else (np.zeros(3, dtype=F32), F32(0))
+    with np.errstate(invalid='ignore', over='ignore'):
+        cen = ((tri[:, 0] + tri[:, 1]) + tri[:, 2]) * (F32(1) / F32(3))
+    keys = np.where(usable, _morton_keys_numpy(cen, lo, scale), _WINDING_NO_KEY)
+    order = np.argsort(keys, kind='stable')
+    fu = int(usable.sum())
+    t32 = tri[order[:fu]]
+    t = t32.astype(np.float64)
+    counts = _winding_levels(fu)
+    rows = np.zeros((sum(counts), 20))
+    A, B, C = t[:, 0], t[:, 1], t[:, 2]
+    an = _cross3(B - A, C - A) * 0.5
+    area = np.sqrt(_dot3(an, an))
+    ct = ((A + B) + C) * (1.0 / 3.0)
+
+    def seq(x):                                                                            # a sum in index order
+        return np.cumsum(x, axis=0)[-1]
+    for i in range(counts[0] if counts else 0):
+        sl = slice(i * WINDING_LEAF, min((i + 1) * WINDING_LEAF, fu))
+        a = seq(area[sl])
+        c = seq(ct[sl] * area[sl, None]) * (1.0 / a) if a > 0 else seq(ct[sl]) * (1.0 / (sl.stop - sl.start))
+        u = ct[sl] - c
+        rel = t[sl] - c
+        rows[i, :3], rows[i, 3], rows[i, 4:7], rows[i, 7] = c, np.sqrt(_dot3(rel, rel).max()), seq(an[sl]), a
+        rows[i, 8:17] = seq(u[:, :, None] * an[sl][:, None, :]).reshape(9)
+    start, span = 0, WINDING_LEAF
+    for lvl in range(1, len(counts)):
+        child0, start = start, start + counts[lvl - 1]
+        for j in range(counts[lvl]):
+            ks = np.arange(j * WINDING_BRANCH, min((j + 1) * WINDING_BRANCH, counts[lvl - 1]))
+            ch = rows[child0 + ks]
+            nk = (np.minimum((ks + 1) * span, fu) - ks * span).astype(np.float64)
+            a = seq(ch[:, 7])
+            c = seq(ch[:, :3] * ch[:, 7:8]) * (1.0 / a) if a > 0 else seq(ch[:, :3] * nk[:, None]) * (1.0 / seq(nk))
+            u = ch[:, :3] - c
+            row = rows[start + j]
+            row[:3], row[3], row[4:7], row[7] = c, (np.sqrt(_dot3(u, u)) + ch[:, 3]).max(), seq(ch[:, 4:7]), a
+            q = np.zeros(9)
+            for k in range(ks.size):                                                       # (Q_k first, then the shift, child by child)
+                q = (q + ch[k, 8:17]) + (u[k][:, None] * ch[k, 4:7][None, :]).reshape(9)
+            row[8:17] = q
+        span *= WINDING_BRANCH
+    return {'order': order, 'tris': t32, 'nodes64': rows, 'counts': counts, 'usable': fu, 'lo': lo, 'scale': scale}
+
+
+def _winding_tree_query_numpy(points, tris, nodes, counts, beta, dtype=np.float64, use_q=True):
+    """NumPy restatement of ia_winding_tree_query on a float32 node table ``nodes`` [n,20] and the sorted usable triangles ``tris``
+    [F_usable,3,3]: ``(w, bound, size, far, pairs)`` per point, with the terms evaluated in ``dtype``, ``size = sum |term| / 4 pi``,
+    ``far`` the number of far terms and ``pairs`` the exact pairs.  The far / near decisions are always the kernel's fp32 ones; the
+    running sum is double in visiting order (depth first, children in index order).  ``use_q=False`` drops the Q terms (tests)."""
+    p32 = np.asarray(points, dtype=F32).reshape(-1, 3)
+    nodes = np.asarray(nodes, dtype=F32).reshape(-1, 20)
+    t = np.asarray(tris, dtype=F32).reshape(-1, 3, 3).astype(dtype)
+    n, fu, b32 = p32.shape[0], t.shape[0], _winding_beta(beta)
+    p = p32.astype(dtype)
+    total, bound, size = np.zeros(n), np.zeros(n), np.zeros(n)
+    far_n, pair_n = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    ok = np.isfinite(p32).all(1)
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    stack = [(len(counts) - 1, 0, np.flatnonzero(ok))] if counts else []
+    with np.errstate(invalid='ignore', over='ignore', under='ignore', divide='ignore'):
+        while stack:
+            lvl, j, idx = stack.pop()
+            row = nodes[starts[lvl] + j]
+            x32 = row[:3] - p32[idx]
+            d2 = (x32[:, 0] * x32[:, 0] + x32[:, 1] * x32[:, 1]) + x32[:, 2] * x32[:, 2]
+            br = b32 * row[3]
+            far = d2 > br * br
+            if far.any():
+                r = idx[far]
+                x = (row[:3].astype(dtype) - p[r]).astype(dtype)
+                dd = _dot3(x, x)
+                D, Q = row[4:7].astype(dtype), row[8:17].astype(dtype).reshape(3, 3)
+                if not use_q:
+                    Q = Q * dtype(0)
+                qx = np.stack([_dot3(Q[0], x), _dot3(Q[1], x), _dot3(Q[2], x)], -1)
+                tr = (Q[0, 0] + Q[1, 1]) + Q[2, 2]
+                term = (((_dot3(D, x) + tr) - dtype(3) * _dot3(x, qx) / dd) / (dd * np.sqrt(dd))).astype(np.float64)
+                total[r] += term
+                size[r] += np.abs(term)
+                e = np.sqrt(d2[far].astype(np.float64)) - np.float64(row[3])
+                bound[r] += 3.0 * np.float64(row[7]) * (np.float64(row[3]) * np.float64(row[3])) / (4.0 * np.pi * ((e * e) * (e * e)))
+                far_n[r] += 1
+            r = idx[~far]
+            if not r.size:
+                continue
+            if lvl == 0:
+                sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, fu))
+                om = _solid_angle(p[r, None, :], t[None, sl, 0], t[None, sl, 1], t[None, sl, 2], dtype).astype(np.float64)
+                total[r] = np.cumsum(np.concatenate([total[r, None], om], 1), axis=1)[:, -1]       # one term at a time, in face order
+                size[r] += np.abs(om).sum(1)
+                pair_n[r] += sl.stop - sl.start
+            else:
+                k1 = min((j + 1) * WINDING_BRANCH, counts[lvl - 1])
+                stack.extend((lvl - 1, k, r) for k in range(k1 - 1, j * WINDING_BRANCH - 1, -1))
+    w, big = total / (4.0 * np.pi), size / (4.0 * np.pi)
+    w[~ok] = np.nan
+    big[~ok] = np.nan
+    bound[~ok] = np.nan
+    return w, bound, big, far_n, pair_n
+
+
+class WindingTree:
+    """The cluster tree of one mesh for ``winding_number(method='tree')``, built once: ``order`` (sorted position -> input face: the
+    usable faces by the 30-bit Morton key of their centroid, ties by face index, then the unusable ones), ``tris`` (the triangles in
+    that order), ``nodes`` (float32 [n,20]: centre, radius, dipole, area and the first-derivative tensor Q per node, leaves first),
+    ``counts`` (nodes per level) and ``info``.  Leaves hold ``WINDING_LEAF`` faces, upper nodes ``WINDING_BRANCH`` children; there are
+    no pointers.  Device tensors build on the kernels (``grid``: a ``TriangleGrid`` of this mesh whose packed triangles are reused);
+    CPU tensors and NumPy arrays take the NumPy restatement, which is the definition.  ``query(points, beta)`` -> float64 [...]."""
+
+    def __init__(self, verts, faces, grid=None):
+        if grid is not None:
+            verts, faces = grid.verts, grid.faces
+        _mesh_args(verts, faces)
+        self.device = verts.device if _is_device(verts) else None
+        self._like = verts
+        if self.device is not None:
+            from . import hipops
+            if grid is None:
+                grid = TriangleGrid(verts, faces, build=False)
+            lo, scale = _morton_cube(grid.lo, grid.hi)
+            self.order, self.tris, self.nodes, self.counts, self.usable = hipops.winding_tree_build(grid.tris, lo.tolist(), float(scale))
+        else:
+            t = _winding_tree_numpy(_np(verts), _np(faces))
+            lo, scale = t['lo'], t['scale']
+            self.order, self.tris, self.counts, self.usable = t['order'], t['tris'], t['counts'], t['usable']
+            self.nodes64 = t['nodes64']
+            self.nodes = t['nodes64'].astype(F32)
+        self.lo, self.scale = [float(x) for x in lo], float(scale)
+        self.info = {'faces': int(faces.shape[0]), 'usable': int(self.usable), 'levels': len(self.counts), 'nodes': int(sum(self.counts)),
+                     'leaf': WINDING_LEAF, 'branch': WINDING_BRANCH}
+
+    @classmethod
+    def from_grid(cls, grid):
+        """The tree of the mesh of a ``TriangleGrid``, from its packed triangles."""
+        return cls(None, None, grid=grid)
+
+    def query(self, points, beta=2.0, return_bound=False, return_counts=False, sort=True):
+        """Winding numbers float64 [...] of points [..., 3]; with ``return_bound`` also the truncation bound, with ``return_counts``
+        also int [..., 2] (far terms, exact pairs).  ``sort`` (device): query in Morton order of the points, so that a wave's lanes walk
+        the same nodes, and return in the caller's order; it changes no result."""
+        b32 = _winding_beta(beta)
+        lead = tuple(points.shape[:-1])
+        if self.device is not None:
+            from . import hipops
+            pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
+            perm = None
+            if sort and pts.shape[0] > 64:
+                perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
+                pts = pts[perm].contiguous()
+            res = hipops.winding_tree_query(pts, self.tris, self.nodes, self.usable, float(b32), bound=return_bound, counts=return_counts)
+            if perm is not None:
+                back = torch.empty_like(perm)
+                back[perm] = torch.arange(perm.numel(), device=perm.device)
+                res = [None if x is None else x[back] for x in res]
+            w, bound, cnt = res
+            out = [w.reshape(lead)]
+            if return_bound:
+                out.append(bound.reshape(lead))
+            if return_counts:
+                out.append(cnt.reshape(lead + (2,)))
+        else:
+            w, bound, _, nf, npair = _winding_tree_query_numpy(_np(points), self.tris, self.nodes, self.counts, b32)
+            out = [_as_out(w.reshape(lead), points, np.float64)]
+            if return_bound:
+                out.append(_as_out(bound.reshape(lead), points, np.float64))
+            if return_counts:
+                out.append(_as_out(np.stack([nf, npair], -1).reshape(lead + (2,)), points, np.int64))
+        return out[0] if len(out) == 1 else tuple(out)
+
+
+def _winding_tree_for(verts, faces, grid, tree):
+    if tree is None:
+        return WindingTree(verts, faces, grid=grid)
+    if not isinstance(tree, WindingTree):
+        raise ValueError(f'tree must be a WindingTree, got {type(tree).__name__}')
+    if (tree.device is not None) != _is_device(verts):
+        raise ValueError('tree: the WindingTree must live where the mesh lives (device or host)')
+    return tree
+
+
+def winding_number(points, verts, faces, grid=None, method='exact', beta=2.0, tree=None, return_bound=False):
     """Generalised winding number of points [..., 3] with respect to the triangle soup (verts float32 [V,3], faces [F,3]): float64
     [...].  ``w(p) = (1 / 4 pi) sum_f omega_f(p)`` with ``omega_f`` the signed solid angle of triangle f seen from p (``_solid_angle``,
     float32): 1 inside a closed mesh wound outward (the winding of ``marching_cubes``), 0 outside, k where k such surfaces nest, and a
@@ -1323,29 +1586,45 @@ def winding_number(points, verts, faces, grid=None):
     without area contributes 0, one with an index out of range or a non-finite vertex is ignored; a non-finite point gives NaN; a mesh
     without usable triangles 0.  The terms are added in double in a fixed order (``_winding_numpy``), so a point's value does not depend
     on the other points of the call.  The cost is N F pairs.  Device tensors run on ia_winding_number (``grid``: a ``TriangleGrid`` of
-    this mesh whose packed triangles are reused); CPU tensors and NumPy arrays take the NumPy restatement (float64 per pair)."""
+    this mesh whose packed triangles are reused); CPU tensors and NumPy arrays take the NumPy restatement (float64 per pair).
+
+    ``method='tree'`` is the approximation for large meshes: a ``WindingTree`` (``tree``, or built here) whose nodes farther from the
+    point than ``beta`` times their radius are replaced by a dipole and its first derivative; nearer leaves add their exact terms.
+    ``beta`` is greater than 1; larger is more accurate and slower, ``inf`` adds the exact terms in the tree's order.  The value is
+    again a pure function of point, mesh and ``beta``.  ``return_bound=True`` returns ``(w, bound)`` with ``bound`` the derived bound of
+    the truncation error per point (0 for ``method='exact'``): loose, about 1e2 times the error at ``beta = 2``."""
     _mesh_args(verts, faces)
+    _winding_method(method)
     lead = tuple(points.shape[:-1])
+    if method == 'tree':
+        _winding_beta(beta)
+        return _winding_tree_for(verts, faces, grid, tree).query(points, beta, return_bound=return_bound)
     if _is_device(verts):
-        return _winding_device(points, verts, faces, grid).reshape(lead)
-    w, _ = _winding_numpy(_np(points), _np(verts), _np(faces))
-    return _as_out(w.reshape(lead), points, np.float64)
+        w = _winding_device(points, verts, faces, grid).reshape(lead)
+    else:
+        w = _as_out(_winding_numpy(_np(points), _np(verts), _np(faces))[0].reshape(lead), points, np.float64)
+    if return_bound:
+        return w, (torch.zeros_like(w) if isinstance(w, torch.Tensor) else np.zeros_like(w))
+    return w
 
 
-def inside(points, verts, faces, threshold=0.5):
-    """bool [...]: ``winding_number(points) >= threshold`` (a non-finite point is not inside)."""
-    return winding_number(points, verts, faces) >= threshold
+def inside(points, verts, faces, threshold=0.5, method='exact', beta=2.0, tree=None):
+    """bool [...]: ``winding_number(points) >= threshold`` (a non-finite point is not inside).  ``method`` / ``beta`` / ``tree``: those
+    of ``winding_number``."""
+    return winding_number(points, verts, faces, method=method, beta=beta, tree=tree) >= threshold
 
 
-def signed_distance(points, verts, faces, grid=None, threshold=0.5):
+def signed_distance(points, verts, faces, grid=None, threshold=0.5, method='exact', beta=2.0, tree=None):
     """Signed distance of points to a mesh: ``{'sdf', 'dist', 'face', 'point', 'winding'}``.  ``dist``, ``face`` and ``point`` are the
     results of ``closest_point`` (the same bits), ``winding`` (float64) is ``winding_number`` and ``sdf`` is ``-dist`` where
-    ``winding >= threshold``, else ``+dist``: negative inside.  ``grid``: a ``TriangleGrid`` of the mesh (device), used by both."""
+    ``winding >= threshold``, else ``+dist``: negative inside.  ``grid``: a ``TriangleGrid`` of the mesh (device), used by both.
+    ``method`` / ``beta`` / ``tree``: those of ``winding_number``."""
     _mesh_args(verts, faces)
+    _winding_method(method)
     if _is_device(verts) and grid is None:
         grid = TriangleGrid(verts, faces)
     r = closest_point(points, verts, faces, grid=grid)
-    w = winding_number(points, verts, faces, grid=grid).reshape(r['dist'].shape)
+    w = winding_number(points, verts, faces, grid=grid, method=method, beta=beta, tree=tree).reshape(r['dist'].shape)
     neg = w >= threshold
     sdf = torch.where(neg, -r['dist'], r['dist']) if isinstance(neg, torch.Tensor) else np.where(neg, -r['dist'], r['dist'])
     return {'sdf': sdf, 'dist': r['dist'], 'face': r['face'], 'point': r['point'], 'winding': w}
@@ -1420,7 +1699,7 @@ def _mesh_is_closed(verts, faces):
     return int(info['boundary_edges']) == 0 and int(info['nonmanifold_edges']) == 0
 
 
-def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=2, sign='auto', threshold=0.5):
+def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=2, sign='auto', threshold=0.5, winding='exact', beta=2.0):
     """A triangle mesh as a signed distance lattice: ``{'sdf' float32 [nx,ny,nz] (negative inside), 'inside' bool [nx,ny,nz],
     'origin', 'spacing', 'info'}``.  The lattice is that of ``marching_cubes``: point (i, j, k) at ``origin + index * spacing`` in fp32,
     volumes indexed [i, j, k] with z fastest, so ``marching_cubes(-sdf, 0, origin, spacing)`` remeshes the surface.  With ``origin``
@@ -1438,11 +1717,18 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
     - ``sign='auto'``: ``'regions'`` when ``MeshAdjacency(...).info`` has no boundary and no non-manifold edge, else ``'winding'``.
       (The test is on edges, not on orientation: the faces of a closed mesh must be wound consistently.)
 
-    ``info``: ``{'mode', 'regions', 'band', 'evaluations'}``: the mode taken, the number of components, the points of the band and
-    the number of winding-number evaluations.  Device tensors run on the kernels; CPU tensors and NumPy arrays take the restatements."""
+    ``winding='tree'`` evaluates every one of those winding numbers (the band, the regions, ``sign='winding'``) through a
+    ``WindingTree`` with ``beta`` (``winding_number(method='tree')``) instead of the exact sum.
+
+    ``info``: ``{'mode', 'regions', 'band', 'evaluations', 'winding'}``: the mode taken, the number of components, the points of the
+    band, the number of winding-number evaluations and how they were made.  Device tensors run on the kernels; CPU tensors and NumPy
+    arrays take the restatements."""
     _mesh_args(verts, faces)
     if sign not in _SIGN_MODES:
         raise ValueError(f'sign must be one of {_SIGN_MODES}, got {sign!r}')
+    _winding_method(winding, 'winding')
+    if winding == 'tree':
+        _winding_beta(beta)
     on_dev = _is_device(verts)
     box = _finite_box(verts)
     dims, org, spc = _volume_lattice(box, resolution, origin, spacing, padding)
@@ -1458,18 +1744,22 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
         grid = TriangleGrid(verts, faces)
         pts = torch.stack(torch.meshgrid(*[torch.from_numpy(ax).to(dev) for ax in axes], indexing='ij'), -1).reshape(-1, 3).contiguous()
         dist = grid.closest(pts)['dist']
+        tree = WindingTree.from_grid(grid) if winding == 'tree' else None
 
         def wind(idx):
-            return _winding_device(pts if idx is None else pts[idx], None, None, grid) >= threshold
+            sel = pts if idx is None else pts[idx]
+            return (tree.query(sel, beta) if tree is not None else _winding_device(sel, None, None, grid)) >= threshold
     else:
         grid = None
         v_np, f_np = _np(verts), _np(faces)
         pts = np.ascontiguousarray(np.stack(np.meshgrid(*axes, indexing='ij'), -1).reshape(-1, 3))
         dist = _closest_numpy(pts, v_np, f_np)[0].astype(F32)
+        tree = WindingTree(v_np, f_np) if winding == 'tree' else None
 
         def wind(idx):
-            return _winding_numpy(pts if idx is None else pts[idx], v_np, f_np)[0] >= threshold
-    info = {'mode': mode, 'regions': 0, 'band': n, 'evaluations': n}
+            sel = pts if idx is None else pts[idx]
+            return (tree.query(sel, beta) if tree is not None else _winding_numpy(sel, v_np, f_np)[0]) >= threshold
+    info = {'mode': mode, 'regions': 0, 'band': n, 'evaluations': n, 'winding': winding}
     if mode == 'winding':
         neg = wind(None)
     else:

@@ -11,8 +11,9 @@ OUT.ply``, writes the moved mesh.  ICP finds the nearest local optimum: a predic
 centroid`` or a pose from landmarks (``geometry.fit_transform``).  ``--signed`` adds the signed numbers of
 ``surface_distance(signed=True)`` (mean signed distance and inside share per direction: is the prediction inflated or deflated?) and
 colours ``--error-ply`` with a diverging map (blue inside the ground truth, red outside, white on it).  ``--iou RES`` adds a
-``volume_iou`` block: the volumetric IoU of the two meshes on a lattice of ``RES`` points along the longest axis.  Without these flags
-the outputs are what they were.  Runs on the device when there is one."""
+``volume_iou`` block: the volumetric IoU of the two meshes on a lattice of ``RES`` points along the longest axis.  ``--winding tree``
+(with ``--winding-beta B``, default 2) makes the winding numbers behind both with ``geometry.WindingTree`` instead of the exact all-pairs
+sum: the route for meshes of hundreds of thousands of faces.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
 import argparse
 import json
 import math
@@ -69,13 +70,15 @@ def alignment_block(fit):
 
 
 def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None, align=None, align_options=None,
-                   save_aligned=None, aligned=None, signed=False, iou=None):
+                   save_aligned=None, aligned=None, signed=False, iou=None, winding='exact', beta=2.0):
     """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance.
     ``align``: 'rigid' or 'similarity' moves the mesh onto the reference first (``align_prediction`` with ``align_options``); the moved
     mesh is scored (and coloured), the result gains ``alignment`` (``alignment_block``), ``save_aligned`` is a PLY path for the moved mesh
     and ``aligned``, a dict, receives its ``verts`` and the ``matrix``.  ``signed``: the signed keys of ``surface_distance`` and a
     diverging ``error_ply`` (``signed_error_colors``); ``iou``: a lattice resolution, adds ``volume_iou`` of the (moved) mesh and the
-    reference."""
+    reference.  ``winding='tree'``: the winding numbers behind ``signed`` and ``iou`` come from ``geometry.WindingTree`` with ``beta``
+    (the approximation for large meshes) and the result gains ``winding: {'method', 'beta'}``."""
+    tree = {'winding': winding, 'beta': beta} if winding != 'exact' else {}
     alignment = None
     if align is not None:
         verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, align_options)
@@ -85,17 +88,19 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
         if aligned is not None:
             aligned.update(verts=verts, matrix=fit['matrix'])
     res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds,
-                                    **({'signed': True} if signed else {}))
+                                    **({'signed': True, **tree} if signed else {}))
+    if tree:
+        res['winding'] = {'method': winding, 'beta': float(beta)}
     res.update(pred_vertices=int(verts.shape[0]), pred_faces=int(faces.shape[0]), gt_vertices=int(ref_verts.shape[0]),
                gt_faces=int(ref_faces.shape[0]))
     if alignment is not None:
         res['alignment'] = alignment
     if iou is not None:
-        res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou))
+        res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou), **tree)
     if error_ply:
         scale = res['thresholds'][-1] if res['thresholds'] else 1.0
         if signed:
-            sdf = geometry.signed_distance(verts, ref_verts, ref_faces)['sdf']
+            sdf = geometry.signed_distance(verts, ref_verts, ref_faces, **({'method': winding, 'beta': beta} if tree else {}))['sdf']
             geometry.write_ply(error_ply, verts, faces, signed_error_colors(geometry._np(sdf), scale))
         else:
             dist = geometry.closest_point(verts, ref_verts, ref_faces)['dist']
@@ -104,14 +109,19 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
 
 
 def add_sign_arguments(ap):
-    """``--signed`` and ``--iou``, shared with extract_geometry."""
+    """``--signed``, ``--iou`` and how their winding numbers are made (``--winding``, ``--winding-beta``), shared with extract_geometry."""
     ap.add_argument('--signed', action='store_true', help='add signed distances (negative inside the reference); diverging --error-ply')
     ap.add_argument('--iou', type=int, default=None, metavar='RES', help='add the volumetric IoU on a lattice of RES points along the longest axis')
+    ap.add_argument('--winding', default='exact', choices=['exact', 'tree'],
+                    help="winding numbers of --signed / --iou: the exact sum, or the cluster tree with a far field (large meshes)")
+    ap.add_argument('--winding-beta', type=float, default=2.0, metavar='B',
+                    help='with --winding tree: a node farther than B times its radius is taken as far (> 1; larger is more accurate)')
 
 
 def sign_options_of(args):
-    """The keyword arguments of ``compare_meshes`` for ``--signed`` / ``--iou``; empty without them."""
-    return {**({'signed': True} if args.signed else {}), **({'iou': args.iou} if args.iou is not None else {})}
+    """The keyword arguments of ``compare_meshes`` for ``--signed`` / ``--iou`` / ``--winding tree``; empty without them."""
+    return {**({'signed': True} if args.signed else {}), **({'iou': args.iou} if args.iou is not None else {}),
+            **({'winding': args.winding, 'beta': args.winding_beta} if args.winding != 'exact' else {})}
 
 
 def add_align_arguments(ap):

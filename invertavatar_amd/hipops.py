@@ -1787,6 +1787,99 @@ def winding_number(points, tris, workspace_bytes=WINDING_WORKSPACE):
     return out
 
 
+# ------------------------------------------------------------------ winding tree (csrc/winding_tree.hip)
+
+WINDING_LEAF = 32            # faces per leaf (csrc/winding_tree.hip kLeaf): part of the results, geometry restates the tree with the same
+WINDING_BRANCH = 8           # children per upper node (kBranch): part of the results
+WINDING_ROW = 20             # floats per node row (5 float4)
+WINDING_MAX_LEVELS = 8
+WINDING_NO_KEY = 1 << 30     # Morton key of an unusable triangle or a non-finite point
+
+
+def winding_tree_layout():
+    """(leaf, branch, floats per node row, most levels) as the library reports them (ia_winding_tree_layout; host only)."""
+    vals = [ctypes.c_int(0) for _ in range(4)]
+    _lib.check(_lib.load().ia_winding_tree_layout(*[ctypes.byref(v) for v in vals]), 'ia_winding_tree_layout')
+    return tuple(v.value for v in vals)
+
+
+def winding_tree_plan(n_usable):
+    """(nodes per level, leaves first; total nodes; scratch bytes of the build) for ``n_usable`` faces (ia_winding_tree_plan; host only)."""
+    levels, nodes, nbytes = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_size_t(0)
+    counts = (ctypes.c_int * WINDING_MAX_LEVELS)()
+    st = _lib.load().ia_winding_tree_plan(int(n_usable), ctypes.byref(levels), counts, ctypes.byref(nodes), ctypes.byref(nbytes))
+    _lib.check(st, 'ia_winding_tree_plan')
+    return list(counts[:levels.value]), nodes.value, nbytes.value
+
+
+def _tris_checked(tris):
+    _f32c(tris, 'tris')
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 4):
+        raise RuntimeError(f'tris must be the [F,3,4] tensor of tri_pack, got {tuple(tris.shape)}')
+
+
+def winding_tree_point_keys(points, lo, scale):
+    """Morton keys int32 [N] of points float32 [N,3] over the cube (lo, scale) (see ia_winding_tree_point_keys)."""
+    _f32c(points, 'points')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points must be [N,3], got {tuple(points.shape)}')
+    n, dev = points.shape[0], points.device
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _Timed('winding_tree_keys', 0.0, 16.0 * n, f'N={n}'):
+        st = _lib.load().ia_winding_tree_point_keys(_p(points), n, _f3(lo), float(scale), _p(keys), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_winding_tree_point_keys')
+    return keys
+
+
+def winding_tree_build(tris, lo, scale):
+    """The cluster tree of packed triangles (see ia_winding_tree_nodes): tris from ``tri_pack``, (lo, scale) the Morton cube ->
+    (order int64 [F]: sorted position -> input face, sorted tris [F,3,4], nodes float32 [n,20], nodes per level, usable faces).  The
+    integer keys are sorted by ``torch.sort`` (stable); one host synchronisation (the number of usable faces)."""
+    _tris_checked(tris)
+    f, dev = tris.shape[0], tris.device
+    lib = _lib.load()
+    keys = torch.empty(f, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        with _Timed('winding_tree_keys', 0.0, 52.0 * f, f'F={f}'):
+            st = lib.ia_winding_tree_face_keys(_p(tris), f, _f3(lo), float(scale), _p(keys), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_winding_tree_face_keys')
+        skeys, order = torch.sort(keys, stable=True)
+        usable = int((skeys < WINDING_NO_KEY).sum()) if f else 0
+        order32 = order.int().contiguous()
+        sorted_tris = torch.empty_like(tris)
+        with _Timed('winding_tree_gather', 0.0, 100.0 * f, f'F={f}'):
+            st = lib.ia_winding_tree_gather(_p(tris), f, _p(order32), _p(sorted_tris), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_winding_tree_gather')
+        counts, total, nbytes = winding_tree_plan(usable)
+        nodes = torch.empty(total, WINDING_ROW, device=dev)
+        scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        with _Timed('winding_tree_nodes', 0.0, 96.0 * usable + 240.0 * total, f'F={usable} nodes={total}'):
+            st = lib.ia_winding_tree_nodes(_p(sorted_tris), usable, _p(scratch), scratch.numel() * 8, _p(nodes), total, _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_winding_tree_nodes')
+    return order, sorted_tris, nodes, counts, usable
+
+
+def winding_tree_query(points, sorted_tris, nodes, n_usable, beta=2.0, bound=False, counts=False):
+    """Winding numbers through the tree (see ia_winding_tree_query): points float32 [N,3], ``sorted_tris`` / ``nodes`` / ``n_usable``
+    from ``winding_tree_build`` -> (w float64 [N], bound float64 [N] or None, counts int32 [N,2] or None)."""
+    _f32c(points, 'points')
+    _tris_checked(sorted_tris)
+    _f32c(nodes, 'nodes')
+    if points.dim() != 2 or points.shape[1] != 3 or points.device != sorted_tris.device or nodes.device != points.device:
+        raise RuntimeError(f'points must be [N,3] on the device of the tree, got {tuple(points.shape)} on {points.device}')
+    if nodes.dim() != 2 or nodes.shape[1] != WINDING_ROW or not 0 <= int(n_usable) <= sorted_tris.shape[0]:
+        raise RuntimeError(f'nodes must be [n,{WINDING_ROW}] and n_usable within the triangles, got {tuple(nodes.shape)} and {n_usable}')
+    n, dev = points.shape[0], points.device
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    bnd = torch.empty(n, dtype=torch.float64, device=dev) if bound else None
+    cnt = torch.empty(n, 2, dtype=torch.int32, device=dev) if counts else None
+    with torch.cuda.device(dev), _Timed('winding_tree_query', 0.0, 36.0 * n, f'N={n} F={int(n_usable)} beta={beta}'):
+        st = _lib.load().ia_winding_tree_query(_p(points), n, _p(sorted_tris), int(n_usable), _p(nodes), nodes.shape[0], float(beta), _p(out),
+                                               _p(bnd), _p(cnt), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_winding_tree_query')
+    return out, bnd, cnt
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

@@ -67,6 +67,13 @@ typedef _Float16 h16x2r __attribute__((ext_vector_type(2)));
 // normal fp16 numbers down to |v| ~ 5e-4, below that the dropped bits are < 2.4e-7 absolute) and weights at 2^12 (|w| < 16), both
 // low parts UNscaled, so the three products of a k-step share one accumulator at 2^20; it starts from bias * 2^20 and one multiply by
 // 2^-20 brings the sums back.  Power-of-two scalings: exact.
+// At and beyond these ranges (tests/test_renderer_edges_gpu.py): a mean feature saturates at +-65000 / 256 = 253.9 (the fmed3
+// in decoder_hidden); a hidden unit above 255.9 keeps 65504 as its high part (v_cvt_pkrtz saturates) and its low part carries the rest
+// with 11 bits: finite, colours good to ~1e-3 only, the density row reads the fp32 value; a staged weight -- w0 * gain * log2(e) in
+// layer 1, w1 * gain in the colour rows -- of 65520 / 4096 or more becomes an fp16 infinity (NaN colours, or a silently wrong hidden
+// unit): the host wrappers refuse it (hipops._render_weights_checked).
+// The fmed3 is a safety margin, not a need of the split (65504 + a residual <= 32 would be exact); widen its bounds if need be, but keep
+// the instruction: a build without it was run-to-run nondeterministic on gfx950, cause not found.
 constexpr float kActScale = 256.f, kWgtScale = 4096.f, kAccScale = kActScale * kWgtScale;
 
 // (hi, lo) of two scaled values: hi = fp16(v) towards zero (v_cvt_pkrtz: any rounding of hi is exact as long as lo is its residual),

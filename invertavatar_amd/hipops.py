@@ -8,6 +8,7 @@ import contextvars
 import ctypes
 import math
 import os
+import weakref
 
 import torch
 
@@ -711,6 +712,41 @@ def planes_channels_last(planes):
     return planes.permute(0, 1, 3, 4, 2).contiguous()
 
 
+# ia_render_rays stages the decoder weights as fp16 hi / lo pairs at 2^12 (csrc/render_rays.hip): a staged weight -- layer 1 times its
+# gain and log2 e, the colour rows of layer 2 times their gain -- of 65520 / 4096 = 15.996 or more has an infinite high part and the
+# launch returns NaN.  The bound below leaves room for the kernel's fp32 rounding of the product.
+RENDER_WEIGHT_BOUND = 15.99
+_render_weight_checks = {}      # (data_ptr, _version) of w0 and w1 -> (their storages, weakly; max |w0|; max |w1 colour rows|)
+
+
+def _render_weight_maxima(w0, w1):
+    """(max |w0|, max |w1[1:]|) as python floats: one device -> host read."""
+    return tuple(torch.stack([w0.abs().max(), w1[1:].abs().max()]).tolist())
+
+
+def _render_weights_checked(w0, w1, lr_multiplier):
+    """Raises if a staged decoder weight leaves the range of the kernel's fp16 pairs.  The maxima are read from the device once per
+    version of the two tensors (an in-place update bumps `_version`, a new tensor has another pointer; the entry also holds weak
+    references to the two storages, so a new tensor at the address of a freed one is not taken for it); while a stream is capturing
+    nothing is read, and nothing is checked unless the version is already known."""
+    key = (w0.data_ptr(), w0._version, w1.data_ptr(), w1._version)
+    s0, s1 = w0.untyped_storage(), w1.untyped_storage()
+    entry = _render_weight_checks.get(key)
+    if entry is None or entry[0]() is not s0 or entry[1]() is not s1:
+        if torch.cuda.is_current_stream_capturing():
+            return
+        if len(_render_weight_checks) >= 64:
+            _render_weight_checks.clear()
+        entry = _render_weight_checks[key] = (weakref.ref(s0), weakref.ref(s1)) + _render_weight_maxima(w0, w1)
+    maxima = entry[2:]
+    lr = abs(float(lr_multiplier))
+    staged = (maxima[0] * lr / math.sqrt(32.0) * math.log2(math.e), maxima[1] * lr / math.sqrt(64.0))
+    for name, value, what in (('w0', staged[0], '|w0| * lr_multiplier / sqrt(32) * log2(e)'), ('w1', staged[1], '|w1[1:]| * lr_multiplier / sqrt(64)')):
+        if not value < RENDER_WEIGHT_BOUND:
+            raise RuntimeError(f'render_rays: {name} is outside the decoder\'s fp16 pair range: max {what} = {value:.4g}, '
+                               f'must stay below {RENDER_WEIGHT_BOUND} (the high parts at 2^12 overflow at 16)')
+
+
 def render_rays(planes_cl, rays_o, rays_d, jitter, dist, w0, b0, w1, b1, lr_multiplier=1.0, box_warp=1.0, white_back=False,
                 n_coarse=48, n_importance=48, debug=False, channel_major=False, u_importance=None, split_styles=None, split_planes=0):
     """Fused importance renderer (see ia_render_rays).  Returns (rgb [B,R,32], depth [B,R,1], wsum [B,R,1][, aux]).
@@ -730,6 +766,7 @@ def render_rays(planes_cl, rays_o, rays_d, jitter, dist, w0, b0, w1, b1, lr_mult
         raise RuntimeError(f'jitter must be [B,R,{n_coarse}(,1)], got {tuple(jitter.shape)}')
     if u_importance is not None and (_f32c(u_importance, 'u_importance').numel() != b * r * n_importance):
         raise RuntimeError(f'u_importance must hold B * R * {n_importance} sorted uniform draws')
+    _render_weights_checked(w0, w1, lr_multiplier)
     dev = planes_cl.device
     lib = _lib.load()
     rgb = torch.empty(b, 32, r, device=dev).permute(0, 2, 1) if channel_major else torch.empty(b, r, 32, device=dev)
@@ -793,6 +830,7 @@ def render_rays_box(planes_cl, rays_o, rays_d, jitter, u_importance, w0, b0, w1,
         raise RuntimeError(f'u_importance must hold B * R * {n_importance} sorted uniform draws')
     if ray_limits is not None and _f32c(ray_limits, 'ray_limits').numel() != b * r * 2:
         raise RuntimeError('ray_limits must be [B,R,2]')
+    _render_weights_checked(w0, w1, lr_multiplier)
     dev = planes_cl.device
     lib = _lib.load()
     rgb, depth, wsum = torch.empty(b, r, 32, device=dev), torch.empty(b, r, 1, device=dev), torch.empty(b, r, 1, device=dev)

@@ -150,7 +150,9 @@ extern "C" int ia_se_gate(const float* v, const int64_t* v_strides, const float*
     hipLaunchKernelGGL(se_pool_kernel, dim3((unsigned)(B * C)), dim3(256), 0, s, vv, pooled_scratch, C, H, W);
     int st = ia::check_launch("ia_se_gate(pool)");
     if (st != IA_OK) return st;
-    const int chunks = H * W > 16384 ? 4 : 1;      // (few planes x many pixels: the 64-channel 128^2 units)
+    // few planes x many pixels: four workgroups per plane ABOVE 128^2 pixels.  The 64-channel 128^2 units have exactly 16384 and stay
+    // on one workgroup per plane (tests/test_encoder_ops_gpu.py runs both sides of the switch).
+    const int chunks = H * W > 16384 ? 4 : 1;
     hipLaunchKernelGGL(se_gate_apply_kernel, dim3((unsigned)(B * C), (unsigned)chunks), dim3(256), 0, s, vv, ss, pooled_scratch, w1, w2, out, C, R, H, W);
     return ia::check_launch("ia_se_gate(apply)");
 }

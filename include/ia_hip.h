@@ -1189,6 +1189,32 @@ int ia_winding_tree_nodes(const void* sorted, int64_t F_usable, void* scratch, s
 int ia_winding_tree_query(const float* points, int64_t N, const void* sorted, int64_t F_usable, const void* nodes, int64_t n_nodes,
                           float beta, double* out, double* bound, int* counts, void* stream);
 
+/*
+ * Closest point on the cluster tree: the query of ia_closest_point by branch and bound over the tree of ia_winding_tree_plan
+ * (csrc/closest_tree.hip; no counterpart in the reference; definition: geometry._closest_tree_numpy).  The tree only
+ * prunes: dist, face and point are bit-identical to ia_closest_point in the brute mode and through any grid.  Additive entry points:
+ * the ABI version is unchanged.
+ *
+ * ia_tree_boxes: boxes float32 [n_nodes, 8], two float4 per node in the level layout of ia_winding_tree_plan (leaves first):
+ * (lo.x, lo.y, lo.z, 0) (hi.x, hi.y, hi.z, 0).  A leaf takes the minimum / maximum per axis over the vertices of its sorted faces
+ * [i L, min((i + 1) L, F_usable)), an upper node over its children.  sorted: the triangles of ia_winding_tree_gather.  Min and max
+ * are exact and independent of order: bit-equal run to run.
+ * ia_closest_point_tree: dist float32 [N], face int32 [N] (an INPUT face index: order[sorted position]), point float32 [N,3] for
+ * points float32 [N,3]; order int32 [>= F_usable]: sorted position -> input face.  best = (dist, face), ordered lexicographically,
+ * starts at (+inf, -1); a visited leaf evaluates the per-triangle function of ia_closest_point for its faces and keeps the smaller
+ * pair.  A node is skipped iff lb is finite and lb - slack > best.dist, where, in fp32 with every operation rounded on its own,
+ * g = max(max(lo - p, p - hi), 0) per axis, lb = sqrt((g.x^2 + g.y^2) + g.z^2) and slack = 2^-17 max(|p|_inf, mesh_extent)
+ * (= 64 eps32 times that; mesh_extent: the largest |coordinate| of the usable triangles).  A skipped node holds no triangle whose
+ * computed distance is <= best.dist, so neither the minimum nor the tie changes.  The walk: each point first descends from the root to
+ * the child with the smallest lb (the lowest index among equals) and evaluates that leaf; then depth first from the root, children in
+ * index order, passing over that leaf.  The order changes the cost, never the result.  A non-finite point gives NaN / -1 / NaN,
+ * F_usable = 0 gives +inf / -1 / NaN.  counts (int32 [N,2], or NULL): boxes tested and point-triangle pairs evaluated for the point,
+ * the first descent included.  N >= 0 with 3 N < 2^31, 0 <= F_usable <= 2^25, n_nodes that of ia_winding_tree_plan.
+ */
+int ia_tree_boxes(const void* sorted, int64_t F_usable, void* boxes, int64_t n_nodes, void* stream);
+int ia_closest_point_tree(const float* points, int64_t N, const void* sorted, const int* order, int64_t F_usable, const void* boxes,
+                          int64_t n_nodes, float mesh_extent, float* dist, int* face, float* point, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

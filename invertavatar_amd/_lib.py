@@ -174,6 +174,9 @@ _SIGNATURES = {
     'ia_winding_tree_gather': [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     'ia_winding_tree_nodes': [c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_int64, c_void_p],
     'ia_winding_tree_query': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_tree_boxes': [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
+    'ia_closest_point_tree': [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p],
 }
 
 

@@ -113,6 +113,42 @@ __device__ __forceinline__ float solid_angle(Vec3<float> p, Vec3<float> A, Vec3<
     return 2.f * atan2f(num, den);
 }
 
+// The per-triangle function of the closest-point queries (surface_distance.hip, closest_tree.hip), every operation rounded on its own.
+// Closest point of the segment a + t e, t in [0, 1] (ee = e . e), to the origin; kept if its squared distance is below `best`.
+__device__ __forceinline__ void seg(Vec3<float> a, Vec3<float> e, float ee, float& best, Vec3<float>& q) {
+    float t = 0.f;
+    if (ee > 0.f) t = fminf(fmaxf(-dot(a, e) / ee, 0.f), 1.f);
+    const Vec3<float> r = {a.x + t * e.x, a.y + t * e.y, a.z + t * e.z};
+    const float d2 = dot(r, r);
+    if (d2 < best) { best = d2; q = r; }
+}
+
+// Distance from p to the closed triangle ABC; q: the closest point relative to p.
+__device__ __forceinline__ float tri_dist(Vec3<float> p, Vec3<float> A, Vec3<float> B, Vec3<float> C, Vec3<float>& q) {
+    const Vec3<float> a = sub(A, p), b = sub(B, p), c = sub(C, p);
+    float d2 = INFINITY;
+    q = {NAN, NAN, NAN};
+    const Vec3<float> eab = sub(b, a), ebc = sub(c, b), eca = sub(a, c);
+    const float lab = dot(eab, eab), lbc = dot(ebc, ebc), lca = dot(eca, eca);
+    seg(a, eab, lab, d2, q);
+    seg(b, ebc, lbc, d2, q);
+    seg(c, eca, lca, d2, q);
+    float d = sqrtf(d2);
+    // the normal from the two shorter edges (eab x ebc = ebc x eca = eca x eab): no cancellation on needle-shaped triangles
+    const Vec3<float> n = (lab >= lbc && lab >= lca) ? cross(ebc, eca) : (lbc >= lca ? cross(eca, eab) : cross(eab, ebc));
+    const float nn = dot(n, n);
+    if (nn > 0.f && dot(n, cross(a, eab)) >= 0.f && dot(n, cross(b, ebc)) >= 0.f && dot(n, cross(c, eca)) >= 0.f) {
+        const float na = dot(n, a);
+        const float dp = fabsf(na) / sqrtf(nn);
+        if (dp < d) {                                // (a vertex or edge that p lies on keeps its exact 0)
+            const float s = na / nn;
+            d = dp;
+            q = {n.x * s, n.y * s, n.z * s};
+        }
+    }
+    return d;
+}
+
 // Cell of coordinate x along an axis of n cells that starts at lo, inv = 1 / cell size; a NaN lands in cell 0.
 __device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
     return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));

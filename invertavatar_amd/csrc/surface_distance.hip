@@ -48,42 +48,7 @@ constexpr int kStatVals = 6 + kMaxThr;               // count, sum, sum sq, max,
 constexpr int kStatBlocks = 1024;
 constexpr int kStatPer = 4;
 
-using V3 = ia::Vec3<float>;                         // sub, dot ((x + y) + z), cross, finite3: geom_common.h
-
-// Closest point of the segment a + t e, t in [0, 1] (ee = e . e), to the origin; kept if its squared distance is below `best`.
-__device__ __forceinline__ void seg(V3 a, V3 e, float ee, float& best, V3& q) {
-    float t = 0.f;
-    if (ee > 0.f) t = fminf(fmaxf(-dot(a, e) / ee, 0.f), 1.f);
-    const V3 r = {a.x + t * e.x, a.y + t * e.y, a.z + t * e.z};
-    const float d2 = dot(r, r);
-    if (d2 < best) { best = d2; q = r; }
-}
-
-// Distance from p to the closed triangle ABC; q: the closest point relative to p.
-__device__ __forceinline__ float tri_dist(V3 p, V3 A, V3 B, V3 C, V3& q) {
-    const V3 a = sub(A, p), b = sub(B, p), c = sub(C, p);
-    float d2 = INFINITY;
-    q = {NAN, NAN, NAN};
-    const V3 eab = sub(b, a), ebc = sub(c, b), eca = sub(a, c);
-    const float lab = dot(eab, eab), lbc = dot(ebc, ebc), lca = dot(eca, eca);
-    seg(a, eab, lab, d2, q);
-    seg(b, ebc, lbc, d2, q);
-    seg(c, eca, lca, d2, q);
-    float d = sqrtf(d2);
-    // the normal from the two shorter edges (eab x ebc = ebc x eca = eca x eab): no cancellation on needle-shaped triangles
-    const V3 n = (lab >= lbc && lab >= lca) ? cross(ebc, eca) : (lbc >= lca ? cross(eca, eab) : cross(eab, ebc));
-    const float nn = dot(n, n);
-    if (nn > 0.f && dot(n, cross(a, eab)) >= 0.f && dot(n, cross(b, ebc)) >= 0.f && dot(n, cross(c, eca)) >= 0.f) {
-        const float na = dot(n, a);
-        const float dp = fabsf(na) / sqrtf(nn);
-        if (dp < d) {                                // (a vertex or edge that p lies on keeps its exact 0)
-            const float s = na / nn;
-            d = dp;
-            q = {n.x * s, n.y * s, n.z * s};
-        }
-    }
-    return d;
-}
+using V3 = ia::Vec3<float>;                         // sub, dot ((x + y) + z), cross, finite3, tri_dist: geom_common.h
 
 struct Grid {
     const int* cell_start;       // [ncell + 1] offsets into cell_tris; null: brute mode

@@ -14,7 +14,7 @@ prints Chamfer distance, Hausdorff distance and F-score of the extracted mesh ag
 its distance to the reference; ``--align rigid|similarity`` (with ``--align-metric``, ``--align-iterations``, ``--align-trim``, ``--align-init``,
 as in ``geometry_metrics``) first moves the extracted mesh onto ``REF.ply`` with ``geometry.align_mesh``, prints the scale, the rotation angle,
 |t| and the rms before and after, and scores, colours and (``--mesh-views``) renders the error of the moved mesh; ``--signed`` and ``--iou RES`` (as in ``geometry_metrics``) add the signed distances (with a
-diverging ``--error-ply``) and the volumetric IoU against ``REF.ply``.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
+diverging ``--error-ply``) and the volumetric IoU against ``REF.ply``; ``--search tree`` (as there) takes their closest-point queries through the cluster tree.  ``--simplify N`` simplifies the mesh to at most N triangles (``geometry.simplify_mesh``: quadric vertex
 clustering; the line per seed then shows the triangle counts before and after), ``--simplify-cells C`` to a grid of C cells along the
 longest axis; ``--simplify-check`` scores the simplified mesh against the full one (``geometry.surface_distance``), prints both directed
 Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geometry.json``.  ``--smooth N`` smooths the mesh with N

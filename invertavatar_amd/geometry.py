@@ -760,16 +760,31 @@ class TriangleGrid:
         return {'dist': dist, 'face': face.long(), 'point': point}
 
 
-def closest_point(points, verts, faces, grid=None, brute=False):
+def closest_point(points, verts, faces, grid=None, brute=False, search='grid', tree=None):
     """Exact distance from points [N,3] to the triangle mesh (verts float32 [V,3], faces [F,3]): ``{'dist' float32 [N] (unsigned),
     'face' int64 [N], 'point' float32 [N,3]}``.  The distance to a triangle is the distance to the closed triangle (a triangle of zero
     area is a segment or a point; a triangle with a non-finite vertex is ignored), the distance to the mesh the minimum over its
     triangles; ``face`` is the triangle that attains the minimum (the lowest index among equal distances) and ``point`` the closest
     point on it.  A non-finite query gives NaN / -1 / NaN, a mesh without usable triangles +inf / -1 / NaN.  Device tensors run on
     ia_closest_point, through ``grid`` (a ``TriangleGrid`` of this mesh; built here if None) or, with ``brute=True``, over all triangles:
-    both give bit-identical results.  CPU tensors and NumPy arrays take the NumPy restatement (float64, brute force in chunks)."""
+    both give bit-identical results.  CPU tensors and NumPy arrays take the NumPy restatement (float64, brute force in chunks).
+
+    ``search='tree'`` takes ``WindingTree.closest`` instead: branch and bound over the cluster tree (``tree``: a ``WindingTree`` of
+    this mesh, built here if None; on the device ``grid`` only lends its packed triangles).  The tree prunes and nothing else: the same
+    bits again, fast far from the mesh where the grid walks every cell.  CPU tensors and NumPy arrays take ``_closest_tree_numpy`` in
+    float64."""
     _mesh_args(verts, faces)
-    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+    _closest_search(search)
+    if search == 'tree' and brute:
+        raise ValueError("search='tree' and brute=True exclude each other")
+    if search != 'tree' and tree is not None:
+        raise ValueError("tree is used with search='tree' only")
+    on_dev = isinstance(verts, torch.Tensor) and verts.is_cuda
+    if search == 'tree':
+        if not on_dev and faces.shape[0] and (_np(faces).min() < 0 or _np(faces).max() >= verts.shape[0]):
+            raise ValueError(f'faces index vertices outside [0, {verts.shape[0]})')
+        return _winding_tree_for(verts, faces, grid, tree).closest(points)
+    if on_dev:
         if grid is None:
             grid = TriangleGrid(verts, faces, build=not brute)
         return grid.closest(points, brute=brute)
@@ -845,7 +860,7 @@ def _sample_set(verts, faces, samples, seed, points):
 
 
 def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None,
-                     signed=False, winding='exact', beta=2.0):
+                     signed=False, winding='exact', beta=2.0, search='grid'):
     """How far surface a is from surface b.  The sample set of each mesh is its vertices (``samples=None``), ``samples`` area-weighted
     points (``sample_surface`` with ``seed`` for a and ``seed + 1`` for b) or the points given (``points_a`` / ``points_b``).  With
     ``d_ab`` the exact distances of a's samples to mesh b and ``d_ba`` those of b's samples to mesh a (``closest_point``; non-finite
@@ -865,11 +880,16 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
       samples with a finite distance (NaN when there is none).  This costs n_a F_b + n_b F_a pairs (``winding_number``);
       ``winding='tree'`` takes ``winding_number(method='tree', beta=beta)`` instead, one ``WindingTree`` per mesh.
 
+    ``search='tree'`` takes the distances through ``closest_point(search='tree')`` (the same bits; no uniform grid is built, and with
+    ``winding='tree'`` the one ``WindingTree`` per mesh serves both): the choice for meshes that do not overlap.
+
     Device meshes run on the kernels (one ``TriangleGrid`` per mesh, ia_distance_stats for the sums); CPU tensors and NumPy arrays take
     the NumPy restatements."""
     _mesh_args(verts_a, faces_a)
     _mesh_args(verts_b, faces_b)
     _winding_method(winding, 'winding')
+    _closest_search(search)
+    by_tree = search == 'tree'
     if winding == 'tree':
         _winding_beta(beta)
     use_tree = bool(signed) and winding == 'tree'
@@ -891,12 +911,13 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     fn_b = face_normals(verts_b, faces_b) if nb is not None else None
     if on_dev:
         from . import hipops
-        grid_a, grid_b = TriangleGrid(verts_a, faces_a), TriangleGrid(verts_b, faces_b)
+        grid_a, grid_b = TriangleGrid(verts_a, faces_a, build=not by_tree), TriangleGrid(verts_b, faces_b, build=not by_tree)
         stats, sides = [], []
         for pts, nrm, grid, fn in ((pa, na, grid_b, fn_b), (pb, nb, grid_a, fn_a)):
-            r = grid.closest(pts)
+            tree = WindingTree.from_grid(grid) if by_tree or use_tree else None
+            r = tree.closest(pts) if by_tree else grid.closest(pts)
             if signed:
-                sides.append((r['dist'], WindingTree.from_grid(grid).query(pts, beta) if use_tree else _winding_device(pts, None, None, grid)))
+                sides.append((r['dist'], tree.query(pts, beta) if use_tree else _winding_device(pts, None, None, grid)))
             if nrm is not None:
                 s = hipops.distance_stats(r['dist'], thresholds, r['face'].int(), nrm.float().contiguous(), fn.float().contiguous())
             else:
@@ -906,10 +927,10 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     else:
         out, sides = [], []
         for pts, nrm, v, f, fn in ((pa, na, verts_b, faces_b, fn_b), (pb, nb, verts_a, faces_a, fn_a)):
-            r = closest_point(_np(pts), _np(v), _np(f))
+            tree = WindingTree(_np(v), _np(f)) if by_tree or use_tree else None
+            r = closest_point(_np(pts), _np(v), _np(f), search=search, tree=tree if by_tree else None)
             if signed:
-                sides.append((r['dist'], WindingTree(_np(v), _np(f)).query(_np(pts), beta) if use_tree
-                              else _winding_numpy(_np(pts), _np(v), _np(f))[0]))
+                sides.append((r['dist'], tree.query(_np(pts), beta) if use_tree else _winding_numpy(_np(pts), _np(v), _np(f))[0]))
             out.append(_stats_numpy(r['dist'], thresholds, *((r['face'], _np(nrm), _np(fn)) if nrm is not None else ())))
         s_ab, s_ba = out
 
@@ -1157,7 +1178,7 @@ def _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol):
             'inliers': n, 'iterations': steps, 'converged': converged}
 
 
-def _align_numpy(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, dtype=np.float64):
+def _align_numpy(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, dtype=np.float64, search='grid'):
     """The NumPy restatement of ``align_mesh`` (the definition); ``dtype``: the precision of the closest-point search."""
     src, verts, faces = np.asarray(src, dtype=F32).reshape(-1, 3), np.asarray(verts, dtype=F32), np.asarray(faces, dtype=np.int64)
     fin = _finite_rows(verts)
@@ -1166,20 +1187,22 @@ def _align_numpy(src, verts, faces, M0, metric, scale, iterations, tol, max_dist
     lo, hi = fin.min(0).astype(np.float64), fin.max(0).astype(np.float64)
     centre, extent = (lo + hi) / 2, float(max(np.abs(lo).max(), np.abs(hi).max()))
     normals = face_normals(verts, faces) if metric == 'plane' else None
+    tree = WindingTree(verts, faces) if search == 'tree' else None
 
     def pair(M):
         p = _transform_numpy(src, M)
-        dist, face, q = _closest_numpy(p, verts, faces, dtype)
+        dist, face, q = _closest_numpy(p, verts, faces, dtype) if tree is None else _closest_tree_numpy(p, tree, dtype)[:3]
         return _align_sums_numpy(p, q, dist, face, normals, centre, _trim_threshold_numpy(dist, face, max_dist, trim), metric)
     return _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol)
 
 
-def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, grid):
+def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, grid, search='grid'):
     from . import hipops
     if not faces.shape[0] or not verts.shape[0]:
         raise ValueError('align_mesh: the target mesh is empty')
     if grid is None:
-        grid = TriangleGrid(verts, faces)
+        grid = TriangleGrid(verts, faces, build=search != 'tree')
+    finder = WindingTree.from_grid(grid) if search == 'tree' else grid
     dev = grid.verts.device
     src = src.detach().to(dev).float().reshape(-1, 3).contiguous()
     centre = [(float(a) + float(b)) / 2 for a, b in zip(grid.lo, grid.hi)]
@@ -1188,7 +1211,7 @@ def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dis
 
     def pair(M):
         p = hipops.transform_points(src, M)
-        r = grid.closest(p)
+        r = finder.closest(p)
         dist, face = r['dist'], r['face'].int()
         thr = base
         if trim < 1.0:                                                    # one more host synchronisation, for tau
@@ -1202,7 +1225,7 @@ def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dis
 
 
 def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30, tol=1e-6, max_dist=None, trim=1.0, init='identity',
-               grid=None):
+               grid=None, search='grid'):
     """Align ``source`` (points [N,3], or a ``(verts, faces)`` pair whose vertices are used) to the triangle mesh ``(verts, faces)`` by
     iterated closest points: the rigid (``scale=False``) or similarity transform ``y = s R x + t`` that brings the points onto the
     surface, as a float64 4x4 ``M`` with ``M[:3,:3] = s R``, ``M[:3,3] = t``.  ICP finds the local optimum nearest to the start, so the
@@ -1225,7 +1248,10 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
     that counted in the last pairing), 'iterations' (steps taken), 'converged'}``.  Fewer than 3 (``'point'``) or 6 (``'plane'``) pairs
     that count, or an empty target, raise ValueError.  Device tensors run on the kernels (one ``TriangleGrid`` for all iterations,
     ``grid`` if given; one host synchronisation per iteration for the sums, one more for tau when ``trim < 1``); CPU tensors and NumPy
-    arrays take the NumPy restatement, which is the definition."""
+    arrays take the NumPy restatement, which is the definition.  ``search='tree'`` takes step 2 through ``closest_point(search='tree')``
+    (one ``WindingTree`` for all iterations, no uniform grid): the same bits, and the choice for a source that starts outside the
+    target's box, where the grid walks every cell."""
+    _closest_search(search)
     if metric not in _ALIGN_MIN:
         raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
     if isinstance(source, (tuple, list)) and len(source) == 2 and getattr(source[0], 'ndim', 0) == 2:
@@ -1254,8 +1280,8 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
         M0 = _matrix44(init)
     args = (M0, metric, bool(scale), iterations, float(tol), max_dist, float(trim))
     if on_dev:
-        return _align_device(torch.as_tensor(source), verts, faces, *args, grid)
-    return _align_numpy(_np(source), _np(verts), _np(faces), *args)
+        return _align_device(torch.as_tensor(source), verts, faces, *args, grid, search)
+    return _align_numpy(_np(source), _np(verts), _np(faces), *args, search=search)
 
 
 # ------------------------------------------------------------------ winding number, signed distance, mesh -> volume
@@ -1499,6 +1525,128 @@ def _winding_tree_query_numpy(points, tris, nodes, counts, beta, dtype=np.float6
     return w, bound, big, far_n, pair_n
 
 
+# ---- closest point on the same tree (csrc/closest_tree.hip)
+
+_SEARCHES = ('grid', 'tree')
+_TREE_SLACK = 2.0 ** -17     # 64 eps32: the margin of the grid search, relative to max(|p|_inf, mesh extent)
+
+
+def _closest_search(search):
+    if search not in _SEARCHES:
+        raise ValueError(f'search must be one of {_SEARCHES}, got {search!r}')
+    return search
+
+
+def _tree_boxes_numpy(tris, counts):
+    """NumPy restatement of ia_tree_boxes: float32 [n,8] = (lo.xyz, 0, hi.xyz, 0) per node of the level layout ``counts`` over the
+    sorted usable triangles ``tris`` float32 [F_usable,3,3].  Min and max are exact: the table equals the kernel's bit for bit."""
+    t = np.asarray(tris, dtype=F32).reshape(-1, 9)
+    fu = t.shape[0]
+    out = np.zeros((sum(counts), 8), dtype=F32)
+    start = 0
+    for lvl, cnt in enumerate(counts):
+        for i in range(cnt):
+            if lvl == 0:
+                v = t[i * WINDING_LEAF:min((i + 1) * WINDING_LEAF, fu)].reshape(-1, 3)
+                lo, hi = v.min(0), v.max(0)
+            else:
+                ch = out[child0 + i * WINDING_BRANCH:child0 + min((i + 1) * WINDING_BRANCH, counts[lvl - 1])]
+                lo, hi = ch[:, 0:3].min(0), ch[:, 4:7].max(0)
+            out[start + i, 0:3], out[start + i, 4:7] = lo, hi
+        child0, start = start, start + cnt
+    return out
+
+
+def _box_dist(p, row):
+    """Distance from points [n,3] to the box of one row (or of one row per point), every operation rounded on its own."""
+    g = np.maximum(np.maximum(row[..., 0:3] - p, p - row[..., 4:7]), p.dtype.type(0))
+    return np.sqrt((g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2])
+
+
+def _closest_tree_numpy(points, tree, dtype=np.float64, slack=None):
+    """NumPy restatement of ia_closest_point_tree in ``dtype`` on a host ``WindingTree``: ``(dist [N], face int32 [N] (input face
+    indices), point [N,3], counts int64 [N,2] = boxes tested, point-triangle pairs evaluated)``.  ``best = (dist, face)`` is ordered
+    lexicographically and starts at ``(+inf, -1)``; a visited leaf evaluates ``point_triangle`` for its faces and keeps the smaller
+    pair.  A node is skipped iff ``lb`` is finite and ``lb - slack > best.dist``: ``lb`` the distance from the point to the node's box
+    (``g = max(max(lo - p, p - hi), 0)``, ``sqrt((gx^2 + gy^2) + gz^2)``), ``slack = 2^-17 max(|p|_inf, tree.extent)``.  Each point
+    first descends from the root to the child with the smallest ``lb`` (the lowest index among equals) and evaluates that leaf, then
+    walks depth first with the children in index order, passing over that leaf: the kernel's order, so ``counts`` are the kernel's.
+    The result equals ``_closest_numpy`` in the same ``dtype`` exactly: the tree only prunes.  ``slack`` (tests): one value for every
+    point instead."""
+    if tree.device is not None:
+        raise ValueError('_closest_tree_numpy restates the query on a host WindingTree')
+    p32 = np.asarray(points, dtype=F32).reshape(-1, 3)
+    p = p32.astype(dtype)
+    t = np.asarray(tree.tris, dtype=F32).reshape(-1, 3, 3).astype(dtype)
+    order = np.asarray(tree.order, dtype=np.int64)
+    counts, boxes = list(tree.counts), np.asarray(tree.boxes, dtype=F32).astype(dtype)
+    n, fu = p.shape[0], t.shape[0]
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    ok = np.isfinite(p32).all(1)
+    best_d, best_f, best_at = np.full(n, np.inf, dtype=dtype), np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+    n_box, n_pair = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        if slack is None:
+            margin = dtype(_TREE_SLACK) * np.maximum(np.abs(p).max(1) if n else np.zeros(0, dtype=dtype), dtype(tree.extent))
+        else:
+            margin = np.full(n, slack, dtype=dtype)
+
+        def leaf(j, r):
+            sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, fu))
+            d, _ = point_triangle(p[r, None, :], t[None, sl, 0], t[None, sl, 1], t[None, sl, 2], dtype)
+            d = np.where(np.isnan(d), np.inf, d)
+            faces = order[sl]
+            dm = d.min(1)
+            tie = d == dm[:, None]
+            fm = np.where(tie, faces[None, :], np.iinfo(np.int64).max).min(1)                # the lowest input index among equals
+            at = sl.start + np.argmax(tie & (faces[None, :] == fm[:, None]), axis=1)
+            take = (dm < best_d[r]) | ((dm == best_d[r]) & (fm < best_f[r]))
+            rr = r[take]
+            best_d[rr], best_f[rr], best_at[rr] = dm[take], fm[take], at[take]
+            n_pair[r] += sl.stop - sl.start
+
+        rows = np.flatnonzero(ok) if counts else np.zeros(0, dtype=np.int64)
+        seed = np.full(n, -1, dtype=np.int64)
+        if rows.size:
+            j = np.zeros(rows.size, dtype=np.int64)
+            for lvl in range(len(counts) - 1, 0, -1):
+                least, pick = np.full(rows.size, np.inf, dtype=dtype), j * WINDING_BRANCH
+                for c in range(WINDING_BRANCH):
+                    k = j * WINDING_BRANCH + c
+                    valid = k < counts[lvl - 1]
+                    lb = _box_dist(p[rows], boxes[starts[lvl - 1] + np.minimum(k, counts[lvl - 1] - 1)])
+                    less = valid & (lb < least)
+                    least, pick = np.where(less, lb, least), np.where(less, k, pick)
+                    n_box[rows] += valid
+                j = pick
+            seed[rows] = j
+            for leaf_j in np.unique(j):
+                leaf(int(leaf_j), rows[j == leaf_j])
+        stack = [(len(counts) - 1, 0, rows)] if rows.size else []
+        while stack:
+            lvl, j, idx = stack.pop()
+            if lvl == 0:
+                idx = idx[seed[idx] != j]
+            lb = _box_dist(p[idx], boxes[starts[lvl] + j])
+            n_box[idx] += 1
+            r = idx[~(np.isfinite(lb) & (lb - margin[idx] > best_d[idx]))]
+            if not r.size:
+                continue
+            if lvl == 0:
+                leaf(j, r)
+            else:
+                k1 = min((j + 1) * WINDING_BRANCH, counts[lvl - 1])
+                stack.extend((lvl - 1, k, r) for k in range(k1 - 1, j * WINDING_BRANCH - 1, -1))
+        hit = best_f >= 0
+        at = np.where(hit, best_at, 0)
+        point = np.full((n, 3), np.nan, dtype=dtype)
+        if fu and hit.any():
+            _, q = point_triangle(p, t[at, 0], t[at, 1], t[at, 2], dtype)
+            point = np.where(hit[:, None], p + q, np.nan).astype(dtype)
+    best_d[~ok] = np.nan
+    return best_d, best_f.astype(np.int32), point, np.stack([n_box, n_pair], -1)
+
+
 class WindingTree:
     """The cluster tree of one mesh for ``winding_number(method='tree')``, built once: ``order`` (sorted position -> input face: the
     usable faces by the 30-bit Morton key of their centroid, ties by face index, then the unusable ones), ``tris`` (the triangles in
@@ -1519,8 +1667,11 @@ class WindingTree:
                 grid = TriangleGrid(verts, faces, build=False)
             lo, scale = _morton_cube(grid.lo, grid.hi)
             self.order, self.tris, self.nodes, self.counts, self.usable = hipops.winding_tree_build(grid.tris, lo.tolist(), float(scale))
+            self.extent = float(grid.extent)
         else:
             t = _winding_tree_numpy(_np(verts), _np(faces))
+            fin = _finite_rows(np.asarray(_np(verts), dtype=F32).reshape(-1, 3))
+            self.extent = float(np.abs(fin).max()) if fin.shape[0] else 0.0
             lo, scale = t['lo'], t['scale']
             self.order, self.tris, self.counts, self.usable = t['order'], t['tris'], t['counts'], t['usable']
             self.nodes64 = t['nodes64']
@@ -1528,6 +1679,7 @@ class WindingTree:
         self.lo, self.scale = [float(x) for x in lo], float(scale)
         self.info = {'faces': int(faces.shape[0]), 'usable': int(self.usable), 'levels': len(self.counts), 'nodes': int(sum(self.counts)),
                      'leaf': WINDING_LEAF, 'branch': WINDING_BRANCH}
+        self._boxes = self._order32 = None
 
     @classmethod
     def from_grid(cls, grid):
@@ -1566,6 +1718,51 @@ class WindingTree:
             if return_counts:
                 out.append(_as_out(np.stack([nf, npair], -1).reshape(lead + (2,)), points, np.int64))
         return out[0] if len(out) == 1 else tuple(out)
+
+
+    @property
+    def boxes(self):
+        """float32 [n,8]: the bounding box (lo.xyz, 0, hi.xyz, 0) of every node, built on first use (ia_tree_boxes on the device,
+        ``_tree_boxes_numpy`` on the host); what ``closest`` prunes with."""
+        if self._boxes is None:
+            if self.device is not None:
+                from . import hipops
+                self._boxes = hipops.tree_boxes(self.tris, self.usable, int(sum(self.counts)))
+            else:
+                self._boxes = _tree_boxes_numpy(self.tris, self.counts)
+        return self._boxes
+
+    def closest(self, points, return_counts=False, sort=True):
+        """``{'dist' [...], 'face' int64 [...], 'point' [..., 3]}`` of points [..., 3]: what ``closest_point`` gives (the same bits),
+        by branch and bound over the tree (``_closest_tree_numpy`` is the definition); with ``return_counts`` also ``'counts'`` int
+        [..., 2] (boxes tested, point-triangle pairs evaluated).  ``sort`` (device): query in Morton order of the points and return in
+        the caller's order; it changes no result.  A host tree answers in float64."""
+        lead = tuple(points.shape[:-1])
+        if self.device is not None:
+            from . import hipops
+            pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
+            if self._order32 is None:
+                self._order32 = self.order.int().contiguous()
+            perm = None
+            if sort and pts.shape[0] > 64:
+                perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
+                pts = pts[perm].contiguous()
+            res = hipops.closest_point_tree(pts, self.tris, self._order32, self.boxes, self.usable, self.extent, counts=return_counts)
+            if perm is not None:
+                back = torch.empty_like(perm)
+                back[perm] = torch.arange(perm.numel(), device=perm.device)
+                res = [None if x is None else x[back] for x in res]
+            dist, face, point, cnt = res
+            out = {'dist': dist.reshape(lead), 'face': face.long().reshape(lead), 'point': point.reshape(lead + (3,))}
+            if return_counts:
+                out['counts'] = cnt.reshape(lead + (2,))
+        else:
+            dist, face, point, cnt = _closest_tree_numpy(_np(points), self)
+            out = {'dist': _as_out(dist.reshape(lead), points), 'face': _as_out(face.reshape(lead), points, np.int64),
+                   'point': _as_out(point.reshape(lead + (3,)), points)}
+            if return_counts:
+                out['counts'] = _as_out(cnt.reshape(lead + (2,)), points, np.int64)
+        return out
 
 
 def _winding_tree_for(verts, faces, grid, tree):
@@ -1614,16 +1811,22 @@ def inside(points, verts, faces, threshold=0.5, method='exact', beta=2.0, tree=N
     return winding_number(points, verts, faces, method=method, beta=beta, tree=tree) >= threshold
 
 
-def signed_distance(points, verts, faces, grid=None, threshold=0.5, method='exact', beta=2.0, tree=None):
+def signed_distance(points, verts, faces, grid=None, threshold=0.5, method='exact', beta=2.0, tree=None, search='grid'):
     """Signed distance of points to a mesh: ``{'sdf', 'dist', 'face', 'point', 'winding'}``.  ``dist``, ``face`` and ``point`` are the
     results of ``closest_point`` (the same bits), ``winding`` (float64) is ``winding_number`` and ``sdf`` is ``-dist`` where
     ``winding >= threshold``, else ``+dist``: negative inside.  ``grid``: a ``TriangleGrid`` of the mesh (device), used by both.
-    ``method`` / ``beta`` / ``tree``: those of ``winding_number``."""
+    ``method`` / ``beta`` / ``tree``: those of ``winding_number``.  ``search``: that of ``closest_point``; with ``search='tree'`` no
+    uniform grid is built, and with ``method='tree'`` as well one ``WindingTree`` (``tree``, or built here) gives sign and magnitude."""
     _mesh_args(verts, faces)
     _winding_method(method)
+    _closest_search(search)
     if _is_device(verts) and grid is None:
-        grid = TriangleGrid(verts, faces)
-    r = closest_point(points, verts, faces, grid=grid)
+        grid = TriangleGrid(verts, faces, build=search != 'tree')
+    if search == 'tree':
+        tree = _winding_tree_for(verts, faces, grid, tree)
+        r = tree.closest(points)
+    else:
+        r = closest_point(points, verts, faces, grid=grid)
     w = winding_number(points, verts, faces, grid=grid, method=method, beta=beta, tree=tree).reshape(r['dist'].shape)
     neg = w >= threshold
     sdf = torch.where(neg, -r['dist'], r['dist']) if isinstance(neg, torch.Tensor) else np.where(neg, -r['dist'], r['dist'])
@@ -1699,7 +1902,8 @@ def _mesh_is_closed(verts, faces):
     return int(info['boundary_edges']) == 0 and int(info['nonmanifold_edges']) == 0
 
 
-def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=2, sign='auto', threshold=0.5, winding='exact', beta=2.0):
+def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=2, sign='auto', threshold=0.5, winding='exact', beta=2.0,
+                   search='grid'):
     """A triangle mesh as a signed distance lattice: ``{'sdf' float32 [nx,ny,nz] (negative inside), 'inside' bool [nx,ny,nz],
     'origin', 'spacing', 'info'}``.  The lattice is that of ``marching_cubes``: point (i, j, k) at ``origin + index * spacing`` in fp32,
     volumes indexed [i, j, k] with z fastest, so ``marching_cubes(-sdf, 0, origin, spacing)`` remeshes the surface.  With ``origin``
@@ -1718,7 +1922,8 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
       (The test is on edges, not on orientation: the faces of a closed mesh must be wound consistently.)
 
     ``winding='tree'`` evaluates every one of those winding numbers (the band, the regions, ``sign='winding'``) through a
-    ``WindingTree`` with ``beta`` (``winding_number(method='tree')``) instead of the exact sum.
+    ``WindingTree`` with ``beta`` (``winding_number(method='tree')``) instead of the exact sum.  ``search='tree'`` takes the magnitude
+    through ``closest_point(search='tree')``: the same bits, no uniform grid, and with ``winding='tree'`` one tree for both.
 
     ``info``: ``{'mode', 'regions', 'band', 'evaluations', 'winding'}``: the mode taken, the number of components, the points of the
     band, the number of winding-number evaluations and how they were made.  Device tensors run on the kernels; CPU tensors and NumPy
@@ -1727,6 +1932,7 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
     if sign not in _SIGN_MODES:
         raise ValueError(f'sign must be one of {_SIGN_MODES}, got {sign!r}')
     _winding_method(winding, 'winding')
+    _closest_search(search)
     if winding == 'tree':
         _winding_beta(beta)
     on_dev = _is_device(verts)
@@ -1741,10 +1947,11 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
     tau = float(F32(max(spc) / 2 + 64 * EPS32 * extent))
     if on_dev:
         dev = verts.device
-        grid = TriangleGrid(verts, faces)
+        grid = TriangleGrid(verts, faces, build=search != 'tree')
         pts = torch.stack(torch.meshgrid(*[torch.from_numpy(ax).to(dev) for ax in axes], indexing='ij'), -1).reshape(-1, 3).contiguous()
-        dist = grid.closest(pts)['dist']
-        tree = WindingTree.from_grid(grid) if winding == 'tree' else None
+        finder = WindingTree.from_grid(grid) if search == 'tree' or winding == 'tree' else None
+        dist = (finder if search == 'tree' else grid).closest(pts)['dist']
+        tree = finder if winding == 'tree' else None
 
         def wind(idx):
             sel = pts if idx is None else pts[idx]
@@ -1753,8 +1960,9 @@ def mesh_to_volume(verts, faces, resolution, origin=None, spacing=None, padding=
         grid = None
         v_np, f_np = _np(verts), _np(faces)
         pts = np.ascontiguousarray(np.stack(np.meshgrid(*axes, indexing='ij'), -1).reshape(-1, 3))
-        dist = _closest_numpy(pts, v_np, f_np)[0].astype(F32)
-        tree = WindingTree(v_np, f_np) if winding == 'tree' else None
+        finder = WindingTree(v_np, f_np) if search == 'tree' or winding == 'tree' else None
+        dist = (_closest_tree_numpy(pts, finder) if search == 'tree' else _closest_numpy(pts, v_np, f_np))[0].astype(F32)
+        tree = finder if winding == 'tree' else None
 
         def wind(idx):
             sel = pts if idx is None else pts[idx]

@@ -13,7 +13,9 @@ centroid`` or a pose from landmarks (``geometry.fit_transform``).  ``--signed`` 
 colours ``--error-ply`` with a diverging map (blue inside the ground truth, red outside, white on it).  ``--iou RES`` adds a
 ``volume_iou`` block: the volumetric IoU of the two meshes on a lattice of ``RES`` points along the longest axis.  ``--winding tree``
 (with ``--winding-beta B``, default 2) makes the winding numbers behind both with ``geometry.WindingTree`` instead of the exact all-pairs
-sum: the route for meshes of hundreds of thousands of faces.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
+sum: the route for meshes of hundreds of thousands of faces.  ``--search tree`` takes every closest-point query (the distances, the
+alignment, the IoU lattice, the colours) through ``geometry.closest_point(search='tree')``: the same numbers bit for bit, for meshes that
+lie far apart, where the uniform grid walks every cell; the JSON then records ``search: tree``.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
 import argparse
 import json
 import math
@@ -70,58 +72,66 @@ def alignment_block(fit):
 
 
 def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None, align=None, align_options=None,
-                   save_aligned=None, aligned=None, signed=False, iou=None, winding='exact', beta=2.0):
+                   save_aligned=None, aligned=None, signed=False, iou=None, winding='exact', beta=2.0, search='grid'):
     """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance.
     ``align``: 'rigid' or 'similarity' moves the mesh onto the reference first (``align_prediction`` with ``align_options``); the moved
     mesh is scored (and coloured), the result gains ``alignment`` (``alignment_block``), ``save_aligned`` is a PLY path for the moved mesh
     and ``aligned``, a dict, receives its ``verts`` and the ``matrix``.  ``signed``: the signed keys of ``surface_distance`` and a
     diverging ``error_ply`` (``signed_error_colors``); ``iou``: a lattice resolution, adds ``volume_iou`` of the (moved) mesh and the
     reference.  ``winding='tree'``: the winding numbers behind ``signed`` and ``iou`` come from ``geometry.WindingTree`` with ``beta``
-    (the approximation for large meshes) and the result gains ``winding: {'method', 'beta'}``."""
+    (the approximation for large meshes) and the result gains ``winding: {'method', 'beta'}``.  ``search='tree'``: every closest-point
+    query goes through the cluster tree (``geometry.closest_point``; the same bits) and the result gains ``search: 'tree'``."""
     tree = {'winding': winding, 'beta': beta} if winding != 'exact' else {}
+    how = {'search': geometry._closest_search(search)} if search != 'grid' else {}
     alignment = None
     if align is not None:
-        verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, align_options)
+        verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, {**dict(align_options or {}), **how})
         alignment = alignment_block(fit)
         if save_aligned:
             geometry.write_ply(save_aligned, verts, faces)
         if aligned is not None:
             aligned.update(verts=verts, matrix=fit['matrix'])
     res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds,
-                                    **({'signed': True, **tree} if signed else {}))
+                                    **({'signed': True, **tree} if signed else {}), **how)
     if tree:
         res['winding'] = {'method': winding, 'beta': float(beta)}
+    if how:
+        res['search'] = search
     res.update(pred_vertices=int(verts.shape[0]), pred_faces=int(faces.shape[0]), gt_vertices=int(ref_verts.shape[0]),
                gt_faces=int(ref_faces.shape[0]))
     if alignment is not None:
         res['alignment'] = alignment
     if iou is not None:
-        res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou), **tree)
+        res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou), **tree, **how)
     if error_ply:
         scale = res['thresholds'][-1] if res['thresholds'] else 1.0
         if signed:
-            sdf = geometry.signed_distance(verts, ref_verts, ref_faces, **({'method': winding, 'beta': beta} if tree else {}))['sdf']
+            sdf = geometry.signed_distance(verts, ref_verts, ref_faces, **({'method': winding, 'beta': beta} if tree else {}), **how)['sdf']
             geometry.write_ply(error_ply, verts, faces, signed_error_colors(geometry._np(sdf), scale))
         else:
-            dist = geometry.closest_point(verts, ref_verts, ref_faces)['dist']
+            dist = geometry.closest_point(verts, ref_verts, ref_faces, **how)['dist']
             geometry.write_ply(error_ply, verts, faces, error_colors(geometry._np(dist), scale))
     return res
 
 
 def add_sign_arguments(ap):
-    """``--signed``, ``--iou`` and how their winding numbers are made (``--winding``, ``--winding-beta``), shared with extract_geometry."""
+    """``--signed``, ``--iou``, how their winding numbers are made (``--winding``, ``--winding-beta``) and how closest points are searched
+    (``--search``), shared with extract_geometry."""
     ap.add_argument('--signed', action='store_true', help='add signed distances (negative inside the reference); diverging --error-ply')
     ap.add_argument('--iou', type=int, default=None, metavar='RES', help='add the volumetric IoU on a lattice of RES points along the longest axis')
     ap.add_argument('--winding', default='exact', choices=['exact', 'tree'],
                     help="winding numbers of --signed / --iou: the exact sum, or the cluster tree with a far field (large meshes)")
     ap.add_argument('--winding-beta', type=float, default=2.0, metavar='B',
                     help='with --winding tree: a node farther than B times its radius is taken as far (> 1; larger is more accurate)')
+    ap.add_argument('--search', default='grid', choices=['grid', 'tree'],
+                    help='closest-point queries: the uniform grid, or branch and bound on the cluster tree (the same numbers; meshes far apart)')
 
 
 def sign_options_of(args):
-    """The keyword arguments of ``compare_meshes`` for ``--signed`` / ``--iou`` / ``--winding tree``; empty without them."""
+    """The keyword arguments of ``compare_meshes`` for ``--signed`` / ``--iou`` / ``--winding tree`` / ``--search tree``; empty without them."""
     return {**({'signed': True} if args.signed else {}), **({'iou': args.iou} if args.iou is not None else {}),
-            **({'winding': args.winding, 'beta': args.winding_beta} if args.winding != 'exact' else {})}
+            **({'winding': args.winding, 'beta': args.winding_beta} if args.winding != 'exact' else {}),
+            **({'search': args.search} if args.search != 'grid' else {})}
 
 
 def add_align_arguments(ap):

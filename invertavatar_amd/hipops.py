@@ -1918,6 +1918,50 @@ def winding_tree_query(points, sorted_tris, nodes, n_usable, beta=2.0, bound=Fal
     return out, bnd, cnt
 
 
+# ------------------------------------------------------------------ closest point on the tree (csrc/closest_tree.hip)
+
+TREE_BOX_ROW = 8             # floats per box row: (lo.xyz, 0) (hi.xyz, 0)
+
+
+def tree_boxes(sorted_tris, n_usable, n_nodes):
+    """Bounding boxes float32 [n_nodes, 8] of the nodes of the tree over ``sorted_tris`` (see ia_tree_boxes)."""
+    _tris_checked(sorted_tris)
+    if not 0 <= int(n_usable) <= sorted_tris.shape[0]:
+        raise RuntimeError(f'n_usable must be within the {sorted_tris.shape[0]} triangles, got {n_usable}')
+    dev = sorted_tris.device
+    boxes = torch.empty(int(n_nodes), TREE_BOX_ROW, device=dev)
+    with torch.cuda.device(dev), _Timed('tree_boxes', 0.0, 48.0 * int(n_usable) + 64.0 * int(n_nodes), f'F={int(n_usable)} nodes={int(n_nodes)}'):
+        st = _lib.load().ia_tree_boxes(_p(sorted_tris), int(n_usable), _p(boxes), int(n_nodes), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_tree_boxes')
+    return boxes
+
+
+def closest_point_tree(points, sorted_tris, order, boxes, n_usable, mesh_extent, counts=False):
+    """Closest triangle per point through the tree (see ia_closest_point_tree): points float32 [N,3], ``sorted_tris`` / ``n_usable``
+    from ``winding_tree_build``, ``order`` int32 (sorted position -> input face), ``boxes`` from ``tree_boxes`` -> (dist [N], face
+    int32 [N]: input face indices, point [N,3], counts int32 [N,2] or None)."""
+    _f32c(points, 'points')
+    _tris_checked(sorted_tris)
+    _i32c(order, 'order')
+    _f32c(boxes, 'boxes')
+    dev = points.device
+    if points.dim() != 2 or points.shape[1] != 3 or any(t.device != dev for t in (sorted_tris, order, boxes)):
+        raise RuntimeError(f'points must be [N,3] on the device of the tree, got {tuple(points.shape)} on {dev}')
+    if boxes.dim() != 2 or boxes.shape[1] != TREE_BOX_ROW or not 0 <= int(n_usable) <= min(sorted_tris.shape[0], order.numel()):
+        raise RuntimeError(f'boxes must be [n,{TREE_BOX_ROW}] and n_usable within the triangles and the order, got {tuple(boxes.shape)} and '
+                           f'{n_usable}')
+    n = points.shape[0]
+    dist = torch.empty(n, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    point = torch.empty(n, 3, device=dev)
+    cnt = torch.empty(n, 2, dtype=torch.int32, device=dev) if counts else None
+    with torch.cuda.device(dev), _Timed('closest_point_tree', 0.0, 32.0 * n, f'N={n} F={int(n_usable)}'):
+        st = _lib.load().ia_closest_point_tree(_p(points), n, _p(sorted_tris), _p(order), int(n_usable), _p(boxes), boxes.shape[0],
+                                               float(mesh_extent), _p(dist), _p(face), _p(point), _p(cnt), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_closest_point_tree')
+    return dist, face, point, cnt
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

@@ -1215,6 +1215,40 @@ int ia_tree_boxes(const void* sorted, int64_t F_usable, void* boxes, int64_t n_n
 int ia_closest_point_tree(const float* points, int64_t N, const void* sorted, const int* order, int64_t F_usable, const void* boxes,
                           int64_t n_nodes, float mesh_extent, float* dist, int* face, float* point, int* counts, void* stream);
 
+/*
+ * Texture atlas of a triangle mesh (csrc/texture.hip; no counterpart in the reference; definition: geometry.TextureAtlas,
+ * atlas_points, project_texture and sample_texture with their NumPy restatements).  Additive entry points: the ABI
+ * version is unchanged.  The texture is size x size texels (4 <= size <= 16384), texel (i, j) = column i, row j, stored [j][i]; faces
+ * 2b and 2b + 1 share the square block b of side s >= 4 at ((b % G) s, (b / G) s), G = size / s, 2 G^2 >= F; L = s - 3.  Inside a
+ * block the lower face owns li + lj <= s - 1 (corners (0, 0), (L, 0), (0, L)), the upper face li + lj >= s (corners (s-1, s-1),
+ * (2, s-1), (s-1, 2)); every other texel is unowned.  fp32, every operation rounded on its own; all launches go to `stream`.
+ *
+ * ia_atlas_points: per texel face int32 (-1: unowned), bary float32 [3] = ((1 - l1) - l2, l1 = a / L, l2 = c / L) with (a, c) the
+ * texel's offset from corner 0 along the two legs (negative l0 on the guard texels: extrapolated, not clamped), point float32 [3] =
+ * (l0 A + l1 B) + l2 C and normal float32 [3]: the unit (B - A) x (C - A), or with normals float32 [V,3] their normalised mix; 0 for
+ * a face whose cross product has no finite positive length or that indexes outside [0, V).  *degenerate (device int32) counts those
+ * faces.  Unowned texels are 0 / -1.
+ * ia_texture_project: for T texels (point, normal, face as above) and N <= 256 views: images float32 [N,H,W,C], C <= 8, cams float32
+ * [N,25] (the last row of K is taken as [0, 0, 1]), depth float32 and mask uint8 [N,H,W] of ia_mesh_resolve.  A view passes a texel
+ * if its projection (that of ia_mesh_project without the snap) is usable with u in [0, W - 1] and v in [0, H - 1], c = n . (o - X) /
+ * |o - X| > min_cos, and at pixel (rint u, rint v) mask is set and ||o - X| - depth| <= depth_tol.  Its colour is the bilinear read of
+ * the image at (u, v), its weight w = c^power (an integer power <= 64: the product ((c c) c) ...; any other: the fp32 rounding of the
+ * double pow).  best = 0: texture = (float)(sum_k (double)(w colour) / sum_k (double)w) in view order, weight = (float)sum w;
+ * best = 1: colour and weight of the largest w, the lowest view among equals.  views int32 = views passed, filled uint8 = views > 0;
+ * a texel no view passes takes fallback float32 [T,C] (or 0 when NULL) and weight 0.
+ * ia_texture_sample: out float32 [P,C] (C <= 64) = the bilinear read of texture float32 [size,size,C] at the uv mix
+ * (b0 uv0 + b1 uv1) + b2 uv2 of the corners of face[p] (uv = (x + 0.5) / size), x = u size - 0.5 clamped into the face's block, so
+ * that all four texels lie inside it; 0 where face[p] is outside [0, F).
+ */
+int ia_atlas_points(const float* verts, int64_t V, const int* faces, int64_t F, int size, int s, const float* normals, float* point,
+                    int* face, float* bary, float* normal, int* degenerate, void* stream);
+int ia_texture_project(const float* point, const float* normal, const int* face, int64_t T, const float* images, const float* cams, int N,
+                       int H, int W, int C, const float* depth, const unsigned char* mask, float near, float min_cos, double power,
+                       float depth_tol, int best, const float* fallback, float* texture, float* weight, int* views, unsigned char* filled,
+                       void* stream);
+int ia_texture_sample(const float* texture, int size, int C, int s, int64_t F, const int* face, const float* bary, int64_t P, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,12 @@ unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  ``--mesh-view
 ``--simplify`` and ``--smooth``) from the same orbit through ``geometry.rasterize_mesh`` and writes the shaded views as
 ``seed%04d_meshview%02d.png``, the coloured ones as ``seed%04d_meshrgb%02d.png`` (unless ``--no-colors``) and, with ``--compare
 --error-ply``, the error-coloured mesh as ``seed%04d_errorview%02d.png``; ``--save-depth`` adds ``seed%04d_meshdepth.npy``; a line per
-seed reports the surface pixels and the culled triangles (``--views`` keeps rendering the volume).  Runs on the device when there is one."""
+seed reports the surface pixels and the culled triangles (``--views`` keeps rendering the volume).  ``--texture SIZE`` bakes the colours of
+the FINAL mesh into a SIZE^2 texture atlas (``geometry.TextureAtlas``) and writes ``seed%04d.obj``, ``.mtl`` and ``.png`` beside the PLY:
+``--texture-source decoder`` (default) queries the decoder at every texel, ``views`` projects ``--texture-views`` rendered images of the
+orbit onto the mesh (``--texture-mode blend|best``) with the decoder bake as the fallback; with ``--mesh-views`` the mesh is also rendered
+through the texture (``seed%04d_meshtex%02d.png``); a line per seed reports the block side, the share of filled texels and the views per
+texel.  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -110,6 +115,10 @@ def main(argv=None):
     ap.add_argument('--smooth-mu', type=parse_mu, default=-0.53, help="the negative factor of a pair, or 'none' for plain Laplacian steps")
     ap.add_argument('--smooth-weights', default='uniform', choices=['uniform', 'cotangent'])
     ap.add_argument('--smooth-check', action='store_true', help='with --smooth: signed volume before and after, distance to the unsmoothed mesh')
+    ap.add_argument('--texture', type=int, default=None, metavar='SIZE', help='bake the colours of the final mesh into a SIZE^2 texture atlas; writes .obj/.mtl/.png')
+    ap.add_argument('--texture-source', default='decoder', choices=['decoder', 'views'], help='colours from the decoder, or projected from rendered views')
+    ap.add_argument('--texture-views', type=int, default=8, help='with --texture-source views: the number of views of the yaw orbit')
+    ap.add_argument('--texture-mode', default='blend', choices=['blend', 'best'], help='with --texture-source views: blend the views or take the best')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -128,11 +137,25 @@ def main(argv=None):
         ap.error('--signed and --iou need --compare')
     smooth = None if args.smooth is None else {'iterations': args.smooth, 'lam': args.smooth_lambda, 'mu': args.smooth_mu,
                                                'weights': args.smooth_weights}
+    texture = {}
+    if args.texture is not None:
+        texture = {'texture': {'size': args.texture, 'source': args.texture_source, 'n_views': args.texture_views, 'mode': args.texture_mode}}
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
-                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, smooth=smooth, noise_mode='const')[0]
+                                 with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, smooth=smooth, noise_mode='const',
+                                 **texture)[0]
         path = os.path.join(args.outdir, f'seed{seed:04d}.ply')
         geometry.write_ply(path, out['verts'], out['faces'], out.get('colors'), out.get('normals'))
+        if 'texture' in out:
+            obj = os.path.join(args.outdir, f'seed{seed:04d}.obj')
+            geometry.write_obj(obj, out['verts'], out['faces'], out['uv'], out['texture'], out.get('normals'))
+            info, atlas = out['texture_info'], out['atlas']
+            owned = max(int(info['mask'].sum()), 1)
+            line = (f'seed {seed}: texture {atlas.size}^2, blocks of side {atlas.s} ({atlas.G} per row), {int(info["filled"].sum()) / owned:.1%} of '
+                    f'{owned} owned texels filled')
+            if 'views' in info:
+                line += f' from views, {float(info["views"][info["mask"]].float().mean()):.2f} views per texel'
+            print(f'{line} -> {obj}')
         if args.save_volume:
             np.save(os.path.join(args.outdir, f'seed{seed:04d}.npy'), out['volume'].cpu().numpy())
         print(f'seed {seed}: {out["verts"].shape[0]} vertices, {out["faces"].shape[0]} triangles -> {path}')
@@ -220,6 +243,11 @@ def main(argv=None):
                 err_cols = torch.from_numpy(geometry.read_ply(os.path.join(args.outdir, f'seed{seed:04d}_error.ply'))[2]).to(out['verts'].device)
                 err_verts = out['aligned']['verts'] if args.align else out['verts']
                 err_rgb = to8(G.render_mesh(err_verts, out['faces'], cams, resolution=args.render_res, colors=err_cols)['rgb'].permute(0, 2, 3, 1))
+            if 'texture' in out:
+                tex_rgb = to8(G.render_mesh(out['verts'], out['faces'], cams, resolution=args.render_res, texture=out['texture'],
+                                            atlas=out['atlas'])['rgb'].permute(0, 2, 3, 1))
+                for k in range(args.mesh_views):
+                    Image.fromarray(tex_rgb[k], mode='RGB').save(os.path.join(args.outdir, f'seed{seed:04d}_meshtex{k:02d}.png'))
             for k in range(args.mesh_views):
                 Image.fromarray(shaded[k], mode='L').save(os.path.join(args.outdir, f'seed{seed:04d}_meshview{k:02d}.png'))
                 if rgb is not None:

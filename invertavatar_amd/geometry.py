@@ -44,6 +44,12 @@ query helpers of inversion/model_utils.py:90-165), not the tool.  Here:
   ``ia_volume_components``; CPU tensors and NumPy arrays take the NumPy restatement that is the definition.  ``WindingTree`` and
   ``method='tree'`` / ``winding='tree'`` are the approximation for large meshes (csrc/winding_tree.hip: a Morton-sorted cluster tree
   whose far nodes are a dipole and its first derivative); the exact sum stays the default and what the tree is held to.
+- ``TextureAtlas`` / ``atlas_points`` / ``bake_texture`` / ``bake_colors`` / ``project_texture`` / ``sample_texture``: the colours of
+  the avatar on a texture of the mesh: two triangles to a square block with a guard texel (no chart bleeds into another under a bilinear
+  lookup), the surface point of every texel, a bake from any function of position (the decoder, a distance), projective texturing from
+  rendered views with the rasteriser's depth as the visibility test, and the lookup.  Device tensors go to ``ia_atlas_points`` +
+  ``ia_texture_project`` + ``ia_texture_sample`` (csrc/texture.hip); CPU tensors and NumPy arrays take the NumPy restatement that is the
+  definition.  ``write_obj`` / ``read_obj``: OBJ + MTL + PNG.
 - ``write_ply`` / ``read_ply``: binary little-endian PLY in NumPy (optionally with vertex normals).
 
 Rasteriser: pixel centres are at integer coordinates, column i and row j of ``RaySampler_zxc`` (ray ``K_res^-1 [i, j, 1]``), so its images
@@ -2849,6 +2855,363 @@ def rasterize_mesh(verts, faces, cameras, resolution, normals=None, attributes=N
     return {k: None if x is None else _as_out(x, verts, kinds.get(k, dtype)) for k, x in out.items()}
 
 
+# ------------------------------------------------------------------ texture atlas
+
+TEXTURE_MIN_BLOCK = 4
+TEXTURE_MAX_CHANNELS = 8        # image channels of ``project_texture``
+TEXTURE_DEPTH_TOL = 16.0        # default ``depth_tol`` = this times mesh extent / max(H, W): measured, see ``project_texture``
+_TEXTURE_MODES = ('blend', 'best')
+
+
+class TextureAtlas:
+    """The texture layout of a mesh of ``n_faces`` triangles on ``size`` x ``size`` texels; integer arithmetic only, the same on host and
+    device (csrc/texture.hip).  Texel (i, j) is column i, row j, stored ``[j, i]``; coordinates are centre coordinates
+    x = u size - 0.5, so texel i has x = i.
+
+    Faces 2b and 2b + 1 share the square block b of side ``s`` at ((b % G) s, (b // G) s), G = size // s; ``s`` is ``block``, or the
+    largest integer with G^2 >= ceil(F / 2); s >= 4 or ValueError (it names the smallest size that fits).  With L = s - 3 and (li, lj)
+    the position inside the block, the lower face has its corners at (0, 0), (L, 0), (0, L) and owns li + lj <= s - 1; the upper face
+    has them at (s-1, s-1), (2, s-1), (s-1, 2) (the lower chart turned by 180 degrees, not mirrored) and owns li + lj >= s.  Texels
+    outside the G s square, in blocks past the last face and in the upper half of the last block of an odd F are unowned (-1).  The four
+    texels of a bilinear lookup at any point of a face's uv triangle are owned by that face: lower floor(x) + floor(y) + 2 <= L + 2 =
+    s - 1, upper floor(x) + floor(y) > s - 1, so no lookup mixes two charts and no dilation pass is needed.
+
+    Attributes: ``n_faces``, ``size``, ``s``, ``G``, ``uv`` float32 [F,3,2] ((x + 0.5) / size of the corners; row 0 of a texture at v = 0)."""
+
+    def __init__(self, n_faces, size, block=None):
+        import math
+        self.n_faces, self.size = int(n_faces), int(size)
+        if self.n_faces < 0 or self.size < 1:
+            raise ValueError(f'n_faces must be >= 0 and size >= 1, got {n_faces}, {size}')
+        need = max(-(-self.n_faces // 2), 1)
+        g = math.isqrt(need - 1) + 1                                      # the fewest blocks per side
+        if block is not None and int(block) < TEXTURE_MIN_BLOCK:
+            raise ValueError(f'block must be >= {TEXTURE_MIN_BLOCK}, got {block}')
+        self.s = int(block) if block is not None else self.size // g
+        self.G = self.size // self.s if self.s > 0 else 0
+        if self.s < TEXTURE_MIN_BLOCK or self.G < g:
+            fit = g * (int(block) if block is not None else TEXTURE_MIN_BLOCK)
+            raise ValueError(f'{self.n_faces} faces need {g} x {g} blocks of side {fit // g}: the smallest size that fits is {fit}, got {self.size}')
+        self.uv = ((self.corners().astype(F32) + F32(0.5)) / F32(self.size)).astype(F32)
+
+    def corners(self):
+        """int64 [F,3,2]: the texel coordinates (x, y) of the three corners of every face."""
+        f = np.arange(self.n_faces, dtype=np.int64)
+        b, up = f >> 1, (f & 1).astype(bool)
+        far, L = self.s - 1, self.s - 3
+        cx = np.stack([np.where(up, far, 0), np.where(up, 2, L), np.where(up, far, 0)], 1) + ((b % self.G) * self.s)[:, None]
+        cy = np.stack([np.where(up, far, 0), np.where(up, far, 0), np.where(up, 2, L)], 1) + ((b // self.G) * self.s)[:, None]
+        return np.stack([cx, cy], -1)
+
+    def texels(self):
+        """(face int32 [size,size], -1 where unowned; a, c int64 [size,size]: the texel's offset from corner 0 of its face along the two
+        legs, 0 where unowned)."""
+        j, i = np.meshgrid(np.arange(self.size, dtype=np.int64), np.arange(self.size, dtype=np.int64), indexing='ij')
+        li, lj = i % self.s, j % self.s
+        up = li + lj >= self.s
+        face = 2 * ((j // self.s) * self.G + i // self.s) + up
+        own = (i < self.G * self.s) & (j < self.G * self.s) & (face < self.n_faces)
+        far = self.s - 1
+        return (np.where(own, face, -1).astype(np.int32), np.where(own, np.where(up, far - li, li), 0), np.where(own, np.where(up, far - lj, lj), 0))
+
+    def texel_face(self):
+        """int32 [size,size]: the face that owns each texel, -1 where none does."""
+        return self.texels()[0]
+
+
+def _atlas_points_numpy(v32, f, atlas, normals, dtype):
+    face, a, c = atlas.texels()
+    n = atlas.size
+    out = {'point': np.zeros((n, n, 3), dtype), 'face': face, 'bary': np.zeros((n, n, 3), dtype), 'normal': np.zeros((n, n, 3), dtype)}
+    if not f.shape[0]:
+        return out, 0
+    own = face >= 0
+    fi = np.where(own, face, 0)
+    with np.errstate(all='ignore'):
+        L = dtype(atlas.s - 3)
+        l1, l2 = a.astype(dtype) / L, c.astype(dtype) / L
+        l0 = (dtype(1) - l1) - l2
+        mix = lambda x: (l0[..., None] * x[f[fi, 0]] + l1[..., None] * x[f[fi, 1]]) + l2[..., None] * x[f[fi, 2]]
+        p = v32.astype(dtype)
+        fn = _cross3(p[f[:, 1]] - p[f[:, 0]], p[f[:, 2]] - p[f[:, 0]])
+        l = np.sqrt(_dot3(fn, fn))
+        bad = ~((l > 0) & np.isfinite(l))
+        nrm = _unit_rows(fn[fi] if normals is None else mix(normals.astype(dtype)), dtype)
+        out['point'] = np.where(own[..., None], mix(p), dtype(0))
+    out['bary'] = np.where(own[..., None], np.stack([l0, l1, l2], -1), dtype(0))
+    out['normal'] = np.where((own & ~bad[fi])[..., None], nrm, dtype(0))
+    return out, int(bad.sum())
+
+
+def _texture_dtype(dtype):
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise ValueError(f'dtype must be float32 or float64, got {dtype}')
+    return dtype
+
+
+def atlas_points(verts, faces, atlas, normals=None, dtype=np.float32):
+    """The surface point under every texel of ``atlas`` (a ``TextureAtlas`` of ``faces.shape[0]`` faces): a dict of 'point' float32
+    [size,size,3], 'face' int32 [size,size] (-1: unowned), 'bary' [size,size,3], 'normal' [size,size,3] and 'info' {'degenerate'}.
+
+    A texel of face t = (A, B, C) at offset (a, c) from corner 0 along the two legs has lambda_1 = fp32(a) / fp32(L), lambda_2 =
+    fp32(c) / fp32(L), lambda_0 = (1 - lambda_1) - lambda_2 and point = (lambda_0 A + lambda_1 B) + lambda_2 C, every operation
+    rounded on its own.  The guard texels of the diagonal have a negative weight: they are extrapolated on the triangle's plane, not
+    clamped, so that the bilinear lookup reproduces an affine function of position everywhere inside the triangle.  'normal' is the unit
+    (B - A) x (C - A), or with ``normals`` [V,3] their normalised mix.  A face with a non-finite vertex or no area keeps the points the
+    formula gives and has a zero normal; 'info'['degenerate'] counts such faces.  Unowned texels are 0 / -1.
+
+    Device tensors run on ia_atlas_points (csrc/texture.hip) and give the bits of the float32 restatement; CPU tensors and NumPy arrays
+    take the NumPy restatement, with ``dtype=np.float64`` in double."""
+    _mesh_args(verts, faces)
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    if not isinstance(atlas, TextureAtlas) or atlas.n_faces != nf:
+        raise ValueError(f'atlas must be a TextureAtlas of {nf} faces')
+    if normals is not None and (normals.ndim != 2 or tuple(normals.shape) != (nv, 3)):
+        raise ValueError(f'normals must be [{nv},3], got {tuple(normals.shape)}')
+    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+        from . import hipops
+        if dtype not in (np.float32, torch.float32):
+            raise ValueError('the device path is float32')
+        dev = verts.device
+        f = torch.as_tensor(faces).to(device=dev, dtype=torch.int32).contiguous()
+        _faces_in_range(f, nv)
+        nrm = None if normals is None else torch.as_tensor(normals).to(device=dev, dtype=torch.float32).contiguous()
+        out = hipops.atlas_points(verts.detach().float().contiguous(), f, atlas.size, atlas.s, nrm)
+        out['info'] = {'degenerate': int(out.pop('degenerate'))}
+        return out
+    dtype = _texture_dtype(dtype)
+    f = _np(faces).astype(np.int64)
+    _faces_in_range(f, nv)
+    as32 = lambda a: None if a is None else np.ascontiguousarray(_np(a), dtype=F32)
+    out, bad = _atlas_points_numpy(as32(verts), f, atlas, as32(normals), dtype)
+    out = {k: _as_out(x, verts, np.int32 if k == 'face' else dtype) for k, x in out.items()}
+    out['info'] = {'degenerate': bad}
+    return out
+
+
+def bake_texture(verts, faces, size, fn, atlas=None, chunk=1 << 20, normals=None):
+    """A texture from a function of position: ``fn(points [M,3]) -> [M,C]`` (or [M]) is called over the owned texels of the atlas
+    (``atlas``, or ``TextureAtlas(F, size)``) in chunks of ``chunk`` points.  Returns {'texture' float32 [size,size,C], 'mask' bool
+    [size,size] (the owned texels), 'atlas', 'points' (what ``atlas_points`` returned)}.  Texels that no face owns are 0."""
+    atlas = TextureAtlas(int(faces.shape[0]), size) if atlas is None else atlas
+    if atlas.size != int(size):
+        raise ValueError(f'atlas has size {atlas.size}, not {size}')
+    pts = atlas_points(verts, faces, atlas, normals=normals)
+    own = pts['face'] >= 0
+    p = pts['point'][own]
+    parts = []
+    for c0 in range(0, int(p.shape[0]), int(chunk)):
+        val = fn(p[c0:c0 + int(chunk)])
+        parts.append(val.reshape(val.shape[0], -1))
+    if isinstance(p, torch.Tensor):
+        vals = torch.cat(parts).float() if parts else torch.zeros(0, 1, device=p.device)
+        tex = torch.zeros(atlas.size, atlas.size, vals.shape[1], device=p.device)
+    else:
+        vals = np.concatenate(parts).astype(F32) if parts else np.zeros((0, 1), F32)
+        tex = np.zeros((atlas.size, atlas.size, vals.shape[1]), F32)
+    tex[own] = vals
+    return {'texture': tex, 'mask': own, 'atlas': atlas, 'points': pts}
+
+
+def _mesh_extent(verts):
+    """The longest side of the bounding box of the finite vertices (0 without any)."""
+    v = _np(verts).astype(np.float64).reshape(-1, 3)
+    v = v[np.isfinite(v).all(1)]
+    return float((v.max(0) - v.min(0)).max()) if v.shape[0] else 0.0
+
+
+def _bilinear_numpy(img, x, y, dtype):
+    """The bilinear read of img [H,W,C] at (x, y) [M] (inside the image): i0 = floor x, fx = x - i0, i1 = min(i0 + 1, W - 1), and
+    (1 - fy) ((1 - fx) I00 + fx I10) + fy ((1 - fx) I01 + fx I11)."""
+    fi, fj = np.floor(x), np.floor(y)
+    fx, fy = (x - fi)[:, None], (y - fj)[:, None]
+    i0, j0 = fi.astype(np.int64), fj.astype(np.int64)
+    i1, j1 = np.minimum(i0 + 1, img.shape[1] - 1), np.minimum(j0 + 1, img.shape[0] - 1)
+    one = dtype(1)
+    top = (one - fx) * img[j0, i0].astype(dtype) + fx * img[j0, i1].astype(dtype)
+    bot = (one - fx) * img[j1, i0].astype(dtype) + fx * img[j1, i1].astype(dtype)
+    return (one - fy) * top + fy * bot
+
+
+def _view_weight_numpy(c, power, dtype):
+    if power == np.floor(power) and power <= 64:
+        w = np.ones_like(c)
+        for _ in range(int(power)):
+            w = w * c
+        return w
+    return np.power(c.astype(np.float64), np.float64(power)).astype(dtype)
+
+
+def _texture_views_numpy(X32, n32, cam32, depth, mask, H, W, near, min_cos, depth_tol, dtype):
+    """Steps 1 to 3 of ``project_texture`` for the points X32 [M,3] with normals n32: per view (passes bool [M], u, v, cos)."""
+    R, o, k = _camera_numpy(cam32, H, W, dtype)
+    X, nr = X32.astype(dtype), n32.astype(dtype)
+    for n in range(cam32.shape[0]):
+        with np.errstate(all='ignore'):
+            d = X - o[n]
+            xc = [(R[n, 0, a] * d[:, 0] + R[n, 1, a] * d[:, 1]) + R[n, 2, a] * d[:, 2] for a in range(3)]
+            px = (k[n, 0] * xc[0] + k[n, 1] * xc[1]) + k[n, 2] * xc[2]
+            py = (k[n, 3] * xc[0] + k[n, 4] * xc[1]) + k[n, 5] * xc[2]
+            u, v, z = px / xc[2], py / xc[2], xc[2]
+            ok = (np.isfinite(u) & np.isfinite(v) & np.isfinite(z) & ~(z <= dtype(near)) & (np.abs(u) < dtype(RASTER_MAX_SCREEN))
+                  & (np.abs(v) < dtype(RASTER_MAX_SCREEN)))
+            ok &= (u >= 0) & (u <= dtype(W - 1)) & (v >= 0) & (v <= dtype(H - 1))
+            e = o[n] - X
+            t = np.sqrt(_dot3(e, e))
+            c = _dot3(nr, e) / t
+            ok &= c > dtype(min_cos)
+            pi, pj = np.rint(np.where(ok, u, 0)).astype(np.int64), np.rint(np.where(ok, v, 0)).astype(np.int64)
+            ok &= mask[n, pj, pi] & (np.abs(t - depth[n, pj, pi].astype(dtype)) <= dtype(depth_tol))
+        yield ok, np.where(ok, u, dtype(0)), np.where(ok, v, dtype(0)), np.where(ok, c, dtype(0))
+
+
+def _texture_project_numpy(X32, n32, images, cam32, depth, mask, near, min_cos, power, depth_tol, best, dtype):
+    M, (N, H, W, C) = X32.shape[0], images.shape
+    num, den = np.zeros((M, C), np.float64), np.zeros(M, np.float64)
+    count, w_best, col_best = np.zeros(M, np.int32), np.zeros(M, dtype), np.zeros((M, C), dtype)
+    for n, (ok, u, v, c) in enumerate(_texture_views_numpy(X32, n32, cam32, depth, mask, H, W, near, min_cos, depth_tol, dtype)):
+        col = _bilinear_numpy(images[n], u, v, dtype)
+        w = _view_weight_numpy(c, power, dtype)
+        num += np.where(ok[:, None], (w[:, None] * col).astype(np.float64), 0.0)
+        den += np.where(ok, w.astype(np.float64), 0.0)
+        better = ok & ((count == 0) | (w > w_best))
+        w_best, col_best = np.where(better, w, w_best), np.where(better[:, None], col, col_best)
+        count += ok
+    hit = count > 0
+    with np.errstate(all='ignore'):
+        tex = col_best if best else (num / den[:, None]).astype(dtype)
+    return np.where(hit[:, None], tex, dtype(0)), np.where(hit, w_best if best else den.astype(dtype), dtype(0)), count, hit
+
+
+def project_texture(verts, faces, atlas, images, cameras, depth=None, mask=None, min_cos=0.2, power=2.0, depth_tol=None, mode='blend',
+                    fallback=None, normals=None, near=1e-6, dtype=np.float32):
+    """Projective texturing: the texture of ``atlas`` from rendered views ``images`` float32 [N,H,W,C] (C <= 8) of the cameras [N,25].
+    ``depth`` / ``mask`` are those of ``rasterize_mesh(verts, faces, cameras, (H, W))`` and are computed here when not given.  Returns
+    {'texture' [size,size,C], 'weight' [size,size] (sum of w, or the best w), 'views' int32 (how many views passed), 'filled' bool}.
+    For the point X and normal n of a texel (``atlas_points``; ``normals``: vertex normals for it) and view k in ascending order, in
+    float32 with every operation rounded on its own:
+
+    1. Project as ``rasterize_mesh`` step 1 without the snap: u, v, z.  The view is skipped if that rule calls X unusable (``near``) or
+       u is outside [0, W - 1] or v outside [0, H - 1].
+    2. e = o - X, t = sqrt(e . e), c = (n . e) / t; skipped unless c > ``min_cos``.
+    3. At pixel (rint u, rint v): skipped unless ``mask`` is set and |t - depth| <= ``depth_tol`` (depth is the ray parameter, as t is).
+    4. colour = the bilinear read of images[k] at (u, v), pixel centres at integer coordinates (``_bilinear_numpy``); w = c^power (an
+       integer power <= 64 is the product ((c c) c) ..., any other the float32 rounding of the double power).
+
+    ``mode='blend'``: sum w colour / sum w, the terms w colour and w float32, the two sums double in view order, the quotient rounded
+    once; ``'best'``: the colour of the view with the largest w, the lowest k among equals.  A texel that no view passes takes
+    ``fallback`` (a texture of the same shape, e.g. the decoder bake) where given, else 0, and weight 0.
+
+    ``depth_tol`` defaults to ``TEXTURE_DEPTH_TOL`` * extent / max(H, W), extent being the longest side of the mesh's bounding box.
+    Measured on the 320-face icosphere (radius 0.5, extent 1, 3 cameras at radius 2.7, atlas sizes 64 and 128), counting the texel-views
+    with c > 0.2 that lie inside their triangle (lambda_0 >= 0; a guard texel is extrapolated off the surface) and whose pixel the mesh
+    covers, which the depth test of the float64 restatement rejects: at 32^2 views the multiples 1, 2, 4, 8 of extent / max(H, W) reject
+    130 / 933, 19 / 124, 0 / 11, 0 / 0 (size 64 / 128), at 64^2 views 120 / 1032, 31 / 198, 7 / 17, 0 / 0.  The smallest power-of-two
+    multiple that rejects none is 8 (at c = 0.2 the depth under a pixel changes by five pixel footprints across the pixel), the default
+    is twice that.  Independently of the tolerance a texel within a pixel of a view's silhouette can find ``mask`` unset there.
+
+    Device tensors run on ia_atlas_points + ia_texture_project (csrc/texture.hip; one thread per texel, the views in a loop, no atomics)
+    and give the bits of the float32 restatement; CPU tensors and NumPy arrays take the NumPy restatement, ``dtype=np.float64`` in
+    double."""
+    if mode not in _TEXTURE_MODES:
+        raise ValueError(f'mode must be one of {_TEXTURE_MODES}, got {mode!r}')
+    if images.ndim != 4 or not 1 <= images.shape[3] <= TEXTURE_MAX_CHANNELS:
+        raise ValueError(f'images must be [N,H,W,C] with 1 <= C <= {TEXTURE_MAX_CHANNELS}, got {tuple(images.shape)}')
+    N, H, W, C = (int(n) for n in images.shape)
+    if cameras.ndim != 2 or tuple(cameras.shape) != (N, 25):
+        raise ValueError(f'cameras must be [{N},25], got {tuple(cameras.shape)}')
+    if (depth is None) != (mask is None):
+        raise ValueError('depth and mask are given together')
+    power, min_cos, near = float(power), float(min_cos), float(near)
+    if not power >= 0 or not near >= 0:
+        raise ValueError(f'power and near must be >= 0, got {power}, {near}')
+    if fallback is not None and tuple(fallback.shape) != (atlas.size, atlas.size, C):
+        raise ValueError(f'fallback must be {(atlas.size, atlas.size, C)}, got {tuple(fallback.shape)}')
+    tol = TEXTURE_DEPTH_TOL * _mesh_extent(verts) / max(H, W) if depth_tol is None else float(depth_tol)
+    if not tol >= 0:
+        raise ValueError(f'depth_tol must be >= 0, got {depth_tol}')
+    pts = atlas_points(verts, faces, atlas, normals=normals, dtype=dtype)
+    if depth is None:
+        r = rasterize_mesh(verts, faces, cameras, (H, W), near=near, dtype=dtype)
+        depth, mask = r['depth'], r['mask']
+    if tuple(depth.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W):
+        raise ValueError(f'depth and mask must be {(N, H, W)}, got {tuple(depth.shape)} and {tuple(mask.shape)}')
+    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+        from . import hipops
+        dev = verts.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
+        return hipops.texture_project(pts['point'], pts['normal'], pts['face'], f32(images), f32(cameras), f32(depth),
+                                      torch.as_tensor(mask).to(device=dev, dtype=torch.bool).contiguous(), near, min_cos, power, tol,
+                                      mode == 'best', f32(fallback))
+    dtype = _texture_dtype(dtype)
+    face = _np(pts['face'])
+    own = face >= 0
+    tex, wgt, cnt, hit = _texture_project_numpy(_np(pts['point'])[own].astype(F32), _np(pts['normal'])[own].astype(F32), _np(images).astype(F32),
+                                                np.ascontiguousarray(_np(cameras), dtype=F32), _np(depth), _np(mask).astype(bool), near, min_cos,
+                                                power, tol, mode == 'best', dtype)
+    n = atlas.size
+    out = {'texture': np.zeros((n, n, C), dtype), 'weight': np.zeros((n, n), dtype), 'views': np.zeros((n, n), np.int32), 'filled': np.zeros((n, n), bool)}
+    out['texture'][own], out['weight'][own], out['views'][own], out['filled'][own] = tex, wgt, cnt, hit
+    if fallback is not None:
+        out['texture'] = np.where(out['filled'][..., None], out['texture'], _np(fallback).astype(dtype))
+    kinds = {'views': np.int32, 'filled': bool}
+    return {k: _as_out(x, verts, kinds.get(k, dtype)) for k, x in out.items()}
+
+
+def _texture_sample_numpy(tex, atlas, face, bary, dtype):
+    size, s, G = atlas.size, atlas.s, atlas.G
+    ok = (face >= 0) & (face < atlas.n_faces)
+    out = np.zeros(face.shape + (tex.shape[2],), dtype)
+    if not ok.any():
+        return out
+    f = face[ok].astype(np.int64)
+    b = bary[ok].astype(dtype)
+    uv = atlas.uv.astype(dtype)[f]                                        # [M,3,2]
+    blk = f >> 1
+    bx, by = (blk % G) * s, (blk // G) * s
+    with np.errstate(all='ignore'):
+        u = (b[:, 0] * uv[:, 0, 0] + b[:, 1] * uv[:, 1, 0]) + b[:, 2] * uv[:, 2, 0]
+        v = (b[:, 0] * uv[:, 0, 1] + b[:, 1] * uv[:, 1, 1]) + b[:, 2] * uv[:, 2, 1]
+        x, y = u * dtype(size) - dtype(0.5), v * dtype(size) - dtype(0.5)
+        xl = np.fmin(np.fmax(x - bx.astype(dtype), dtype(0)), dtype(s - 1))
+        yl = np.fmin(np.fmax(y - by.astype(dtype), dtype(0)), dtype(s - 1))
+        fi, fj = np.floor(xl), np.floor(yl)
+        fx, fy = (xl - fi)[:, None], (yl - fj)[:, None]
+        i0, j0 = fi.astype(np.int64), fj.astype(np.int64)
+        i1, j1 = np.minimum(i0 + 1, s - 1), np.minimum(j0 + 1, s - 1)
+        t = lambda jj, ii: tex[by + jj, bx + ii].astype(dtype)
+        one = dtype(1)
+        top = (one - fx) * t(j0, i0) + fx * t(j0, i1)
+        bot = (one - fx) * t(j1, i0) + fx * t(j1, i1)
+        out[ok] = (one - fy) * top + fy * bot
+    return out
+
+
+def sample_texture(texture, atlas, face, bary, dtype=np.float32):
+    """The texture [size,size,C] looked up at points of the mesh given as ``face`` int [...] and ``bary`` [..., 3] (the 'face' / 'bary'
+    of ``rasterize_mesh``): float32 [..., C], 0 where face < 0.  In float32, every operation rounded on its own: the uv mix
+    (b0 uv0 + b1 uv1) + b2 uv2 of the face's atlas corners, x = u size - 0.5 and y likewise, clamped into the face's block
+    (fmin(fmax(x - bx, 0), s - 1), so that rounding at a corner or an extrapolating weight never reads another chart), i0 = floor,
+    fx = x - i0, i1 = min(i0 + 1, s - 1) and (1 - fy) ((1 - fx) T00 + fx T10) + fy ((1 - fx) T01 + fx T11).  Device tensors run on
+    ia_texture_sample (csrc/texture.hip) and give the bits of the float32 restatement; ``dtype=np.float64``: the restatement in double."""
+    if texture.ndim != 3 or tuple(texture.shape[:2]) != (atlas.size, atlas.size):
+        raise ValueError(f'texture must be [{atlas.size},{atlas.size},C], got {tuple(texture.shape)}')
+    if tuple(bary.shape) != tuple(face.shape) + (3,):
+        raise ValueError(f'bary must be face.shape + [3], got {tuple(bary.shape)} for {tuple(face.shape)}')
+    if isinstance(texture, torch.Tensor) and texture.is_cuda:
+        from . import hipops
+        if dtype not in (np.float32, torch.float32):
+            raise ValueError('the device path is float32')
+        dev = texture.device
+        return hipops.texture_sample(texture.detach().float().contiguous(), atlas.s, atlas.n_faces,
+                                     torch.as_tensor(face).to(device=dev, dtype=torch.int32).contiguous(),
+                                     torch.as_tensor(bary).to(device=dev, dtype=torch.float32).contiguous())
+    dtype = _texture_dtype(dtype)
+    out = _texture_sample_numpy(_np(texture), atlas, _np(face), _np(bary), dtype)
+    return _as_out(out, texture, dtype)
+
+
 # ------------------------------------------------------------------ generator-level helpers
 
 def generator_planes(G, ws, mesh_condition, update_emas=False, **synthesis_kwargs):
@@ -2865,6 +3228,13 @@ def vertex_colors(planes, decoder, verts, box_warp):
         return torch.zeros(0, 3, dtype=torch.uint8, device=verts.device)
     rgb = query_planes(planes, decoder, verts[None].float(), box_warp, rgb=True)['rgb'][0, :, :3]
     return (rgb.clamp(0, 1) * 255).round().to(torch.uint8)
+
+
+def bake_colors(planes, decoder, verts, faces, size, box_warp, atlas=None, chunk=1 << 20):
+    """``bake_texture`` of the decoder's rgb[:3], clamped to [0, 1], for the planes [1,3,32,H,W] of one avatar: what ``vertex_colors``
+    samples at the vertices, at every texel."""
+    fn = lambda p: query_planes(planes, decoder, p[None].float(), box_warp, rgb=True)['rgb'][0, :, :3].clamp(0, 1)
+    return bake_texture(verts, faces, size, fn, atlas=atlas, chunk=chunk)
 
 
 # ------------------------------------------------------------------ PLY
@@ -2921,3 +3291,81 @@ def read_ply(path, with_normals=False):
         return verts, frec['i'].astype(np.int64), cols
     nrm = np.stack([vrec['nx'], vrec['ny'], vrec['nz']], -1).astype(np.float32) if has_nrm else None
     return verts, frec['i'].astype(np.int64), cols, nrm
+
+
+# ------------------------------------------------------------------ OBJ
+
+def write_obj(path, verts, faces, uv, texture, normals=None):
+    """Wavefront OBJ with a texture: ``name.obj`` (``v``; ``vt``, 3 F entries from ``uv`` [F,3,2] with 1 - v, OBJ's origin being
+    bottom-left; ``vn`` with ``normals`` [V,3]; ``f a/ta/na ...``, 1-based), ``name.mtl`` (``map_Kd name.png``) and ``name.png`` (the
+    first three channels of ``texture`` float [size,size,C] in [0, 1], or one grey channel; 8 bit, row 0 on top).  ``path`` is the .obj."""
+    import os
+    from PIL import Image
+    stem = os.path.splitext(path)[0]
+    name = os.path.basename(stem)
+    v, f = _np(verts).astype(np.float64).reshape(-1, 3), _np(faces).astype(np.int64).reshape(-1, 3)
+    t = _np(uv).astype(np.float64).reshape(-1, 3, 2)
+    if t.shape[0] != f.shape[0]:
+        raise ValueError(f'uv must be [{f.shape[0]},3,2], got {tuple(_np(uv).shape)}')
+    tex = _np(texture).astype(np.float64)
+    tex = tex[..., None] if tex.ndim == 2 else tex
+    img = np.rint(np.clip(tex[..., :3] if tex.shape[2] >= 3 else tex[..., 0], 0, 1) * 255).astype(np.uint8)
+    Image.fromarray(img, mode='RGB' if img.ndim == 3 else 'L').save(stem + '.png')
+    with open(stem + '.mtl', 'w') as fh:
+        fh.write(f'newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n')
+    lines = [f'mtllib {name}.mtl', f'usemtl {name}']
+    lines += ['v %.9g %.9g %.9g' % tuple(p) for p in v]
+    lines += ['vt %.17g %.17g' % (p[0], 1.0 - p[1]) for p in t.reshape(-1, 2)]         # (1 - v is exact in double: the round trip is too)
+    if normals is not None:
+        lines += ['vn %.9g %.9g %.9g' % tuple(p) for p in _np(normals).astype(np.float64).reshape(-1, 3)]
+    for k, (a, b, c) in enumerate(f + 1):
+        ta = 3 * k + 1
+        if normals is None:
+            lines.append(f'f {a}/{ta} {b}/{ta + 1} {c}/{ta + 2}')
+        else:
+            lines.append(f'f {a}/{ta}/{a} {b}/{ta + 1}/{b} {c}/{ta + 2}/{c}')
+    with open(stem + '.obj', 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+
+
+def read_obj(path):
+    """Inverse of ``write_obj``: {'verts' float32 [V,3], 'faces' int64 [F,3], 'uv' float32 [F,3,2] (v flipped back), 'normals' float32
+    [V,3] or None, 'texture' float32 [size,size,C] in [0, 1] or None (the ``map_Kd`` image of the material library)}."""
+    import os
+    v, vt, vn, tri, tri_t, tri_n, mtl = [], [], [], [], [], [], None
+    with open(path) as fh:
+        for line in fh:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == 'v':
+                v.append([float(x) for x in p[1:4]])
+            elif p[0] == 'vt':
+                vt.append([float(x) for x in p[1:3]])
+            elif p[0] == 'vn':
+                vn.append([float(x) for x in p[1:4]])
+            elif p[0] == 'mtllib':
+                mtl = p[1]
+            elif p[0] == 'f':
+                ids = [(q.split('/') + ['', ''])[:3] for q in p[1:4]]
+                tri.append([int(q[0]) - 1 for q in ids])
+                tri_t.append([int(q[1]) - 1 if q[1] else -1 for q in ids])
+                tri_n.append([int(q[2]) - 1 if q[2] else -1 for q in ids])
+    verts, faces = np.array(v, dtype=np.float32).reshape(-1, 3), np.array(tri, dtype=np.int64).reshape(-1, 3)
+    out = {'verts': verts, 'faces': faces, 'uv': None, 'normals': None, 'texture': None}
+    if vt:
+        t = np.array(vt, dtype=np.float64)[np.array(tri_t, dtype=np.int64).reshape(-1, 3)]
+        out['uv'] = np.stack([t[..., 0], 1.0 - t[..., 1]], -1).astype(np.float32)
+    if vn:
+        nrm = np.zeros((verts.shape[0], 3), np.float32)
+        nrm[faces.reshape(-1)] = np.array(vn, dtype=np.float32)[np.array(tri_n, dtype=np.int64).reshape(-1)]
+        out['normals'] = nrm
+    folder = os.path.dirname(path)
+    if mtl and os.path.exists(os.path.join(folder, mtl)):
+        with open(os.path.join(folder, mtl)) as fh:
+            maps = [l.split()[1] for l in fh if l.startswith('map_Kd')]
+        if maps and os.path.exists(os.path.join(folder, maps[0])):
+            from PIL import Image
+            img = np.asarray(Image.open(os.path.join(folder, maps[0]))).astype(np.float32) / np.float32(255)
+            out['texture'] = img[..., None] if img.ndim == 2 else img
+    return out

@@ -2319,3 +2319,64 @@ def rasterize_mesh(verts, faces, cams, h, w, normals=None, attributes=None, cull
     out = mesh_resolve(vis, proj, verts, faces, cams, normals, attributes, cull_back)
     out['culled'] = culled
     return out
+
+
+# ------------------------------------------------------------------ texture atlas (csrc/texture.hip)
+
+TEXTURE_TIMES = None         # a dict collects seconds per stage, as SMOOTH_TIMES does: tools/bench_texture.py
+
+
+def atlas_points(verts, faces, size, s, normals=None):
+    """dict of 'point' [size,size,3], 'face' int32 [size,size], 'bary' [size,size,3], 'normal' [size,size,3] and 'degenerate' int32 [1]
+    (a device counter) for the atlas of block side ``s`` (ia_atlas_points)."""
+    _mesh_checked(verts, faces)
+    if normals is not None:
+        _f32c(normals, 'normals')
+    dev = verts.device
+    out = {'point': torch.empty(size, size, 3, device=dev), 'face': torch.empty(size, size, dtype=torch.int32, device=dev),
+           'bary': torch.empty(size, size, 3, device=dev), 'normal': torch.empty(size, size, 3, device=dev),
+           'degenerate': torch.empty(1, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev), _Phase('atlas_points', dev, 'TEXTURE_TIMES'):
+        st = _lib.load().ia_atlas_points(_p(verts), verts.shape[0], _p(faces), faces.shape[0], int(size), int(s), _p(normals), _p(out['point']),
+                                         _p(out['face']), _p(out['bary']), _p(out['normal']), _p(out['degenerate']), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_atlas_points')
+    return out
+
+
+def texture_project(point, normal, face, images, cams, depth, mask, near, min_cos, power, depth_tol, best=False, fallback=None):
+    """dict of 'texture' [..., C], 'weight', 'views' int32 and 'filled' bool with the leading shape of ``face`` (ia_texture_project)."""
+    _f32c(point, 'point'), _f32c(normal, 'normal'), _i32c(face, 'face'), _f32c(images, 'images'), _f32c(depth, 'depth')
+    n, h, w, c = images.shape
+    _views_checked(cams, (h, w))
+    if mask.dtype != torch.bool or not mask.is_contiguous() or tuple(mask.shape) != (n, h, w) or tuple(depth.shape) != (n, h, w) or cams.shape[0] != n:
+        raise RuntimeError(f'depth and mask must be [N,H,W] = {(n, h, w)} (mask bool) with N cameras')
+    lead, dev = tuple(face.shape), point.device
+    t = face.numel()
+    if tuple(point.shape) != lead + (3,) or tuple(normal.shape) != lead + (3,):
+        raise RuntimeError('point and normal must have the shape of face plus [3]')
+    if fallback is not None:
+        _f32c(fallback, 'fallback')
+        if tuple(fallback.shape) != lead + (c,):
+            raise RuntimeError(f'fallback must be {lead + (c,)}, got {tuple(fallback.shape)}')
+    out = {'texture': torch.empty(lead + (c,), device=dev), 'weight': torch.empty(lead, device=dev),
+           'views': torch.empty(lead, dtype=torch.int32, device=dev), 'filled': torch.empty(lead, dtype=torch.bool, device=dev)}
+    with torch.cuda.device(dev), _Phase('project', dev, 'TEXTURE_TIMES'):
+        st = _lib.load().ia_texture_project(_p(point), _p(normal), _p(face), t, _p(images), _p(cams), n, h, w, c, _p(depth), _p(mask), float(near),
+                                            float(min_cos), float(power), float(depth_tol), int(bool(best)), _p(fallback), _p(out['texture']),
+                                            _p(out['weight']), _p(out['views']), _p(out['filled']), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_texture_project')
+    return out
+
+
+def texture_sample(texture, s, n_faces, face, bary):
+    """float32 ``face.shape + [C]``: the bilinear lookup of ``texture`` [size,size,C] at the barycentrics of the faces (ia_texture_sample)."""
+    _f32c(texture, 'texture'), _i32c(face, 'face'), _f32c(bary, 'bary')
+    if texture.dim() != 3 or texture.shape[0] != texture.shape[1] or tuple(bary.shape) != tuple(face.shape) + (3,):
+        raise RuntimeError(f'texture must be [size,size,C] and bary face.shape + [3], got {tuple(texture.shape)}, {tuple(bary.shape)}')
+    dev = texture.device
+    out = torch.empty(tuple(face.shape) + (texture.shape[2],), device=dev)
+    with torch.cuda.device(dev), _Phase('sample', dev, 'TEXTURE_TIMES'):
+        st = _lib.load().ia_texture_sample(_p(texture), texture.shape[0], texture.shape[2], int(s), int(n_faces), _p(face), _p(bary), face.numel(),
+                                           _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_texture_sample')
+    return out

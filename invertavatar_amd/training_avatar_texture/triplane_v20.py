@@ -535,7 +535,7 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         with_normals=False, keep=None, min_voxels=0, simplify=None, smooth=None, **synthesis_kwargs):
+                         with_normals=False, keep=None, min_voxels=0, simplify=None, smooth=None, texture=None, **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
@@ -551,8 +551,11 @@ class TriPlaneGenerator(torch.nn.Module):
         target).  ``smooth`` (None: nothing changes; an int = Taubin pairs with the defaults of ``geometry.smooth_mesh``; or a dict of
         its keyword arguments) smooths the mesh after the filter and after ``simplify``: 'faces' stay, 'verts' move, colours are
         queried at the final vertices, normals come from the mesh (``geometry.mesh_normals``) instead of the volume, and 'smooth' holds
-        the smoothing's 'info' ('edges', 'boundary_edges', 'nonmanifold_edges', 'steps', ...).  The planes are computed once per call;
-        device tensors stay on the device throughout."""
+        the smoothing's 'info' ('edges', 'boundary_edges', 'nonmanifold_edges', 'steps', ...).  ``texture`` (None: nothing changes; an
+        int = the atlas size with the decoder as source; or a dict of ``bake_texture`` keyword arguments) bakes the colours of the
+        FINAL mesh (after ``keep``, ``simplify`` and ``smooth``) into a texture atlas: 'texture' [size,size,3], 'uv' float32 [F,3,2],
+        'atlas' and 'texture_info' {'filled', 'mask' and, from views, 'views'}.  The planes are computed once per call; device tensors
+        stay on the device throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
         length = box_warp if cube_length is None else cube_length
@@ -589,6 +592,12 @@ class TriPlaneGenerator(torch.nn.Module):
                 item['normals'] = geometry.mesh_normals(verts, faces, adjacency=adjacency)
             elif with_normals:
                 item['normals'] = geometry.volume_normals(vol_b, verts, [float(a[1]) for a in axes], [float(a[2]) for a in axes])
+            if texture is not None:
+                kw = dict(texture) if isinstance(texture, dict) else {'size': int(texture)}
+                cond_b = {k: x[b:b + 1] if isinstance(x, torch.Tensor) and x.shape[0] == ws.shape[0] else x for k, x in mesh_condition.items()}
+                baked = self.bake_texture(ws[b:b + 1], cond_b, verts, faces, **kw, **synthesis_kwargs)
+                item['texture'], item['uv'], item['atlas'] = baked['texture'], baked['uv'], baked['atlas']
+                item['texture_info'] = {k: baked[k] for k in ('filled', 'mask', 'views') if k in baked}
             out.append(item)
         return out
 
@@ -636,15 +645,19 @@ class TriPlaneGenerator(torch.nn.Module):
             out[k] = x.reshape(lead + x.shape[1:])
         return out
 
-    def render_mesh(self, verts, faces, c, resolution=512, normals=None, colors=None, cull='none'):
+    def render_mesh(self, verts, faces, c, resolution=512, normals=None, colors=None, cull='none', texture=None, atlas=None):
         """Renders of one triangle mesh (verts [V,3], faces [F,3]: an extracted, simplified or smoothed mesh, or one read with
         ``read_ply``) from the cameras ``c`` ([V,25] or [B,V,25]) through ``geometry.rasterize_mesh``; pixels align with
         ``render_geometry`` and ``image_depth`` at the same resolution.  Returns the NCHW dictionary of ``render_geometry``: 'depth'
         [(B,)V,1,H,W] (ray parameter; 0 on a miss), 'mask' bool, 'normal' [(B,)V,3,H,W] (the face normal of the winding, or with
         ``normals`` [V,3] their interpolation), 'shaded' (headlight Lambert, ``geometry.shade`` with the rays of the generator's ray
         sampler) and, with ``colors`` ([V,3], uint8 or float in [0, 1]), 'rgb' [(B,)V,3,H,W] (0 on a miss); besides these 'culled'
-        int32 [(B,)V], the triangles dropped per view for a vertex at or behind the near plane (nothing is clipped)."""
+        int32 [(B,)V], the triangles dropped per view for a vertex at or behind the near plane (nothing is clipped).  With ``texture``
+        [size,size,C] and its ``atlas`` (``geometry.TextureAtlas``) 'rgb' [(B,)V,C,H,W] is ``geometry.sample_texture`` of the raster's
+        face and barycentrics instead of the interpolated vertex colours."""
         from .. import geometry
+        if (texture is None) != (atlas is None):
+            raise ValueError('texture and atlas are given together')
         lead = tuple(c.shape[:-1])
         cam = c.reshape(-1, 25).float()
         attrs = None
@@ -657,8 +670,42 @@ class TriPlaneGenerator(torch.nn.Module):
                'shaded': geometry.shade(hit['normal'], rays_d, hit['mask'])}
         if colors is not None:
             out['rgb'] = hit['attributes']
+        if texture is not None:
+            out['rgb'] = geometry.sample_texture(texture, atlas, hit['face'], hit['bary'])
         out = {k: x.permute(0, 3, 1, 2).reshape(lead + (x.shape[3], resolution, resolution)) for k, x in out.items()}
         out['culled'] = hit['culled'].reshape(lead)
+        return out
+
+    @torch.no_grad()
+    def bake_texture(self, ws, mesh_condition, verts, faces, size=2048, source='decoder', cameras=None, mode='blend', n_views=8, atlas=None,
+                     **synthesis_kwargs):
+        """The colours of the avatar ``ws`` [1,L,512] on the texture atlas of a mesh of it (verts [V,3], faces [F,3]: the output of
+        ``extract_geometry``).  ``source='decoder'``: the decoder's rgb[:3] at the surface point of every texel
+        (``geometry.bake_colors``).  ``source='views'``: ``synthesis(ws, c, mesh_condition)['image']`` of every camera of ``cameras``
+        [N,25] (default: the yaw orbit of ``extract_geometry.orbit_cameras`` with ``n_views`` views), mapped to [0, 1] and projected
+        onto the mesh (``geometry.project_texture``, ``mode``) with the decoder bake as the fallback of the texels no view sees.  Returns
+        {'texture' [size,size,3], 'atlas', 'uv' float32 [F,3,2], 'mask' (owned texels), 'filled', 'views' (int32, views per texel),
+        'weight'}; for the decoder source 'filled' is 'mask' and 'views' / 'weight' are absent."""
+        from .. import geometry
+        if source not in ('decoder', 'views'):
+            raise ValueError(f"source must be 'decoder' or 'views', got {source!r}")
+        if ws.shape[0] != 1:
+            raise ValueError(f'bake_texture takes one avatar, got a batch of {ws.shape[0]}')
+        box_warp = self.rendering_kwargs['box_warp']
+        planes = geometry.generator_planes(self, ws, mesh_condition, **synthesis_kwargs)
+        atlas = geometry.TextureAtlas(int(faces.shape[0]), size) if atlas is None else atlas
+        dec = geometry.bake_colors(planes[:1], self.decoder, verts, faces, size, box_warp, atlas=atlas)
+        out = {'texture': dec['texture'], 'atlas': atlas, 'uv': atlas.uv, 'mask': dec['mask'], 'filled': dec['mask']}
+        if source == 'decoder':
+            return out
+        if cameras is None:
+            from ..extract_geometry import orbit_cameras
+            cameras = orbit_cameras(self, n_views, device=ws.device)
+        cameras = cameras.reshape(-1, 25).float()
+        images = torch.cat([self.synthesis(ws, cameras[k:k + 1], mesh_condition, **synthesis_kwargs)['image'] for k in range(cameras.shape[0])])
+        images = ((images.float() + 1) / 2).clamp(0, 1).permute(0, 2, 3, 1).contiguous()
+        proj = geometry.project_texture(verts, faces, atlas, images, cameras, mode=mode, fallback=dec['texture'])
+        out.update(texture=proj['texture'], filled=proj['filled'], views=proj['views'], weight=proj['weight'])
         return out
 
     def forward(self, z, c, v, truncation_psi=1, truncation_cutoff=None, neural_rendering_resolution=None, update_emas=False,

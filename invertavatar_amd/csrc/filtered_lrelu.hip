@@ -4,7 +4,7 @@
 // Replaces filtered_lrelu_plugin.filtered_lrelu (torch_utils/ops/filtered_lrelu.cpp:20-22, kernels filtered_lrelu.cu:144-1103);
 // semantics are those of the reference's own definition of the op, _filtered_lrelu_ref (filtered_lrelu.py:123-155):
 //     t = upfirdn2d(x + b, fu, up = up, padding = [px0, px1, py0, py1], gain = up^2)
-//     t = clamp(lrelu(t, slope) * gain, +-clamp)
+//     t = clamp(lrelu(t, slope) * gain, +-clamp)                      (torch.clamp: a NaN stays a NaN)
 //     y = upfirdn2d(t, fd, down = down)
 // with the filters applied as true convolutions unless flip_filter (upfirdn2d semantics).
 //
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void filtered_lrelu_kernel(const T* __restrict
             }
             v = acc > 0.f ? acc : acc * g.slope;
             v *= g.gain;
-            if (g.clamp >= 0.f) v = fminf(fmaxf(v, -g.clamp), g.clamp);
+            if (g.clamp >= 0.f) { const float t = fminf(fmaxf(v, -g.clamp), g.clamp); v = (v != v) ? v : t; }      // (NaN stays NaN, as torch.clamp)
         }
         s_mid[i] = v;
     }

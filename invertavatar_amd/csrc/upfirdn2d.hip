@@ -39,6 +39,13 @@ struct Tail {
     float alpha, gain, clamp;
 };
 
+// The tail's clamp keeps a NaN, as torch.clamp does (fminf / fmaxf alone return the other operand: NaN would leave as -clamp, a finite
+// number the range watch of the split cannot see).  The select of fir_tail_split_dma_kernel, so that every form gives the same bits.
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) {
+    const float t = fminf(fmaxf(v, -c), c);
+    return (v != v) ? v : t;
+}
+
 __device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
 // Stage K[ky][kx] = gain * f[flip ? ky : fh-1-ky][flip ? kx : fw-1-kx] into LDS.
@@ -151,7 +158,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled(const T* __restrict__ x, 
             acc += t_bias;
             if (tail.act == IA_ACT_LRELU) acc = acc > 0.f ? acc : acc * tail.alpha;
             acc *= tail.gain;
-            if (tail.clamp >= 0.f) acc = fminf(fmaxf(acc, -tail.clamp), tail.clamp);
+            if (tail.clamp >= 0.f) acc = clamp_keep_nan(acc, tail.clamp);
         }
         ia::Num<T>::store(yp + (int64_t)oy * g.out_w + ox, acc);
     }
@@ -234,7 +241,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tiled_pipe(const T* __restrict_
                     acc += t_bias;
                     if (tail.act == IA_ACT_LRELU) acc = acc > 0.f ? acc : acc * tail.alpha;
                     acc *= tail.gain;
-                    if (tail.clamp >= 0.f) acc = fminf(fmaxf(acc, -tail.clamp), tail.clamp);
+                    if (tail.clamp >= 0.f) acc = clamp_keep_nan(acc, tail.clamp);
                 }
                 ia::Num<T>::store(yp + (int64_t)oy * g.out_w + ox, acc);
             }
@@ -341,7 +348,7 @@ __global__ __launch_bounds__(256, IA_FIR_WAVES) void fir_tail_split_kernel(const
             acc += t_bias;
             if (tail.act == IA_ACT_LRELU) acc = acc > 0.f ? acc : acc * tail.alpha;
             acc *= tail.gain;
-            if (tail.clamp >= 0.f) acc = fminf(fmaxf(acc, -tail.clamp), tail.clamp);
+            if (tail.clamp >= 0.f) acc = clamp_keep_nan(acc, tail.clamp);
             const int oy = oy0 + ty + r;
             if (y && ox < g.out_w && oy < g.out_h) y[((int64_t)b * g.c + c) * ohw + (int64_t)oy * g.out_w + ox] = acc;
             const float t = styles_next ? acc * sn : acc;

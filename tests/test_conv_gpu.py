@@ -224,12 +224,7 @@ def test_split_fp16_form_large_transposed_tile():
 
 
 # ---------------------------------------------------------------- split-format (LDS-DMA) convolution: ia_act_split + ia_conv2d_mfma_sx
-def _split_reference(x, s):
-    """The fp16 pair the kernels must store: hi = fp16(v) (0 below the normal range), lo = fp16((v - hi) * 2^11), v = x * s saturated."""
-    v = (x * s[:, :, None, None]).clamp(-65504.0, 65504.0)
-    hi = torch.where(v.abs() < 6.103515625e-5, torch.zeros_like(v), v).half()
-    lo = ((v - hi.float()) * 2048.0).half()
-    return hi, lo
+from resample_reference import split_pair as _split_reference      # noqa: E402  (the fp16 pair the kernels must store)
 
 
 def test_act_split_format():

@@ -8,7 +8,11 @@
 //   mouth = (255 - filled) / 255.
 // One workgroup per image; the label image lives in LDS (1 byte / pixel, rows padded by 4 bytes so that per-row
 // sweeps hit distinct banks).  Propagation is by alternating full-line sweeps (left/right per row, up/down per
-// column), each of which carries the fill along a whole line in one pass; convex-ish masks converge in 2-3 rounds.
+// column), each of which carries the fill along a whole line in one pass; convex-ish masks converge in 2-3 rounds, a corridor
+// that turns at every step needs about one round per two turns (a depth-first maze on 256 x 256: ~2100 rounds).
+// Termination: the loops run until a round reaches no new pixel.  Every round but the last turns at least one of the H * W
+// pixels from passable to reached and none ever turns back, so at most H * W rounds change anything: that is the bound the
+// loops carry (it is never the reason they stop; it only keeps them finite by construction).
 #include "ia_common.h"
 
 namespace {
@@ -30,7 +34,7 @@ __global__ __launch_bounds__(kThreads) void fill_mouth_kernel(const float* __res
     __syncthreads();
     if (threadIdx.x == 0) st[0] = 2;
     __syncthreads();
-    for (int round = 0; round < H + W; ++round) {
+    for (int round = 0; round < H * W; ++round) {
         if (threadIdx.x == 0) changed = 0;
         __syncthreads();
         int local = 0;
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(kN) void fill_mouth256_kernel(const float* __restri
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < kNW; ++w) Pc[w] = Pcol[tid * kNW + w];
-    for (int round = 0; round < 2 * kN; ++round) {
+    for (int round = 0; round < kN * kN; ++round) {
         if (tid == 0) changed = 0;
         u64 before[kNW];
 #pragma unroll

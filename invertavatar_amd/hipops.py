@@ -942,13 +942,16 @@ def channels_last_copy(t):
 
 
 def blend_planes(stitch, full_alpha, static_planes, bbox):
-    """Channels-last blended tri-planes [B,3,256,256,32] (see ia_blend_planes).  static_planes [B,96,256,256]."""
+    """Channels-last blended tri-planes [B,3,256,256,32] (see ia_blend_planes).  static_planes [B,96,256,256]: dense per batch
+    element, any batch stride (0 for planes expanded over the batch; the kernel takes the stride)."""
     b = stitch.shape[0]
+    if not (static_planes.is_cuda and static_planes.dtype == torch.float32 and tuple(static_planes.stride()[1:]) == (65536, 256, 1)):
+        static_planes = _f32c(static_planes, 'static_planes')
     planes_cl = torch.empty(b, 3, 256, 256, 32, device=stitch.device, dtype=torch.float32)
     y0, y1, x0, x1 = bbox
     with torch.cuda.device(stitch.device):
         st = _lib.load().ia_blend_planes(_p(_f32c(stitch, 'stitch')), _p(_f32c(full_alpha, 'full_alpha')),
-                                         _p(_f32c(static_planes, 'static_planes')), static_planes.stride(0), _p(planes_cl),
+                                         static_planes.data_ptr(), static_planes.stride(0), _p(planes_cl),
                                          b, y0, y1, x0, x1, _lib.stream_ptr(stitch.device))
     _lib.check(st, 'ia_blend_planes')
     return planes_cl

@@ -1249,6 +1249,38 @@ int ia_texture_project(const float* point, const float* normal, const int* face,
 int ia_texture_sample(const float* texture, int size, int C, int s, int64_t F, const int* face, const float* bary, int64_t P, float* out,
                       void* stream);
 
+/*
+ * LPIPS (csrc/lpips.hip): the three kernels the perceptual score needs besides the 3x3 MFMA convolutions.  Replaces, for evaluation,
+ * encoder_inversion/criteria/lpips (lpips.py, networks.py, utils.py): torchvision feature stacks, normalize_activation, 1x1 linear
+ * layers and spatial means.
+ *
+ * ia_conv2d_direct: y[n,o,oy,ox] = act(bias[o] + sum_{i,ky,kx} w[o,i,ky,kx] * x[n,i,oy*stride - pad + ky, ox*stride - pad + kx]) with
+ * zeros outside the image; act = IA_ACT_RELU (v < 0 ? 0 : v) or IA_ACT_LINEAR.  x [N,I,H,W], w [O,I,k,k] (the module's own layout),
+ * bias [O] or NULL, y [N,O,OH,OW] with OH = (H + 2 pad - k) / stride + 1 (floor), all fp32.  1 <= k <= 11, stride 1 or 4,
+ * 0 <= pad < k, any channel counts, any H x W with OH, OW >= 1, N <= 65535.  fp32 fused multiply-adds in the order (i, ky, kx) within
+ * blocks of max(1, min(16, 144 / k^2)) input channels, whose sums are added in block order: the same bits run to run and for any batch.
+ *
+ * ia_maxpool2d: y[n,c,oy,ox] = max over the k x k window at (oy*stride, ox*stride), no padding, floor mode: OH = (H - k) / stride + 1.
+ * (k, stride) = (3, 2) or (2, 2).  The maximum is taken in row-major window order with `v > m || v != v`, torch.max_pool2d's rule: the
+ * results are its bits on finite inputs (and NaN propagates).  y fp32 [N,C,OH,OW] or NULL; ys or NULL: the same values in the split
+ * format of ia_act_split (ys_planes = 1 or 2, C % 8 == 0, styles = 1), for a 3x3 MFMA convolution behind the pool.  One of y / ys.
+ *
+ * ia_lpips_layer: one tap of a batch of N pairs.  f fp32 [2N,C,h,w]: maps n and N + n are the two images of pair n.  At every pixel
+ *     fx^_c = fx_c / (sqrt(sum_c fx_c^2) + 1e-10),  fy^ likewise (fp32; the sum of squares in channel order),
+ *     d = sum_c (double)lin[c] * (double)(fx^_c - fy^_c)^2   (the difference is formed in fp32 and squared in double, channel order),
+ * out[n * out_stride] = (float)(sum over the pixels of d / (h w)).  A thread owns a pixel; a workgroup adds its 256 pixels in double
+ * (xor tree in each wave, then the waves in order) into its slot of `scratch`, and a finalising launch adds a frame's slots
+ * lane-strided + xor tree: no floating-point atomics.  Identical maps give exactly 0, exchanging the halves of f gives the same bits,
+ * a pair's value does not depend on N, and the same inputs give the same bits.  lin [C]; scratch: ia_lpips_layer_scratch_bytes(N, h, w)
+ * bytes, 8-byte aligned; N <= 65535.
+ */
+int ia_conv2d_direct(const float* x, const float* w, const float* bias, float* y, int N, int I, int O, int H, int W, int k, int stride,
+                     int pad, int act, void* stream);
+int ia_maxpool2d(const float* x, float* y, void* ys, int ys_planes, int N, int C, int H, int W, int k, int stride, void* stream);
+int ia_lpips_layer_scratch_bytes(int N, int h, int w, size_t* h_bytes);
+int ia_lpips_layer(const float* f, const float* lin, int N, int C, int h, int w, void* scratch, size_t scratch_bytes, float* out,
+                   int out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

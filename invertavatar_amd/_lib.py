@@ -181,6 +181,10 @@ _SIGNATURES = {
     'ia_texture_project': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                            c_float, ctypes.c_double, c_float, c_int] + [c_void_p] * 6,
     'ia_texture_sample': [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_conv2d_direct': [c_void_p] * 4 + [c_int] * 9 + [c_void_p],
+    'ia_maxpool2d': [c_void_p] * 3 + [c_int] * 7 + [c_void_p],
+    'ia_lpips_layer_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_lpips_layer': [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p],
 }
 
 

@@ -2383,3 +2383,75 @@ def texture_sample(texture, s, n_faces, face, bary):
                                            _p(out), _lib.stream_ptr(dev))
     _lib.check(st, 'ia_texture_sample')
     return out
+
+
+# ------------------------------------------------------------------ LPIPS (csrc/lpips.hip)
+
+ACT_RELU = 2     # IA_ACT_RELU
+
+
+def conv2d_direct(x, w, bias=None, stride=1, padding=0, relu=True):
+    """ia_conv2d_direct: fp32 direct convolution + bias (+ ReLU) of x [N,I,H,W] with w [O,I,k,k] (k <= 11, stride 1 or 4, padding < k)."""
+    _f32c(x, 'x'), _f32c(w, 'w')
+    if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1] or w.shape[2] != w.shape[3] or w.device != x.device:
+        raise RuntimeError(f'conv2d_direct: x [N,I,H,W] and w [O,I,k,k] on one device, got {tuple(x.shape)} and {tuple(w.shape)}')
+    n, i, h, wd = x.shape
+    o, k = w.shape[0], w.shape[2]
+    if bias is not None and _f32c(bias, 'bias').numel() != o:
+        raise RuntimeError(f'conv2d_direct: bias has {bias.numel()} elements, expected {o}')
+    stride, padding = int(stride), int(padding)
+    if stride < 1 or h + 2 * padding < k or wd + 2 * padding < k:
+        raise RuntimeError(f'conv2d_direct: a {h} x {wd} image (padding {padding}) is smaller than the {k} x {k} kernel, or stride < 1')
+    oh, ow = (h + 2 * padding - k) // stride + 1, (wd + 2 * padding - k) // stride + 1
+    y = torch.empty(n, o, oh, ow, device=x.device, dtype=torch.float32)
+    flops = 2.0 * n * oh * ow * i * o * k * k
+    with torch.cuda.device(x.device), _Timed('conv2d_direct', flops, 4.0 * (x.numel() + w.numel() + y.numel()), f'N{n} I{i} O{o} {h}x{wd} k{k} s{stride}'):
+        st = _lib.load().ia_conv2d_direct(_p(x), _p(w), _p(bias), _p(y), n, i, o, h, wd, k, stride, padding, ACT_RELU if relu else ACT_ID['linear'],
+                                          _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_conv2d_direct')
+    return y
+
+
+def maxpool2d(x, kernel_size, stride=2, want_f32=True, want_split=False, split_planes=2, consumer=None):
+    """ia_maxpool2d: floor-mode max pool (k3 s2 or k2 s2) of fp32 [N,C,H,W].  Returns the fp32 result, a SplitAct (the operand of a 3x3
+    MFMA convolution behind the pool; C % 8 == 0), or the pair (y, ys) when both are asked for."""
+    _f32c(x, 'x')
+    if x.dim() != 4 or not (want_f32 or want_split):
+        raise RuntimeError('maxpool2d: x must be [N,C,H,W], and one of want_f32 / want_split')
+    n, c, h, w = x.shape
+    k, stride = int(kernel_size), int(stride)
+    if k < 1 or stride < 1 or h < k or w < k:
+        raise RuntimeError(f'maxpool2d: a {h} x {w} map is smaller than the {k} x {k} window')
+    if want_split and c % 8:
+        raise RuntimeError(f'the split format stores channels in groups of 8 (C = {c})')
+    oh, ow = (h - k) // stride + 1, (w - k) // stride + 1
+    y = torch.empty(n, c, oh, ow, device=x.device, dtype=torch.float32) if want_f32 else None
+    ys = torch.empty(n, split_planes, c // 8, oh, ow, 8, device=x.device, dtype=torch.float16) if want_split else None
+    with torch.cuda.device(x.device), _Timed('maxpool2d', 0.0, 4.0 * x.numel() + 4.0 * n * c * oh * ow * (int(want_f32) + int(want_split)),
+                                             f'N{n} C{c} {h}x{w} k{k}'):
+        st = _lib.load().ia_maxpool2d(_p(x), _p(y), _p(ys), int(split_planes), n, c, h, w, k, stride, _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_maxpool2d')
+    out_s = SplitAct(ys, c, consumer) if want_split else None
+    if want_f32 and want_split:
+        return y, out_s
+    return y if want_f32 else out_s
+
+
+def lpips_layer(f, lin, out=None):
+    """ia_lpips_layer: f fp32 [2N,C,h,w] (maps n and N + n are a pair), lin [C] -> float32 [N], the tap's layer value per pair; `out`:
+    a float32 [N] view (any stride) to write into, e.g. a column of the [N,5] table."""
+    _f32c(f, 'f'), _f32c(lin, 'lin')
+    if f.dim() != 4 or f.shape[0] % 2 or f.shape[0] < 2 or lin.numel() != f.shape[1] or lin.device != f.device:
+        raise RuntimeError(f'lpips_layer: f [2N,C,h,w] and lin [C] on one device, got {tuple(f.shape)} and {tuple(lin.shape)}')
+    n, c, h, w = f.shape[0] // 2, f.shape[1], f.shape[2], f.shape[3]
+    if out is None:
+        out = torch.empty(n, device=f.device, dtype=torch.float32)
+    if not (out.is_cuda and out.device == f.device and out.dtype == torch.float32 and out.dim() == 1 and out.shape[0] == n
+            and (n == 1 or out.stride(0) >= 1)):
+        raise RuntimeError('lpips_layer: out must be a float32 [N] device view with a positive stride')
+    scratch, nbytes = _scratch('ia_lpips_layer_scratch_bytes', n, h, w, dtype=torch.float64, device=f.device)
+    with torch.cuda.device(f.device), _Timed('lpips_layer', 6.0 * f.numel(), 8.0 * f.numel(), f'N{n} C{c} {h}x{w}'):
+        st = _lib.load().ia_lpips_layer(_p(f), _p(lin), n, c, h, w, _p(scratch), nbytes, _p(out), max(int(out.stride(0)), 1),
+                                        _lib.stream_ptr(f.device))
+    _lib.check(st, 'ia_lpips_layer')
+    return out

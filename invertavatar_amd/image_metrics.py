@@ -11,10 +11,12 @@ the device tests.  Inputs: float32 ``[N,C,H,W]`` (what ``synthesis`` returns; ``
 or uint8 ``[N,H,W,C]`` (what the output side holds; ``data_range`` defaults to 255), ``1 <= C <= 4``.
 
 CLI:  python -m invertavatar_amd.image_metrics --pred P --gt G [--data-range R] [--levels K] [--chunk N] --out metrics.json
-where P / G are ``.npy`` stacks or directories of them (sorted order)."""
+where P / G are ``.npy`` stacks or directories of them (sorted order).  ``--lpips alex|vgg --lpips-weights FILE --lpips-lin FILE`` adds
+LPIPS (``invertavatar_amd/lpips.py``) per frame; ``--lpips-synthetic SEED`` takes seeded weights instead (smoke runs: meaningless scores)."""
 import json
 import math
 import os
+import sys
 
 import numpy as np
 import torch
@@ -140,13 +142,17 @@ class ClipMetrics:
     """Scores of a clip, gathered call by call: ``update`` keeps each call's per-frame results where they were computed (no host
     synchronisation); ``summary`` makes the clip's one device -> host read."""
 
-    def __init__(self, data_range=2.0, levels=MAX_LEVELS):
-        self.data_range, self.levels = data_range, levels
+    def __init__(self, data_range=2.0, levels=MAX_LEVELS, lpips=None):
+        self.data_range, self.levels, self.lpips = data_range, levels, lpips      # lpips: an lpips.LPIPS model, or None
         self._calls = []
 
     def update(self, pred, gt):
-        self._calls.append(compare(pred, gt, self.data_range, self.levels))
-        return self._calls[-1]
+        res = compare(pred, gt, self.data_range, self.levels)
+        if self.lpips is not None:
+            from . import lpips as _lpips
+            res.update(_lpips.compare(pred, gt, self.lpips, self.data_range))
+        self._calls.append(res)
+        return res
 
     def reset(self):
         self._calls = []
@@ -200,8 +206,8 @@ def _frames(files):
         yield arr[None] if arr.ndim == 3 else arr
 
 
-def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None):
-    """Scores two ``.npy`` stacks (or directories of them) chunk by chunk -> ClipMetrics."""
+def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None, lpips=None):
+    """Scores two ``.npy`` stacks (or directories of them) chunk by chunk -> ClipMetrics (with LPIPS when `lpips` is a model)."""
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
     p_files, g_files = _stack_files(pred), _stack_files(gt)
     if len(p_files) != len(g_files):
@@ -214,7 +220,7 @@ def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=N
             a = torch.from_numpy(np.array(pa[lo:lo + chunk])).to(device)
             b = torch.from_numpy(np.array(ga[lo:lo + chunk])).to(device)
             if clip is None:
-                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels)
+                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels, lpips)
             clip.update(a, b)
     return clip
 
@@ -229,8 +235,24 @@ def main(argv=None):
     ap.add_argument('--chunk', type=int, default=16, help='frames per device call')
     ap.add_argument('--device', default=None)
     ap.add_argument('--out', required=True)
+    ap.add_argument('--lpips', choices=('alex', 'vgg'), default=None, help='also score LPIPS with this backbone')
+    ap.add_argument('--lpips-weights', default=None, help="the backbone's torchvision state dict (alexnet / vgg16)")
+    ap.add_argument('--lpips-lin', default=None, help='the LPIPS v0.1 linear layers of the backbone')
+    ap.add_argument('--lpips-synthetic', type=int, default=None, metavar='SEED', help='seeded weights instead of files (smoke runs only)')
     args = ap.parse_args(argv)
-    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device).write_json(args.out)
+    model = None
+    if args.lpips is not None:
+        from . import lpips as _lpips
+        if args.lpips_synthetic is not None:
+            print(f'warning: LPIPS with synthetic weights (seed {args.lpips_synthetic}): the lpips numbers mean nothing', file=sys.stderr)
+            model = _lpips.LPIPS.synthetic(args.lpips, args.lpips_synthetic)
+        elif args.lpips_weights and args.lpips_lin:
+            model = _lpips.LPIPS(args.lpips, args.lpips_weights, args.lpips_lin)
+        else:
+            ap.error('--lpips needs --lpips-weights and --lpips-lin (or --lpips-synthetic SEED)')
+    elif args.lpips_weights or args.lpips_lin or args.lpips_synthetic is not None:
+        ap.error('--lpips-weights / --lpips-lin / --lpips-synthetic need --lpips alex|vgg')
+    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device, model).write_json(args.out)
     print(json.dumps({'frames': res['frames'], 'mean': res['mean']}))
     return 0
 

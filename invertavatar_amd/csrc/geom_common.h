@@ -1,7 +1,7 @@
-// Primitives shared by the geometry translation units (geometry, raycast, components, surface_distance, simplify, smooth): scans,
-// wave reductions, 3-vectors, lattice helpers and the host-side argument checks.  Device code is __forceinline__ functions and
-// templates only, no kernels: every .hip is its own code object, so a kernel that needs one of these (the scan) is a wrapper of a few
-// lines in that file's anonymous namespace.  Every operation order here is part of the results (geometry.py restates them in NumPy).
+// Primitives shared by the geometry translation units (every .hip that includes this file, and cluster_tree.h on top of it): scans,
+// wave reductions, 3-vectors, the per-triangle functions, lattice helpers and the host-side argument checks.  Device code is
+// __forceinline__ functions and templates only, no kernels: every .hip is its own code object, so a kernel that needs one of these (the
+// scan) is a wrapper of a few lines in that file's anonymous namespace.  Every operation order here is part of the results (geometry.py restates them in NumPy).
 #pragma once
 
 #include "ia_common.h"

@@ -6,8 +6,7 @@
 //            on the longest side of the box of the finite vertices; fp32: ((A + B) + C) * fp32(1/3), floor((c - lo) * scale), clamped
 //            to [0, 1023]; x is the lowest bit of a triple).  The sort of the keys is the caller's (stable: ties by face index);
 //            unusable triangles have the key 2^30, go last and belong to no leaf.
-// Tree     : leaf i = sorted faces [i L, min((i + 1) L, Fu)), L = kLeaf; level k + 1 groups B = kBranch consecutive nodes of level
-//            k until one root is left.  Node (level, index) sits at row start[level] + index, leaves first; there are no pointers.
+// Tree     : leaves of L = kLeaf sorted faces under nodes of B = kBranch children, level by level (cluster_tree.h).
 // Node row : 5 float4 = (c.x, c.y, c.z, r) (D.x, D.y, D.z, A) (Q00, Q01, Q02, Q10) (Q11, Q12, Q20, Q21) (Q22, 0, 0, 0) with
 //            A = sum a_t, D = sum a_t n_t, c = sum a_t c_t / A (the mean of the c_t when A = 0), Q = sum (c_t - c) (x) a_t n_t and
 //            r = the largest distance of a vertex from c.  Leaves are summed in double in face order; an upper node is formed in
@@ -19,52 +18,22 @@
 //            ((D . x + tr Q) - 3 (x^T Q x) / d2) / (d2 sqrt(d2)); else a leaf adds solid_angle of its faces in sorted order; else
 //            descend.  Terms are fp32, the running sum is double in visiting order, the result is the sum over 4 pi.  The value is
 //            a pure function of point, mesh and beta.
-// Kernel   : a wave walks the UNION of its 64 lanes' traversals without a stack: (level, index) are wave-uniform, a node is visited
-//            while the ballot of lanes that need it is non-zero, and a lane that accepted a node as far stays masked until the walk
-//            leaves that subtree.  Node rows and leaf triangles are wave-uniform loads; every lane adds exactly its own terms in
-//            its own order, so the result does not depend on which points share its wave.
-#include "geom_common.h"
+// Kernel   : the wave-union walk of cluster_tree.h: a lane holds a node it accepted as far and needs what is below a near one.
+#include "cluster_tree.h"
 
 #include <cmath>
 
 namespace {
 
 using ia::blocks; using ia::on_device;
+using namespace ia::tree;
 
 constexpr int kBlock = 256;
-constexpr int kLeaf = 32;                            // faces per leaf: part of the results
-constexpr int kBranch = 8;                           // children per upper node: part of the results
-constexpr int kLeafShift = 5, kBranchShift = 3;
-constexpr int kMaxLevels = 8;                        // 2^25 faces -> 2^20 leaves -> 8 levels
 constexpr int kRow = 20;                             // floats per node row, and doubles per scratch row
 constexpr int kNoKey = 1 << 30;                      // key of an unusable triangle / a non-finite point
-constexpr int64_t kMaxFaces = (int64_t)1 << 25;      // the limit of ia_tri_pack
-static_assert((1 << kLeafShift) == kLeaf && (1 << kBranchShift) == kBranch, "shifts");
 
 using V3 = ia::Vec3<float>;
 using D3 = ia::Vec3<double>;
-
-struct Levels {
-    int n;                                           // number of levels (0: no usable face)
-    int count[kMaxLevels];
-    int start[kMaxLevels];
-    int total;
-};
-
-Levels levels_of(int64_t Fu) {
-    Levels t = {};
-    if (Fu <= 0) return t;
-    int64_t c = ia::ceil_div(Fu, (int64_t)kLeaf);
-    for (;;) {
-        t.count[t.n] = (int)c;
-        t.start[t.n] = t.total;
-        t.total += (int)c;
-        ++t.n;
-        if (c == 1) break;
-        c = ia::ceil_div(c, (int64_t)kBranch);
-    }
-    return t;
-}
 
 // ------------------------------------------------------------------ Morton keys
 
@@ -88,10 +57,10 @@ __device__ __forceinline__ int morton(V3 p, V3 lo, float scale) {
 __global__ __launch_bounds__(kBlock) void face_keys_kernel(const float4* __restrict__ tris, int F, V3 lo, float scale, int* __restrict__ keys) {
     const int f = blockIdx.x * kBlock + threadIdx.x;
     if (f >= F) return;
-    const float4 A = tris[3 * (int64_t)f], B = tris[3 * (int64_t)f + 1], C = tris[3 * (int64_t)f + 2];
+    const Tri t = load_tri(tris, f);
     const float third = 1.f / 3.f;
-    const V3 c = {((A.x + B.x) + C.x) * third, ((A.y + B.y) + C.y) * third, ((A.z + B.z) + C.z) * third};
-    keys[f] = A.w == 0.f ? kNoKey : morton(c, lo, scale);
+    const V3 c = {((t.A.x + t.B.x) + t.C.x) * third, ((t.A.y + t.B.y) + t.C.y) * third, ((t.A.z + t.B.z) + t.C.z) * third};
+    keys[f] = t.A.w == 0.f ? kNoKey : morton(c, lo, scale);
 }
 
 __global__ __launch_bounds__(kBlock) void point_keys_kernel(const float* __restrict__ pts, int64_t N, V3 lo, float scale, int* __restrict__ keys) {
@@ -152,11 +121,12 @@ __global__ __launch_bounds__(kBlock) void leaf_kernel(const float4* __restrict__
                                                       float4* __restrict__ nodes) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= leaves) return;
-    const int f0 = i * kLeaf, f1 = min(f0 + kLeaf, Fu);
+    const Range fr = leaf_range(i, Fu);
     Node64 n = {};
     D3 S = {0.0, 0.0, 0.0}, M = {0.0, 0.0, 0.0};
-    for (int f = f0; f < f1; ++f) {
-        const D3 A = d3(tris[3 * (int64_t)f]), B = d3(tris[3 * (int64_t)f + 1]), C = d3(tris[3 * (int64_t)f + 2]);
+    for (int f = fr.lo; f < fr.hi; ++f) {
+        const Tri t = load_tri(tris, f);
+        const D3 A = d3(t.A), B = d3(t.B), C = d3(t.C);
         const D3 an = mul(cross(sub(B, A), sub(C, A)), 0.5);                // area times unit normal
         const double a = sqrt(dot(an, an));
         const D3 ct = mul(add(add(A, B), C), 1.0 / 3.0);
@@ -165,9 +135,10 @@ __global__ __launch_bounds__(kBlock) void leaf_kernel(const float4* __restrict__
         S = add(S, mul(ct, a));
         M = add(M, ct);
     }
-    n.c = n.A > 0.0 ? mul(S, 1.0 / n.A) : mul(M, 1.0 / (double)(f1 - f0));
-    for (int f = f0; f < f1; ++f) {
-        const D3 A = d3(tris[3 * (int64_t)f]), B = d3(tris[3 * (int64_t)f + 1]), C = d3(tris[3 * (int64_t)f + 2]);
+    n.c = n.A > 0.0 ? mul(S, 1.0 / n.A) : mul(M, 1.0 / (double)(fr.hi - fr.lo));
+    for (int f = fr.lo; f < fr.hi; ++f) {
+        const Tri t = load_tri(tris, f);
+        const D3 A = d3(t.A), B = d3(t.B), C = d3(t.C);
         const D3 an = mul(cross(sub(B, A), sub(C, A)), 0.5);
         const D3 ct = mul(add(add(A, B), C), 1.0 / 3.0);
         add_outer(n.Q, sub(ct, n.c), an);
@@ -182,11 +153,11 @@ __global__ __launch_bounds__(kBlock) void upper_kernel(int Fu, int span, int chi
                                                        double* __restrict__ rows, float4* __restrict__ nodes) {
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= count) return;
-    const int k0 = j * kBranch, k1 = min(k0 + kBranch, children);
+    const Range kr = child_range(j, children);
     Node64 n = {};
     D3 S = {0.0, 0.0, 0.0}, M = {0.0, 0.0, 0.0};
     double faces = 0.0;
-    for (int k = k0; k < k1; ++k) {
+    for (int k = kr.lo; k < kr.hi; ++k) {
         const double* row = rows + (int64_t)(child_start + k) * kRow;
         const D3 ck = {row[0], row[1], row[2]};
         const double nk = (double)(min((int64_t)(k + 1) * span, (int64_t)Fu) - (int64_t)k * span);
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void upper_kernel(int Fu, int span, int chi
         faces += nk;
     }
     n.c = n.A > 0.0 ? mul(S, 1.0 / n.A) : mul(M, 1.0 / faces);
-    for (int k = k0; k < k1; ++k) {
+    for (int k = kr.lo; k < kr.hi; ++k) {
         const double* row = rows + (int64_t)(child_start + k) * kRow;
         const D3 u = sub(D3{row[0], row[1], row[2]}, n.c);
 #pragma unroll
@@ -210,20 +181,13 @@ __global__ __launch_bounds__(kBlock) void upper_kernel(int Fu, int span, int chi
 
 // ------------------------------------------------------------------ query
 
-struct Tree {
-    int top;                                         // level of the root; -1: no node
-    int start[kMaxLevels];
-};
-
 constexpr double kFourPi = 4.0 * 3.14159265358979323846;
 
 // counts: int32 [N, 2] = far terms and exact pairs of the point; bound: sum over the far terms of 3 A r^2 / (4 pi (d - r)^4).
 __global__ __launch_bounds__(kBlock) void query_kernel(const float* __restrict__ pts, int64_t N, const float4* __restrict__ tris, int Fu,
                                                        const float4* __restrict__ nodes, Tree tree, float beta, double* __restrict__ out,
                                                        double* __restrict__ bound, int* __restrict__ counts) {
-    __shared__ int s_start[kMaxLevels];
-    if (threadIdx.x < kMaxLevels) s_start[threadIdx.x] = tree.start[threadIdx.x];
-    __syncthreads();
+    IA_TREE_STAGE(tree);
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     V3 q = {0.f, 0.f, 0.f};
     bool ok = false;
@@ -233,18 +197,15 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const float* __restrict__
     }
     double acc = 0.0, bnd = 0.0;
     int n_far = 0, n_exact = 0;
-    int held = ok ? -1 : kMaxLevels;                 // level of the far node this lane waits under; -1: walking; kMaxLevels: never walks
-    int l = tree.top, j = 0;                         // (wave-uniform)
-    while (l >= 0) {
-        const float4* row = nodes + 5 * (int64_t)(__builtin_amdgcn_readfirstlane(s_start[l]) + j);
+    IA_TREE_WALK(tree, ok)
+        const float4* row = nodes + 5 * (int64_t)node;
         const float4 n0 = row[0], n1 = row[1];
         const V3 x = {n0.x - q.x, n0.y - q.y, n0.z - q.z};
         const float d2 = dot(x, x);
         const float br = beta * n0.w;
-        const bool walking = held < 0;
-        const bool far = walking && d2 > br * br;
-        const bool near = walking && !far;
-        if (far) {
+        const bool walking = IA_TREE_WALKING;
+        const bool hold = walking && d2 > br * br, need = walking && !hold;      // far, near
+        if (hold) {
             const float4 n2 = row[2], n3 = row[3], n4 = row[4];
             const V3 D = {n1.x, n1.y, n1.z};
             const V3 Qx = {dot(V3{n2.x, n2.y, n2.z}, x), dot(V3{n2.w, n3.x, n3.y}, x), dot(V3{n3.z, n3.w, n4.x}, x)};
@@ -254,31 +215,15 @@ __global__ __launch_bounds__(kBlock) void query_kernel(const float* __restrict__
             const double e = sqrt((double)d2) - (double)n0.w;
             bnd += 3.0 * (double)n1.w * ((double)n0.w * (double)n0.w) / (kFourPi * ((e * e) * (e * e)));
             ++n_far;
-            held = l;
         }
-        if (l > 0) {
-            if (__ballot(near)) {                    // some lane needs the children
-                --l;
-                j *= kBranch;
-                continue;
-            }
-        } else if (__ballot(near)) {
-            const int f0 = j * kLeaf, f1 = min(f0 + kLeaf, Fu);
-            for (int f = f0; f < f1; ++f) {          // (the same triangle in every lane)
-                const float4 A = tris[3 * (int64_t)f], B = tris[3 * (int64_t)f + 1], C = tris[3 * (int64_t)f + 2];
-                if (near) acc += (double)solid_angle(q, {A.x, A.y, A.z}, {B.x, B.y, B.z}, {C.x, C.y, C.z});
-            }
-            if (near) n_exact += f1 - f0;
+    IA_TREE_LEAF
+        const Range fr = leaf_range(j, Fu);
+        for (int f = fr.lo; f < fr.hi; ++f) {
+            const float4 A = tris[3 * (int64_t)f], B = tris[3 * (int64_t)f + 1], C = tris[3 * (int64_t)f + 2];     // (load_tri here: 6 more VGPRs)
+            if (need) acc += (double)solid_angle(q, xyz(A), xyz(B), xyz(C));
         }
-        for (;;) {                                   // the subtree of (l, j) is done: the next node in depth-first order
-            if (held == l) held = -1;
-            if (l == tree.top) { l = -1; break; }
-            const int count = (Fu + (kLeaf << (kBranchShift * l)) - 1) >> (kLeafShift + kBranchShift * l);
-            if (((j + 1) & (kBranch - 1)) != 0 && j + 1 < count) { ++j; break; }
-            j >>= kBranchShift;
-            ++l;
-        }
-    }
+        if (need) n_exact += fr.hi - fr.lo;
+    IA_TREE_END(tree, const int count = IA_TREE_COUNT(Fu, l), count)
     if (i >= N) return;
     out[i] = ok ? acc / kFourPi : (double)NAN;
     if (bound) bound[i] = ok ? bnd : (double)NAN;
@@ -303,7 +248,7 @@ extern "C" int ia_winding_tree_layout(int* h_leaf, int* h_branch, int* h_row_flo
 }
 
 extern "C" int ia_winding_tree_plan(int64_t F_usable, int* h_levels, int* h_counts, int64_t* h_nodes, size_t* h_scratch_bytes) {
-    IA_REQUIRE(F_usable >= 0 && F_usable <= kMaxFaces, "ia_winding_tree_plan: F_usable must be >= 0 and <= 2^25, got %lld", (long long)F_usable);
+    if (int e = check_faces(F_usable, "ia_winding_tree_plan")) return e;
     IA_REQUIRE(h_levels && h_counts && h_nodes && h_scratch_bytes, "ia_winding_tree_plan: the four outputs must not be NULL");
     const Levels t = levels_of(F_usable);
     *h_levels = t.n;
@@ -324,7 +269,7 @@ extern "C" int ia_winding_tree_face_keys(const void* tris, int64_t F, const floa
 }
 
 extern "C" int ia_winding_tree_point_keys(const float* points, int64_t N, const float* h_lo, float h_scale, int* keys, void* stream) {
-    IA_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) / 3, "ia_winding_tree_point_keys: N must be >= 0 and 3 N < 2^31, got %lld", (long long)N);
+    if (int e = check_points(N, "ia_winding_tree_point_keys")) return e;
     if (int e = check_cube(h_lo, h_scale, "ia_winding_tree_point_keys")) return e;
     if (N == 0) return IA_OK;
     if (!on_device(points) || !on_device(keys)) return ia::fail(IA_ERR_INVALID_ARG, "ia_winding_tree_point_keys: points and keys must be device pointers");
@@ -345,10 +290,9 @@ extern "C" int ia_winding_tree_gather(const void* tris, int64_t F, const int* or
 
 extern "C" int ia_winding_tree_nodes(const void* sorted, int64_t F_usable, void* scratch, size_t scratch_bytes, void* nodes, int64_t n_nodes,
                                      void* stream) {
-    IA_REQUIRE(F_usable >= 0 && F_usable <= kMaxFaces, "ia_winding_tree_nodes: F_usable must be >= 0 and <= 2^25, got %lld", (long long)F_usable);
+    if (int e = check_faces(F_usable, "ia_winding_tree_nodes")) return e;
     const Levels t = levels_of(F_usable);
-    IA_REQUIRE(n_nodes == t.total, "ia_winding_tree_nodes: %lld usable faces make %d nodes, got n_nodes = %lld", (long long)F_usable, t.total,
-               (long long)n_nodes);
+    if (int e = check_nodes(t, F_usable, n_nodes, "ia_winding_tree_nodes")) return e;
     const size_t need = sizeof(double) * (size_t)kRow * (size_t)t.total;
     if (scratch_bytes < need) return ia::fail(IA_ERR_INVALID_ARG, "ia_winding_tree_nodes: scratch holds %zu bytes, needs %zu", scratch_bytes, need);
     if (t.n == 0) return IA_OK;
@@ -370,20 +314,16 @@ extern "C" int ia_winding_tree_nodes(const void* sorted, int64_t F_usable, void*
 
 extern "C" int ia_winding_tree_query(const float* points, int64_t N, const void* sorted, int64_t F_usable, const void* nodes, int64_t n_nodes,
                                      float beta, double* out, double* bound, int* counts, void* stream) {
-    IA_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) / 3, "ia_winding_tree_query: N must be >= 0 and 3 N < 2^31, got %lld", (long long)N);
-    IA_REQUIRE(F_usable >= 0 && F_usable <= kMaxFaces, "ia_winding_tree_query: F_usable must be >= 0 and <= 2^25, got %lld", (long long)F_usable);
+    if (int e = check_points(N, "ia_winding_tree_query")) return e;
+    if (int e = check_faces(F_usable, "ia_winding_tree_query")) return e;
     IA_REQUIRE(beta > 1.f, "ia_winding_tree_query: beta must be greater than 1 (inf: never far), got %g", (double)beta);
     const Levels t = levels_of(F_usable);
-    IA_REQUIRE(n_nodes == t.total, "ia_winding_tree_query: %lld usable faces make %d nodes, got n_nodes = %lld", (long long)F_usable, t.total,
-               (long long)n_nodes);
+    if (int e = check_nodes(t, F_usable, n_nodes, "ia_winding_tree_query")) return e;
     if (N == 0) return IA_OK;
     if (!on_device(points) || !on_device(out) || (bound && !on_device(bound)) || (counts && !on_device(counts)) ||
         (t.n && (!on_device(sorted) || !on_device(nodes))))
         return ia::fail(IA_ERR_INVALID_ARG, "ia_winding_tree_query: points, sorted, nodes, out, bound and counts must be device pointers");
-    Tree tree = {};
-    tree.top = t.n - 1;
-    for (int l = 0; l < t.n; ++l) tree.start[l] = t.start[l];
     query_kernel<<<blocks(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(points, N, static_cast<const float4*>(sorted), (int)F_usable,
-                                                                        static_cast<const float4*>(nodes), tree, beta, out, bound, counts);
+                                                                        static_cast<const float4*>(nodes), tree_of(t), beta, out, bound, counts);
     return ia::check_launch("ia_winding_tree_query");
 }

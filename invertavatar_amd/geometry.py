@@ -1474,6 +1474,18 @@ def _winding_tree_numpy(verts, faces):
     return {'order': order, 'tris': t32, 'nodes64': rows, 'counts': counts, 'usable': fu, 'lo': lo, 'scale': scale}
 
 
+def _tree_walk(counts, idx, visit):
+    """The walk of csrc/cluster_tree.h over the level layout ``counts``, depth first, children in index order: ``visit(level, j, row,
+    idx)`` does the work of the points ``idx`` at that node (table row ``row``) and returns those that go below; none prunes the subtree."""
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    stack = [(len(counts) - 1, 0, idx)] if counts and idx.size else []
+    while stack:
+        lvl, j, idx = stack.pop()
+        below = visit(lvl, j, starts[lvl] + j, idx)
+        if lvl > 0 and below.size:
+            stack.extend((lvl - 1, k, below) for k in range(min((j + 1) * WINDING_BRANCH, counts[lvl - 1]) - 1, j * WINDING_BRANCH - 1, -1))
+
+
 def _winding_tree_query_numpy(points, tris, nodes, counts, beta, dtype=np.float64, use_q=True):
     """NumPy restatement of ia_winding_tree_query on a float32 node table ``nodes`` [n,20] and the sorted usable triangles ``tris``
     [F_usable,3,3]: ``(w, bound, size, far, pairs)`` per point, with the terms evaluated in ``dtype``, ``size = sum |term| / 4 pi``,
@@ -1487,43 +1499,39 @@ def _winding_tree_query_numpy(points, tris, nodes, counts, beta, dtype=np.float6
     total, bound, size = np.zeros(n), np.zeros(n), np.zeros(n)
     far_n, pair_n = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
     ok = np.isfinite(p32).all(1)
-    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    stack = [(len(counts) - 1, 0, np.flatnonzero(ok))] if counts else []
+
+    def visit(lvl, j, at, idx):
+        row = nodes[at]
+        x32 = row[:3] - p32[idx]
+        d2 = (x32[:, 0] * x32[:, 0] + x32[:, 1] * x32[:, 1]) + x32[:, 2] * x32[:, 2]
+        br = b32 * row[3]
+        far = d2 > br * br
+        if far.any():
+            r = idx[far]
+            x = (row[:3].astype(dtype) - p[r]).astype(dtype)
+            dd = _dot3(x, x)
+            D, Q = row[4:7].astype(dtype), row[8:17].astype(dtype).reshape(3, 3)
+            if not use_q:
+                Q = Q * dtype(0)
+            qx = np.stack([_dot3(Q[0], x), _dot3(Q[1], x), _dot3(Q[2], x)], -1)
+            tr = (Q[0, 0] + Q[1, 1]) + Q[2, 2]
+            term = (((_dot3(D, x) + tr) - dtype(3) * _dot3(x, qx) / dd) / (dd * np.sqrt(dd))).astype(np.float64)
+            total[r] += term
+            size[r] += np.abs(term)
+            e = np.sqrt(d2[far].astype(np.float64)) - np.float64(row[3])
+            bound[r] += 3.0 * np.float64(row[7]) * (np.float64(row[3]) * np.float64(row[3])) / (4.0 * np.pi * ((e * e) * (e * e)))
+            far_n[r] += 1
+        r = idx[~far]
+        if lvl == 0 and r.size:
+            sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, fu))
+            om = _solid_angle(p[r, None, :], t[None, sl, 0], t[None, sl, 1], t[None, sl, 2], dtype).astype(np.float64)
+            total[r] = np.cumsum(np.concatenate([total[r, None], om], 1), axis=1)[:, -1]           # one term at a time, in face order
+            size[r] += np.abs(om).sum(1)
+            pair_n[r] += sl.stop - sl.start
+        return r
+
     with np.errstate(invalid='ignore', over='ignore', under='ignore', divide='ignore'):
-        while stack:
-            lvl, j, idx = stack.pop()
-            row = nodes[starts[lvl] + j]
-            x32 = row[:3] - p32[idx]
-            d2 = (x32[:, 0] * x32[:, 0] + x32[:, 1] * x32[:, 1]) + x32[:, 2] * x32[:, 2]
-            br = b32 * row[3]
-            far = d2 > br * br
-            if far.any():
-                r = idx[far]
-                x = (row[:3].astype(dtype) - p[r]).astype(dtype)
-                dd = _dot3(x, x)
-                D, Q = row[4:7].astype(dtype), row[8:17].astype(dtype).reshape(3, 3)
-                if not use_q:
-                    Q = Q * dtype(0)
-                qx = np.stack([_dot3(Q[0], x), _dot3(Q[1], x), _dot3(Q[2], x)], -1)
-                tr = (Q[0, 0] + Q[1, 1]) + Q[2, 2]
-                term = (((_dot3(D, x) + tr) - dtype(3) * _dot3(x, qx) / dd) / (dd * np.sqrt(dd))).astype(np.float64)
-                total[r] += term
-                size[r] += np.abs(term)
-                e = np.sqrt(d2[far].astype(np.float64)) - np.float64(row[3])
-                bound[r] += 3.0 * np.float64(row[7]) * (np.float64(row[3]) * np.float64(row[3])) / (4.0 * np.pi * ((e * e) * (e * e)))
-                far_n[r] += 1
-            r = idx[~far]
-            if not r.size:
-                continue
-            if lvl == 0:
-                sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, fu))
-                om = _solid_angle(p[r, None, :], t[None, sl, 0], t[None, sl, 1], t[None, sl, 2], dtype).astype(np.float64)
-                total[r] = np.cumsum(np.concatenate([total[r, None], om], 1), axis=1)[:, -1]       # one term at a time, in face order
-                size[r] += np.abs(om).sum(1)
-                pair_n[r] += sl.stop - sl.start
-            else:
-                k1 = min((j + 1) * WINDING_BRANCH, counts[lvl - 1])
-                stack.extend((lvl - 1, k, r) for k in range(k1 - 1, j * WINDING_BRANCH - 1, -1))
+        _tree_walk(counts, np.flatnonzero(ok), visit)
     w, big = total / (4.0 * np.pi), size / (4.0 * np.pi)
     w[~ok] = np.nan
     big[~ok] = np.nan
@@ -1628,21 +1636,18 @@ def _closest_tree_numpy(points, tree, dtype=np.float64, slack=None):
             seed[rows] = j
             for leaf_j in np.unique(j):
                 leaf(int(leaf_j), rows[j == leaf_j])
-        stack = [(len(counts) - 1, 0, rows)] if rows.size else []
-        while stack:
-            lvl, j, idx = stack.pop()
+
+        def visit(lvl, j, at, idx):
             if lvl == 0:
                 idx = idx[seed[idx] != j]
-            lb = _box_dist(p[idx], boxes[starts[lvl] + j])
+            lb = _box_dist(p[idx], boxes[at])
             n_box[idx] += 1
             r = idx[~(np.isfinite(lb) & (lb - margin[idx] > best_d[idx]))]
-            if not r.size:
-                continue
-            if lvl == 0:
+            if lvl == 0 and r.size:
                 leaf(j, r)
-            else:
-                k1 = min((j + 1) * WINDING_BRANCH, counts[lvl - 1])
-                stack.extend((lvl - 1, k, r) for k in range(k1 - 1, j * WINDING_BRANCH - 1, -1))
+            return r
+
+        _tree_walk(counts, rows, visit)
         hit = best_f >= 0
         at = np.where(hit, best_at, 0)
         point = np.full((n, 3), np.nan, dtype=dtype)
@@ -1692,6 +1697,17 @@ class WindingTree:
         """The tree of the mesh of a ``TriangleGrid``, from its packed triangles."""
         return cls(None, None, grid=grid)
 
+    def _sorted(self, points, sort, fn):
+        """``list(fn(hipops, pts))`` for device points as float32 [N,3], Morton-sorted if ``sort`` and N > 64; unsorted on return."""
+        from . import hipops
+        pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        if not (sort and pts.shape[0] > 64):
+            return list(fn(hipops, pts))
+        perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
+        back = torch.empty_like(perm)
+        back[perm] = torch.arange(perm.numel(), device=perm.device)
+        return [None if x is None else x[back] for x in fn(hipops, pts[perm].contiguous())]
+
     def query(self, points, beta=2.0, return_bound=False, return_counts=False, sort=True):
         """Winding numbers float64 [...] of points [..., 3]; with ``return_bound`` also the truncation bound, with ``return_counts``
         also int [..., 2] (far terms, exact pairs).  ``sort`` (device): query in Morton order of the points, so that a wave's lanes walk
@@ -1699,18 +1715,8 @@ class WindingTree:
         b32 = _winding_beta(beta)
         lead = tuple(points.shape[:-1])
         if self.device is not None:
-            from . import hipops
-            pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
-            perm = None
-            if sort and pts.shape[0] > 64:
-                perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
-                pts = pts[perm].contiguous()
-            res = hipops.winding_tree_query(pts, self.tris, self.nodes, self.usable, float(b32), bound=return_bound, counts=return_counts)
-            if perm is not None:
-                back = torch.empty_like(perm)
-                back[perm] = torch.arange(perm.numel(), device=perm.device)
-                res = [None if x is None else x[back] for x in res]
-            w, bound, cnt = res
+            w, bound, cnt = self._sorted(points, sort, lambda hipops, pts: hipops.winding_tree_query(
+                pts, self.tris, self.nodes, self.usable, float(b32), bound=return_bound, counts=return_counts))
             out = [w.reshape(lead)]
             if return_bound:
                 out.append(bound.reshape(lead))
@@ -1724,7 +1730,6 @@ class WindingTree:
             if return_counts:
                 out.append(_as_out(np.stack([nf, npair], -1).reshape(lead + (2,)), points, np.int64))
         return out[0] if len(out) == 1 else tuple(out)
-
 
     @property
     def boxes(self):
@@ -1745,20 +1750,10 @@ class WindingTree:
         the caller's order; it changes no result.  A host tree answers in float64."""
         lead = tuple(points.shape[:-1])
         if self.device is not None:
-            from . import hipops
-            pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
             if self._order32 is None:
                 self._order32 = self.order.int().contiguous()
-            perm = None
-            if sort and pts.shape[0] > 64:
-                perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
-                pts = pts[perm].contiguous()
-            res = hipops.closest_point_tree(pts, self.tris, self._order32, self.boxes, self.usable, self.extent, counts=return_counts)
-            if perm is not None:
-                back = torch.empty_like(perm)
-                back[perm] = torch.arange(perm.numel(), device=perm.device)
-                res = [None if x is None else x[back] for x in res]
-            dist, face, point, cnt = res
+            dist, face, point, cnt = self._sorted(points, sort, lambda hipops, pts: hipops.closest_point_tree(
+                pts, self.tris, self._order32, self.boxes, self.usable, self.extent, counts=return_counts))
             out = {'dist': dist.reshape(lead), 'face': face.long().reshape(lead), 'point': point.reshape(lead + (3,))}
             if return_counts:
                 out['counts'] = cnt.reshape(lead + (2,))

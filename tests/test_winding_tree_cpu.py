@@ -58,6 +58,19 @@ def test_layout_is_the_kernels():
     assert geometry._winding_levels(13324) == [417, 53, 7, 1]
 
 
+def test_host_walk_is_depth_first_in_index_order_and_an_empty_subset_prunes():
+    counts, seen = [9, 2, 1], []
+
+    def visit(lvl, j, row, idx):
+        seen.append((lvl, j, int(row), idx.tolist()))
+        return idx[idx != 1] if (lvl, j) == (1, 0) else idx[:0] if (lvl, j) == (1, 1) else idx
+
+    geometry._tree_walk(counts, np.array([0, 1]), visit)
+    assert seen == ([(2, 0, 11, [0, 1]), (1, 0, 9, [0, 1])] + [(0, k, k, [0]) for k in range(8)] + [(1, 1, 10, [0, 1])])
+    for nothing in (([], np.array([0])), (counts, np.zeros(0, dtype=np.int64))):
+        geometry._tree_walk(*nothing, lambda *a: pytest.fail('nothing to walk'))
+
+
 def test_order_is_the_stable_morton_sort_with_unusable_faces_last():
     verts, faces = sphere()
     nan_vert = np.concatenate([verts, [[np.nan, 0, 0]]]).astype(F32)

@@ -1281,6 +1281,46 @@ int ia_lpips_layer_scratch_bytes(int N, int h, int w, size_t* h_bytes);
 int ia_lpips_layer(const float* f, const float* lin, int N, int C, int h, int w, void* scratch, size_t scratch_bytes, float* out,
                    int out_stride, void* stream);
 
+/*
+ * Identity similarity (csrc/identity.hip): what the ArcFace IR-SE50 score of encoder_inversion/criteria/id_loss.py (IDLoss) needs besides
+ * the residual units on ia_conv2d_mfma_sx / ia_conv2d_down_sx / ia_se_gate.  Additive entry points: the ABI version is unchanged.
+ *
+ * ia_face_crop_pool: images fp32 [N,3,H,W] (IA_IMAGE_F32_NCHW) or uint8 [N,H,W,3] (IA_IMAGE_U8_NHWC, read as v / 127.5 - 1), H, W >= 256
+ * -> y fp32 [N,3,112,112] = AdaptiveAvgPool2d(112)(AdaptiveAvgPool2d(256)(images)[:, :, 35:223, 32:220]); a 256 x 256 frame skips the
+ * first pool.  Windows are torch's, [floor(i In / Out), ceil((i + 1) In / Out)); each stage is the fp32 sum of its window in row-major
+ * order divided by the window's size.
+ *
+ * ia_prelu_channels: y = x < 0 ? x * slopes[c] : x on fp32 [B,C,P] (y may be x).
+ *
+ * ia_conv3x3_small: y[b,o] = prelu(out_scale[o] * sum_{i,ky,kx} wk[ky*3+kx][i][o] * pad0(in_scale[i] * x[b,i] + in_shift[i]) + out_shift[o])
+ * for h, w in 1..7, I % 8 == 0, O % 8 == 0: stride 1, and the zero padding is applied AFTER the input affine map (a BatchNorm in front
+ * of the convolution).  x [B,I,h,w], wk [9][I][O] (hipops.pack_conv_weight), y [B,O,h,w], all fp32; in_scale / in_shift [I] (both or
+ * neither), out_scale / out_shift / slopes [O] or NULL.  fp32 fused multiply-adds: blocks of 8 input channels (72 terms in the order
+ * i, ky, kx) summed on their own, four blocks per chunk of 32 channels, one workgroup per chunk; the chunks' sums are added in chunk
+ * order by a second launch (no floating-point atomics).  The split depends on I alone: an image's result is the same in any batch.
+ * scratch: ia_conv3x3_small_scratch_bytes(B, I, O, h, w) bytes.  B <= 65535.
+ *
+ * ia_id_head: out[b] = z / ||z||_2 with z[o] = (sum_k wt[o][k] * x[b][k] + bias[o]) * scale[o] + shift[o]; x [B,K], wt [O,K], bias / scale /
+ * shift [O] or NULL, out [B,O], fp32.  The BatchNorm2d in front of the reference's Linear is folded into wt and bias by the caller (no
+ * padding is involved), scale / shift are its BatchNorm1d.  K is cut into slices of 3136: a thread adds k = t, t + 256, ... of a slice in
+ * fp32, a workgroup's 256 sums go through an xor tree per wave and the waves in order, the slices are added in order; ||z|| is the
+ * fp32 root of the squares summed in double the same way.  A zero z gives NaN (0 / 0), as torch.div does.
+ * scratch: ia_id_head_scratch_bytes(B, K, O) bytes.
+ *
+ * ia_id_similarity: out[n * out_stride] = sum_d f[n][d] * f[N + n][d] over f [2N,D] fp32: fp32 products added in double, lane-strided over
+ * one wave and an xor tree.  Exchanging the halves of f gives the same bits; a pair's value does not depend on N.
+ */
+int ia_face_crop_pool(const void* images, int layout, float* y, int N, int H, int W, void* stream);
+int ia_prelu_channels(const float* x, const float* slopes, float* y, int B, int C, int64_t P, void* stream);
+int ia_conv3x3_small_scratch_bytes(int B, int I, int O, int h, int w, size_t* h_bytes);
+int ia_conv3x3_small(const float* x, const float* wk, const float* in_scale, const float* in_shift, const float* out_scale,
+                     const float* out_shift, const float* slopes, float* y, void* scratch, size_t scratch_bytes, int B, int I, int O,
+                     int h, int w, void* stream);
+int ia_id_head_scratch_bytes(int B, int K, int O, size_t* h_bytes);
+int ia_id_head(const float* x, const float* wt, const float* bias, const float* scale, const float* shift, float* out, void* scratch,
+               size_t scratch_bytes, int B, int K, int O, void* stream);
+int ia_id_similarity(const float* f, int N, int D, float* out, int out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,13 @@ _SIGNATURES = {
     'ia_maxpool2d': [c_void_p] * 3 + [c_int] * 7 + [c_void_p],
     'ia_lpips_layer_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     'ia_lpips_layer': [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, ctypes.c_size_t, c_void_p, c_int, c_void_p],
+    'ia_face_crop_pool': [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    'ia_prelu_channels': [c_void_p] * 3 + [c_int, c_int, c_int64, c_void_p],
+    'ia_conv3x3_small_scratch_bytes': [c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_conv3x3_small': [c_void_p] * 9 + [ctypes.c_size_t] + [c_int] * 5 + [c_void_p],
+    'ia_id_head_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    'ia_id_head': [c_void_p] * 7 + [ctypes.c_size_t] + [c_int] * 3 + [c_void_p],
+    'ia_id_similarity': [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
 }
 
 

@@ -2455,3 +2455,93 @@ def lpips_layer(f, lin, out=None):
                                         _lib.stream_ptr(f.device))
     _lib.check(st, 'ia_lpips_layer')
     return out
+
+
+# ------------------------------------------------------------------ identity similarity (csrc/identity.hip)
+
+def face_crop_pool(images):
+    """ia_face_crop_pool: float32 [N,3,H,W] or uint8 [N,H,W,3] (H, W >= 256) -> float32 [N,3,112,112], the reference's crop + pool."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.is_contiguous() and images.dim() == 4
+            and images.dtype in (torch.float32, torch.uint8)):
+        raise RuntimeError('face_crop_pool: a contiguous float32 [N,3,H,W] or uint8 [N,H,W,3] device tensor')
+    u8 = images.dtype == torch.uint8
+    n, c, h, w = (images.shape[0], images.shape[3], images.shape[1], images.shape[2]) if u8 else images.shape
+    if c != 3 or n < 1 or h < 256 or w < 256:
+        raise RuntimeError(f'face_crop_pool: 3 channels and sides >= 256, got {tuple(images.shape)}')
+    y = torch.empty(n, 3, 112, 112, device=images.device, dtype=torch.float32)
+    with torch.cuda.device(images.device), _Timed('face_crop_pool', 0.0, float(images.numel() * images.element_size() + 4 * y.numel()), f'N{n} {h}x{w}'):
+        st = _lib.load().ia_face_crop_pool(_p(images), 1 if u8 else 0, _p(y), n, h, w, _lib.stream_ptr(images.device))
+    _lib.check(st, 'ia_face_crop_pool')
+    return y
+
+
+def prelu_channels(x, slopes, inplace=False):
+    """ia_prelu_channels: per-channel PReLU of fp32 [B,C,...]."""
+    _f32c(x, 'x'), _f32c(slopes, 'slopes')
+    if x.dim() < 2 or slopes.numel() != x.shape[1] or slopes.device != x.device or x.numel() == 0:
+        raise RuntimeError(f'prelu_channels: x [B,C,...] and slopes [C] on one device, got {tuple(x.shape)} and {tuple(slopes.shape)}')
+    y = x if inplace else torch.empty_like(x)
+    b, c = x.shape[0], x.shape[1]
+    with torch.cuda.device(x.device), _Timed('prelu_channels', float(x.numel()), 8.0 * x.numel(), f'B{b} C{c}'):
+        st = _lib.load().ia_prelu_channels(_p(x), _p(slopes), _p(y), b, c, x.numel() // (b * c), _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_prelu_channels')
+    return y
+
+
+def conv3x3_small(x, wk, in_scale=None, in_shift=None, out_scale=None, out_shift=None, slopes=None):
+    """ia_conv3x3_small: 3x3 stride-1 padding-1 convolution of fp32 [B,I,h,w] with h, w < 8; wk = pack_conv_weight(w) [9,I,O].  in_scale /
+    in_shift [I]: an affine map per input channel applied before the zero padding; out_scale / out_shift / slopes [O]: the epilogue."""
+    _f32c(x, 'x'), _f32c(wk, 'wk')
+    if x.dim() != 4 or wk.dim() != 3 or wk.shape[0] != 9 or wk.shape[1] != x.shape[1] or wk.device != x.device:
+        raise RuntimeError(f'conv3x3_small: x [B,I,h,w] and wk [9,I,O] on one device, got {tuple(x.shape)} and {tuple(wk.shape)}')
+    b, i, h, w = x.shape
+    o = wk.shape[2]
+    if (in_scale is None) != (in_shift is None):
+        raise RuntimeError('conv3x3_small: in_scale and in_shift come together')
+    for name, t, n in (('in_scale', in_scale, i), ('in_shift', in_shift, i), ('out_scale', out_scale, o), ('out_shift', out_shift, o),
+                       ('slopes', slopes, o)):
+        if t is not None and (_f32c(t, name).numel() != n or t.device != x.device):
+            raise RuntimeError(f'conv3x3_small: {name} has {t.numel()} elements, expected {n}')
+    scratch, nbytes = _scratch('ia_conv3x3_small_scratch_bytes', b, i, o, h, w, dtype=torch.float32, device=x.device)
+    y = torch.empty(b, o, h, w, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device), _Timed('conv3x3_small', 18.0 * b * h * w * i * o, 4.0 * (x.numel() + wk.numel() + y.numel()), f'B{b} I{i} O{o} {h}x{w}'):
+        st = _lib.load().ia_conv3x3_small(_p(x), _p(wk), _p(in_scale), _p(in_shift), _p(out_scale), _p(out_shift), _p(slopes), _p(y), _p(scratch),
+                                          nbytes, b, i, o, h, w, _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_conv3x3_small')
+    return y
+
+
+def id_head(x, wt, bias=None, scale=None, shift=None):
+    """ia_id_head: x fp32 [B,K] (or [B,C,h,w], flattened), wt [O,K] -> float32 [B,O], ((wt x + bias) * scale + shift) l2-normalised."""
+    _f32c(x, 'x'), _f32c(wt, 'wt')
+    x2 = x.reshape(x.shape[0], -1)
+    if wt.dim() != 2 or wt.shape[1] != x2.shape[1] or wt.device != x.device or x2.shape[0] < 1:
+        raise RuntimeError(f'id_head: x [B,K] and wt [O,K] on one device, got {tuple(x.shape)} and {tuple(wt.shape)}')
+    b, k = x2.shape
+    o = wt.shape[0]
+    for name, t in (('bias', bias), ('scale', scale), ('shift', shift)):
+        if t is not None and (_f32c(t, name).numel() != o or t.device != x.device):
+            raise RuntimeError(f'id_head: {name} has {t.numel()} elements, expected {o}')
+    scratch, nbytes = _scratch('ia_id_head_scratch_bytes', b, k, o, dtype=torch.float32, device=x.device)
+    out = torch.empty(b, o, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device), _Timed('id_head', 2.0 * b * k * o, 4.0 * (x.numel() + wt.numel() + out.numel()), f'B{b} K{k} O{o}'):
+        st = _lib.load().ia_id_head(_p(x2), _p(wt), _p(bias), _p(scale), _p(shift), _p(out), _p(scratch), nbytes, b, k, o, _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_id_head')
+    return out
+
+
+def id_similarity(f, out=None):
+    """ia_id_similarity: f fp32 [2N,D] -> float32 [N], rows n and N + n dotted; `out`: a float32 [N] view (any positive stride) to write into."""
+    _f32c(f, 'f')
+    if f.dim() != 2 or f.shape[0] % 2 or f.shape[0] < 2 or f.shape[1] < 1:
+        raise RuntimeError(f'id_similarity: f must be [2N,D], got {tuple(f.shape)}')
+    n, d = f.shape[0] // 2, f.shape[1]
+    if out is None:
+        out = torch.empty(n, device=f.device, dtype=torch.float32)
+    if not (out.is_cuda and out.device == f.device and out.dtype == torch.float32 and out.dim() == 1 and out.shape[0] == n
+            and (n == 1 or out.stride(0) >= 1)):
+        raise RuntimeError('id_similarity: out must be a float32 [N] device view with a positive stride')
+    with torch.cuda.device(f.device), _Timed('id_similarity', 2.0 * f.numel(), 4.0 * f.numel(), f'N{n} D{d}'):
+        st = _lib.load().ia_id_similarity(_p(f), n, d, _p(out), max(int(out.stride(0)), 1), _lib.stream_ptr(f.device))
+    _lib.check(st, 'ia_id_similarity')
+    return out

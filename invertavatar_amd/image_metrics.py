@@ -12,7 +12,9 @@ or uint8 ``[N,H,W,C]`` (what the output side holds; ``data_range`` defaults to 2
 
 CLI:  python -m invertavatar_amd.image_metrics --pred P --gt G [--data-range R] [--levels K] [--chunk N] --out metrics.json
 where P / G are ``.npy`` stacks or directories of them (sorted order).  ``--lpips alex|vgg --lpips-weights FILE --lpips-lin FILE`` adds
-LPIPS (``invertavatar_amd/lpips.py``) per frame; ``--lpips-synthetic SEED`` takes seeded weights instead (smoke runs: meaningless scores)."""
+LPIPS (``invertavatar_amd/lpips.py``) per frame; ``--lpips-synthetic SEED`` takes seeded weights instead (smoke runs: meaningless scores).
+``--id-weights FILE`` (the ArcFace IR-SE50 state dict) adds the identity similarity ``id_sim`` (``invertavatar_amd/identity.py``) per
+frame; ``--id-synthetic SEED`` takes seeded weights instead."""
 import json
 import math
 import os
@@ -142,8 +144,9 @@ class ClipMetrics:
     """Scores of a clip, gathered call by call: ``update`` keeps each call's per-frame results where they were computed (no host
     synchronisation); ``summary`` makes the clip's one device -> host read."""
 
-    def __init__(self, data_range=2.0, levels=MAX_LEVELS, lpips=None):
+    def __init__(self, data_range=2.0, levels=MAX_LEVELS, lpips=None, identity=None):
         self.data_range, self.levels, self.lpips = data_range, levels, lpips      # lpips: an lpips.LPIPS model, or None
+        self.identity = identity                                                  # an identity.IDScore model, or None
         self._calls = []
 
     def update(self, pred, gt):
@@ -151,6 +154,9 @@ class ClipMetrics:
         if self.lpips is not None:
             from . import lpips as _lpips
             res.update(_lpips.compare(pred, gt, self.lpips, self.data_range))
+        if self.identity is not None:
+            from . import identity as _identity
+            res.update(_identity.compare(pred, gt, self.identity, self.data_range))
         self._calls.append(res)
         return res
 
@@ -206,8 +212,9 @@ def _frames(files):
         yield arr[None] if arr.ndim == 3 else arr
 
 
-def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None, lpips=None):
-    """Scores two ``.npy`` stacks (or directories of them) chunk by chunk -> ClipMetrics (with LPIPS when `lpips` is a model)."""
+def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None, lpips=None, identity=None):
+    """Scores two ``.npy`` stacks (or directories of them) chunk by chunk -> ClipMetrics (with LPIPS when `lpips` is a model, with the
+    identity similarity when `identity` is one)."""
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
     p_files, g_files = _stack_files(pred), _stack_files(gt)
     if len(p_files) != len(g_files):
@@ -220,7 +227,7 @@ def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=N
             a = torch.from_numpy(np.array(pa[lo:lo + chunk])).to(device)
             b = torch.from_numpy(np.array(ga[lo:lo + chunk])).to(device)
             if clip is None:
-                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels, lpips)
+                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels, lpips, identity)
             clip.update(a, b)
     return clip
 
@@ -239,6 +246,8 @@ def main(argv=None):
     ap.add_argument('--lpips-weights', default=None, help="the backbone's torchvision state dict (alexnet / vgg16)")
     ap.add_argument('--lpips-lin', default=None, help='the LPIPS v0.1 linear layers of the backbone')
     ap.add_argument('--lpips-synthetic', type=int, default=None, metavar='SEED', help='seeded weights instead of files (smoke runs only)')
+    ap.add_argument('--id-weights', default=None, help='also score identity similarity: the ArcFace IR-SE50 state dict (model_ir_se50.pth)')
+    ap.add_argument('--id-synthetic', type=int, default=None, metavar='SEED', help='seeded identity weights instead of a file (smoke runs only)')
     args = ap.parse_args(argv)
     model = None
     if args.lpips is not None:
@@ -252,7 +261,17 @@ def main(argv=None):
             ap.error('--lpips needs --lpips-weights and --lpips-lin (or --lpips-synthetic SEED)')
     elif args.lpips_weights or args.lpips_lin or args.lpips_synthetic is not None:
         ap.error('--lpips-weights / --lpips-lin / --lpips-synthetic need --lpips alex|vgg')
-    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device, model).write_json(args.out)
+    id_model = None
+    if args.id_weights is not None and args.id_synthetic is not None:
+        ap.error('--id-weights and --id-synthetic exclude each other')
+    if args.id_synthetic is not None:
+        from . import identity as _identity
+        print(f'warning: identity similarity with synthetic weights (seed {args.id_synthetic}): the id_sim numbers mean nothing', file=sys.stderr)
+        id_model = _identity.IDScore.synthetic(args.id_synthetic)
+    elif args.id_weights is not None:
+        from . import identity as _identity
+        id_model = _identity.IDScore(args.id_weights)
+    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device, model, id_model).write_json(args.out)
     print(json.dumps({'frames': res['frames'], 'mean': res['mean']}))
     return 0
 

@@ -1321,6 +1321,46 @@ int ia_id_head(const float* x, const float* wt, const float* bias, const float* 
                size_t scratch_bytes, int B, int K, int O, void* stream);
 int ia_id_similarity(const float* f, int N, int D, float* out, int out_stride, void* stream);
 
+/*
+ * Contextual loss (csrc/contextual.hip): what the CX score of encoder_inversion/criteria/cx_loss.py (CXLoss, contextual_loss with the
+ * cosine distance) needs besides the VGG19 trunk on ia_conv2d_direct / ia_maxpool2d / ia_conv2d_mfma_sx.  Additive entry points: the
+ * ABI version is unchanged.
+ *
+ * ia_resize_bilinear: F.interpolate(mode='bilinear', align_corners=False), no antialiasing, any sizes.  src fp32 [N,C,H,W]
+ * (IA_IMAGE_F32_NCHW) or uint8 [N,H,W,C] (IA_IMAGE_U8_NHWC, read as v / 127.5 - 1) -> dst fp32 [N,C,OH,OW].  Per axis the source
+ * coordinate is s = max(0, (In / Out)(o + 0.5) - 0.5) in double, the taps floor(s) and min(floor(s) + 1, In - 1), the weights
+ * w1 = fp32(s - floor(s)), w0 = 1 - w1; dst = wy0 (wx0 v00 + wx1 v01) + wy1 (wx0 v10 + wx1 v11) in fp32.  H == 2 OH and W == 2 OW take a
+ * branch with the constant taps (2 o, 2 o + 1) and weights 0.5 -- the 2 x 2 mean, the same bits; general != 0 forces the general path.
+ *
+ * The head, for N pairs of maps fx, fy fp32 [N,C,P] (P = h w positions) and a table mu of per-channel shifts:
+ *     x^_i = (fx_i - mu) / max(||fx_i - mu||_2, 1e-12),  y^_j likewise;   d_ij = 1 - x^_i . y^_j;   m_i = min_j d_ij;
+ *     w_ij = exp((1 - clamp(d_ij / (m_i + 1e-5), -10, 10)) / band_width);   s_i = sum_j w_ij;
+ *     colmax_j = max_i w_ij / s_i;   cx = (sum_j colmax_j) / P;   cx_loss = -log(cx + 1e-5).
+ * ia_cx_layout: tile = rows / columns per workgroup of ia_cx_rows / ia_cx_cols, k_step = the multiple the channel count is padded to.
+ * ia_cx_scratch_bytes(N, C, P): bytes for the double [N,C] means, float [N,P] m, double [N,P] s and double [N,P] colmax -- O(N (C + P));
+ * the P x P matrix is never stored.  The operands x^, y^ (fp32 [N,P,Cpad] each) are the caller's.
+ * ia_cx_channel_mean: mean64[n,c] = (sum_p f[n,c,p]) / P in double (a workgroup per map: lane-strided partials, xor tree per wave, waves
+ * in order), mu_frames [N,C] = fp32 of it; mu_batch [C] or NULL = fp32((sum_n mean64[n,c]) / N), frames in order.  No atomics.
+ * ia_cx_normalize: f [N,C,P], mu [mu_rows,C] with mu_rows = 1 (one row for the batch) or N -> out [N,P,Cpad], Cpad % k_step == 0, zeros
+ * from channel C on.  The difference is fp32, the squared norm is added in double in channel order, the norm rounded to fp32 and the
+ * quotient fp32; a NaN norm stays NaN.
+ * ia_cx_rows: m [N,P] and s [N,P].  ia_cx_cols: colmax [N,P] from the same operands and that m, s.  Both form the dot products with
+ * v_mfma_f32_16x16x4_f32 (x^ as A, y^ as B), 16 channels per fp32 accumulator, the accumulators added in double in channel order, and
+ * d = fp32(1 - dot): the same bits of d in both.  t, w and the sums are double.  s_i adds a lane's columns in order and 16 lanes by the
+ * xor tree; minima and maxima propagate NaN.  Cpad <= 624 (a 64-row block in LDS), else IA_ERR_UNSUPPORTED; N <= 65535.
+ * ia_cx_finish: cx [N] = fp32((sum_j colmax_j) / P) (one wave per frame: lane-strided double partials, xor tree), cx_loss [N] =
+ * fp32(-log of the double + 1e-5).  A frame's results depend on its two maps and its mu row alone: the same bits in any batch and run.
+ */
+int ia_resize_bilinear(const void* src, int layout, float* dst, int N, int C, int H, int W, int OH, int OW, int general, void* stream);
+int ia_cx_layout(int* tile, int* k_step);
+int ia_cx_scratch_bytes(int N, int C, int64_t P, size_t* h_bytes);
+int ia_cx_channel_mean(const float* f, int N, int C, int64_t P, double* mean64, float* mu_frames, float* mu_batch, void* stream);
+int ia_cx_normalize(const float* f, const float* mu, int mu_rows, float* out, int N, int C, int64_t P, int cpad, void* stream);
+int ia_cx_rows(const float* xh, const float* yh, int N, int64_t P, int cpad, float band_width, float* m, double* s, void* stream);
+int ia_cx_cols(const float* xh, const float* yh, const float* m, const double* s, int N, int64_t P, int cpad, float band_width,
+               double* colmax, void* stream);
+int ia_cx_finish(const double* colmax, int N, int64_t P, float* cx, float* cx_loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

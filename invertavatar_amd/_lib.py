@@ -192,6 +192,14 @@ _SIGNATURES = {
     'ia_id_head_scratch_bytes': [c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     'ia_id_head': [c_void_p] * 7 + [ctypes.c_size_t] + [c_int] * 3 + [c_void_p],
     'ia_id_similarity': [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
+    'ia_resize_bilinear': [c_void_p, c_int, c_void_p] + [c_int] * 7 + [c_void_p],
+    'ia_cx_layout': [ctypes.POINTER(c_int)] * 2,
+    'ia_cx_scratch_bytes': [c_int, c_int, c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_cx_channel_mean': [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_cx_normalize': [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p],
+    'ia_cx_rows': [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p],
+    'ia_cx_cols': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p],
+    'ia_cx_finish': [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p],
 }
 
 

@@ -2545,3 +2545,90 @@ def id_similarity(f, out=None):
         st = _lib.load().ia_id_similarity(_p(f), n, d, _p(out), max(int(out.stride(0)), 1), _lib.stream_ptr(f.device))
     _lib.check(st, 'ia_id_similarity')
     return out
+
+
+# ------------------------------------------------------------------ contextual loss (csrc/contextual.hip)
+
+def resize_bilinear(images, size, general=False):
+    """ia_resize_bilinear: float32 [N,C,H,W] or uint8 [N,H,W,C] (read as v / 127.5 - 1) -> float32 [N,C,OH,OW], what
+    F.interpolate(mode='bilinear', align_corners=False) gives.  `general`: take the general path where the exact 2 : 1 branch applies."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.is_contiguous() and images.dim() == 4
+            and images.dtype in (torch.float32, torch.uint8)):
+        raise RuntimeError('resize_bilinear: a contiguous float32 [N,C,H,W] or uint8 [N,H,W,C] device tensor')
+    u8 = images.dtype == torch.uint8
+    n, c, h, w = (images.shape[0], images.shape[3], images.shape[1], images.shape[2]) if u8 else images.shape
+    oh, ow = int(size[0]), int(size[1])
+    if min(n, c, h, w, oh, ow) < 1:
+        raise RuntimeError(f'resize_bilinear: empty input or output ({tuple(images.shape)} -> {oh} x {ow})')
+    y = torch.empty(n, c, oh, ow, device=images.device, dtype=torch.float32)
+    with torch.cuda.device(images.device), _Timed('resize_bilinear', 7.0 * y.numel(), float(images.numel() * images.element_size() + 4 * y.numel()),
+                                                  f'N{n} C{c} {h}x{w}->{oh}x{ow}'):
+        st = _lib.load().ia_resize_bilinear(_p(images), 1 if u8 else 0, _p(y), n, c, h, w, oh, ow, int(bool(general)), _lib.stream_ptr(images.device))
+    _lib.check(st, 'ia_resize_bilinear')
+    return y
+
+
+def cx_layout():
+    """(tile, k_step) of the contextual head: rows / columns per workgroup, and the multiple the channel count is padded to."""
+    tile, step = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().ia_cx_layout(ctypes.byref(tile), ctypes.byref(step)), 'ia_cx_layout')
+    return tile.value, step.value
+
+
+def cx_scratch_bytes(n, c, p):
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(_lib.load().ia_cx_scratch_bytes(int(n), int(c), int(p), ctypes.byref(nbytes)), 'ia_cx_scratch_bytes')
+    return nbytes.value
+
+
+def cx_head(fx, fy, band_width=0.5, mu='frame', debug=False):
+    """The contextual head on fp32 maps fx, fy [N,C,h,w] -> (cx [N], cx_loss [N]) float32: ia_cx_channel_mean, ia_cx_normalize (twice),
+    ia_cx_rows, ia_cx_cols, ia_cx_finish.  mu: 'frame' (a frame's own channel means of fy), 'batch' (the batch's), or a float32 [1,C] /
+    [N,C] table.  debug: also a dict with mu, the operands xh / yh [N,P,Cpad], m [N,P] float32, s and colmax [N,P] float64."""
+    _f32c(fx, 'fx'), _f32c(fy, 'fy')
+    if fx.dim() != 4 or fx.shape != fy.shape or fx.device != fy.device or fx.numel() == 0:
+        raise RuntimeError(f'cx_head: two float32 [N,C,h,w] maps of one shape on one device, got {tuple(fx.shape)} and {tuple(fy.shape)}')
+    n, c, h, w = fx.shape
+    p = h * w
+    _, step = cx_layout()
+    cpad = -(-c // step) * step
+    dev = fx.device
+    lib, stream = _lib.load(), _lib.stream_ptr(dev)
+    scratch = torch.empty(-(-cx_scratch_bytes(n, c, p) // 8), dtype=torch.float64, device=dev)
+    mean64, s, colmax = scratch[:n * c], scratch[n * c:n * c + n * p], scratch[n * c + n * p:n * c + 2 * n * p]
+    m = scratch[n * c + 2 * n * p:].view(torch.float32)[:n * p]
+    xh = torch.empty(n, p, cpad, device=dev, dtype=torch.float32)
+    yh = torch.empty(n, p, cpad, device=dev, dtype=torch.float32)
+    cx = torch.empty(n, device=dev, dtype=torch.float32)
+    loss = torch.empty(n, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        if torch.is_tensor(mu):
+            table = _f32c(mu, 'mu')
+            if table.dim() != 2 or table.shape[1] != c or table.shape[0] not in (1, n) or table.device != dev:
+                raise RuntimeError(f'cx_head: mu must be float32 [1,C] or [N,C] on the maps\' device, got {tuple(table.shape)}')
+        elif mu in ('frame', 'batch'):
+            frames = torch.empty(n, c, device=dev, dtype=torch.float32)
+            batch = torch.empty(1, c, device=dev, dtype=torch.float32) if mu == 'batch' else None
+            with _Timed('cx_channel_mean', float(fy.numel()), 4.0 * fy.numel(), f'N{n} C{c} P{p}'):
+                st = lib.ia_cx_channel_mean(_p(fy), n, c, p, _p(mean64), _p(frames), _p(batch), stream)
+            _lib.check(st, 'ia_cx_channel_mean')
+            table = batch if mu == 'batch' else frames
+        else:
+            raise RuntimeError(f"cx_head: mu must be 'frame', 'batch' or a table, got {mu!r}")
+        for src, dst in ((fx, xh), (fy, yh)):
+            with _Timed('cx_normalize', 4.0 * src.numel(), 12.0 * src.numel(), f'N{n} C{c} P{p}'):
+                st = lib.ia_cx_normalize(_p(src), _p(table), table.shape[0], _p(dst), n, c, p, cpad, stream)
+            _lib.check(st, 'ia_cx_normalize')
+        with _Timed('cx_rows', 4.0 * n * p * p * cpad, 8.0 * n * p * cpad, f'N{n} C{c} P{p}'):
+            st = lib.ia_cx_rows(_p(xh), _p(yh), n, p, cpad, float(band_width), _p(m), _p(s), stream)
+        _lib.check(st, 'ia_cx_rows')
+        with _Timed('cx_cols', 2.0 * n * p * p * cpad, 8.0 * n * p * cpad, f'N{n} C{c} P{p}'):
+            st = lib.ia_cx_cols(_p(xh), _p(yh), _p(m), _p(s), n, p, cpad, float(band_width), _p(colmax), stream)
+        _lib.check(st, 'ia_cx_cols')
+        with _Timed('cx_finish', float(n * p), 8.0 * n * p, f'N{n} P{p}'):
+            st = lib.ia_cx_finish(_p(colmax), n, p, _p(cx), _p(loss), stream)
+        _lib.check(st, 'ia_cx_finish')
+    if debug:
+        return cx, loss, {'mu': table, 'xh': xh, 'yh': yh, 'm': m.reshape(n, p).clone(), 's': s.reshape(n, p).clone(),
+                          'colmax': colmax.reshape(n, p).clone()}
+    return cx, loss

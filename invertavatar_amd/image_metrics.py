@@ -14,7 +14,9 @@ CLI:  python -m invertavatar_amd.image_metrics --pred P --gt G [--data-range R] 
 where P / G are ``.npy`` stacks or directories of them (sorted order).  ``--lpips alex|vgg --lpips-weights FILE --lpips-lin FILE`` adds
 LPIPS (``invertavatar_amd/lpips.py``) per frame; ``--lpips-synthetic SEED`` takes seeded weights instead (smoke runs: meaningless scores).
 ``--id-weights FILE`` (the ArcFace IR-SE50 state dict) adds the identity similarity ``id_sim`` (``invertavatar_amd/identity.py``) per
-frame; ``--id-synthetic SEED`` takes seeded weights instead."""
+frame; ``--id-synthetic SEED`` takes seeded weights instead.  ``--cx-weights FILE`` (a torchvision ``vgg19`` state dict) adds the contextual
+score ``cx`` / ``cx_loss`` (``invertavatar_amd/contextual.py``) per frame; ``--cx-synthetic SEED`` takes seeded weights instead and
+``--cx-band-width H`` sets the band width (0.5)."""
 import json
 import math
 import os
@@ -144,9 +146,10 @@ class ClipMetrics:
     """Scores of a clip, gathered call by call: ``update`` keeps each call's per-frame results where they were computed (no host
     synchronisation); ``summary`` makes the clip's one device -> host read."""
 
-    def __init__(self, data_range=2.0, levels=MAX_LEVELS, lpips=None, identity=None):
+    def __init__(self, data_range=2.0, levels=MAX_LEVELS, lpips=None, identity=None, contextual=None):
         self.data_range, self.levels, self.lpips = data_range, levels, lpips      # lpips: an lpips.LPIPS model, or None
         self.identity = identity                                                  # an identity.IDScore model, or None
+        self.contextual = contextual                                              # a contextual.CXScore model, or None
         self._calls = []
 
     def update(self, pred, gt):
@@ -157,6 +160,9 @@ class ClipMetrics:
         if self.identity is not None:
             from . import identity as _identity
             res.update(_identity.compare(pred, gt, self.identity, self.data_range))
+        if self.contextual is not None:
+            from . import contextual as _contextual
+            res.update(_contextual.compare(pred, gt, self.contextual, self.data_range))
         self._calls.append(res)
         return res
 
@@ -212,9 +218,9 @@ def _frames(files):
         yield arr[None] if arr.ndim == 3 else arr
 
 
-def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None, lpips=None, identity=None):
+def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=None, lpips=None, identity=None, contextual=None):
     """Scores two ``.npy`` stacks (or directories of them) chunk by chunk -> ClipMetrics (with LPIPS when `lpips` is a model, with the
-    identity similarity when `identity` is one)."""
+    identity similarity when `identity` is one, with the contextual score when `contextual` is one)."""
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')
     p_files, g_files = _stack_files(pred), _stack_files(gt)
     if len(p_files) != len(g_files):
@@ -227,7 +233,7 @@ def score_files(pred, gt, data_range=None, levels=MAX_LEVELS, chunk=16, device=N
             a = torch.from_numpy(np.array(pa[lo:lo + chunk])).to(device)
             b = torch.from_numpy(np.array(ga[lo:lo + chunk])).to(device)
             if clip is None:
-                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels, lpips, identity)
+                clip = ClipMetrics(data_range if data_range is not None else (255.0 if a.dtype == torch.uint8 else 2.0), levels, lpips, identity, contextual)
             clip.update(a, b)
     return clip
 
@@ -248,6 +254,9 @@ def main(argv=None):
     ap.add_argument('--lpips-synthetic', type=int, default=None, metavar='SEED', help='seeded weights instead of files (smoke runs only)')
     ap.add_argument('--id-weights', default=None, help='also score identity similarity: the ArcFace IR-SE50 state dict (model_ir_se50.pth)')
     ap.add_argument('--id-synthetic', type=int, default=None, metavar='SEED', help='seeded identity weights instead of a file (smoke runs only)')
+    ap.add_argument('--cx-weights', default=None, help='also score the contextual loss: a torchvision vgg19 state dict')
+    ap.add_argument('--cx-synthetic', type=int, default=None, metavar='SEED', help='seeded VGG19 weights instead of a file (smoke runs only)')
+    ap.add_argument('--cx-band-width', type=float, default=None, metavar='H', help='band width of the contextual loss (default 0.5)')
     args = ap.parse_args(argv)
     model = None
     if args.lpips is not None:
@@ -271,7 +280,19 @@ def main(argv=None):
     elif args.id_weights is not None:
         from . import identity as _identity
         id_model = _identity.IDScore(args.id_weights)
-    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device, model, id_model).write_json(args.out)
+    cx_model = None
+    if args.cx_weights is not None and args.cx_synthetic is not None:
+        ap.error('--cx-weights and --cx-synthetic exclude each other')
+    if args.cx_band_width is not None and args.cx_weights is None and args.cx_synthetic is None:
+        ap.error('--cx-band-width needs --cx-weights FILE or --cx-synthetic SEED')
+    if args.cx_synthetic is not None:
+        from . import contextual as _contextual
+        print(f'warning: contextual loss with synthetic weights (seed {args.cx_synthetic}): the cx numbers mean nothing', file=sys.stderr)
+        cx_model = _contextual.CXScore.synthetic(args.cx_synthetic, 0.5 if args.cx_band_width is None else args.cx_band_width)
+    elif args.cx_weights is not None:
+        from . import contextual as _contextual
+        cx_model = _contextual.CXScore(args.cx_weights, 0.5 if args.cx_band_width is None else args.cx_band_width)
+    res = score_files(args.pred, args.gt, args.data_range, args.levels, args.chunk, args.device, model, id_model, cx_model).write_json(args.out)
     print(json.dumps({'frames': res['frames'], 'mean': res['mean']}))
     return 0
 

@@ -254,27 +254,28 @@ def _route(op, h, w):
     return 'mfma' if (k == 3 and s == 1 and p == 1 and hipops.conv_sx_supported(cin, cout, h, w, 3, False)) else 'direct'
 
 
-@torch.no_grad()
-def device_table(x, y, model):
-    """The layer values through the HIP kernels -> float32 [N,5] on the inputs' device."""
-    from . import hipops
-    held = model.on(x.device)
-    n = x.shape[0]
-    v, vs = _batch(x, y, torch.float32), None              # the activation as fp32 and / or as a SplitAct
-    h, w = v.shape[2], v.shape[3]
-    # route of every convolution at the size it runs at
-    routes, hh, ww = [], h, w
-    for op in model.plan:
+def plan_routes(plan, h, w):
+    """The route of every convolution of `plan` at the size it runs at for an h x w input (None at the pools)."""
+    routes = []
+    for op in plan:
         if op[0] == 'conv':
-            routes.append(_route(op, hh, ww))
-            hh, ww = (hh + 2 * op[6] - op[4]) // op[5] + 1, (ww + 2 * op[6] - op[4]) // op[5] + 1
+            routes.append(_route(op, h, w))
+            h, w = (h + 2 * op[6] - op[4]) // op[5] + 1, (w + 2 * op[6] - op[4]) // op[5] + 1
         else:
             routes.append(None)
-            hh, ww = (hh - op[1]) // op[2] + 1, (ww - op[1]) // op[2] + 1
-    table = torch.empty(n, 5, device=x.device, dtype=torch.float32)
+            h, w = (h - op[1]) // op[2] + 1, (w - op[1]) // op[2] + 1
+    return routes
+
+
+def run_plan(v, plan, held, on_tap=None):
+    """Runs the feature stack `plan` on the fp32 batch `v` through the HIP kernels; held: a model's ``on(device)`` dict ('w', 'b',
+    'split').  ``on_tap(map, index)`` is called with every tapped map (fp32).  Returns the last layer's fp32 output."""
+    from . import hipops
+    vs = None                                              # the activation as fp32 (v) and / or as a SplitAct (vs)
+    routes = plan_routes(plan, v.shape[2], v.shape[3])
     i = taps = 0
-    for j, op in enumerate(model.plan):
-        nxt = model.plan[j + 1] if j + 1 < len(model.plan) else None
+    for j, op in enumerate(plan):
+        nxt = plan[j + 1] if j + 1 < len(plan) else None
         nxt_conv = next((r for r in routes[j + 1:] if r is not None), None)     # route of the next convolution
         if op[0] == 'pool':
             out = hipops.maxpool2d(v, op[1], op[2], want_f32=nxt_conv != 'mfma', want_split=nxt_conv == 'mfma')
@@ -295,9 +296,19 @@ def device_table(x, y, model):
             v = hipops.conv2d_direct(v, held['w'][i], held['b'][i], stride=op[5], padding=op[6], relu=True)
             vs = hipops.act_split(v) if need_split else None
         i += 1
-        if tap:
-            hipops.lpips_layer(v, held['lin'][taps], out=table[:, taps])
+        if tap and on_tap is not None:
+            on_tap(v, taps)
             taps += 1
+    return v
+
+
+@torch.no_grad()
+def device_table(x, y, model):
+    """The layer values through the HIP kernels -> float32 [N,5] on the inputs' device."""
+    from . import hipops
+    held = model.on(x.device)
+    table = torch.empty(x.shape[0], 5, device=x.device, dtype=torch.float32)
+    run_plan(_batch(x, y, torch.float32), model.plan, held, lambda f, t: hipops.lpips_layer(f, held['lin'][t], out=table[:, t]))
     return table
 
 

@@ -19,9 +19,17 @@
 // write the three planes channels-last [B,3,256,256,32].
 #include "ia_common.h"
 
-// Compile-time ablations (tools/, never in the product build): bit 0 = no static-crop loads, bit 1 = no texture walk
+// Compile-time ablations (tools/, never in the product build): bit 0 = no static-crop loads, bit 1 = no texture walk,
+// bit 2 = no stores of the blended channels
 #ifndef IA_RAST_ABLATE
 #define IA_RAST_ABLATE 0
+#endif
+// Rows of a workgroup's tile on the 64^2 and the 128^2 level (the tile is 16 pixels wide; 16 x rows must be a multiple of 16 pixels)
+#ifndef IA_RAST_TY64
+#define IA_RAST_TY64 1
+#endif
+#ifndef IA_RAST_TY128
+#define IA_RAST_TY128 1
 #endif
 
 namespace {
@@ -323,6 +331,7 @@ __global__ __launch_bounds__(256) void rasterize_level_kernel(RastParams p) {
                 }
             }
             float* dst = outb + (int64_t)(c + j) * rr;
+            if ((IA_RAST_ABLATE & 4) && p.res > 0) continue;               // (the run-time half keeps the arithmetic alive)
             if (vec_ok) *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
             else for (int k = 0; k < PXB && xt + k < res; ++k) dst[k] = o[k];
         }
@@ -394,6 +403,369 @@ __global__ __launch_bounds__(256) void rasterize_level_kernel(RastParams p) {
     if (tid < PXB && xt + tid < res) outb[(int64_t)p.C * rr + tid] = s_u[tid];
 }
 
+// ---- the 64^2 and 128^2 levels: a workgroup of 4 waves owns a tile of TX x TY output pixels, made of the 4-pixel groups above.
+// The footprint of the whole tile is staged once.  Then, a round at a time, every wave takes one group through the chain of the
+// kernel above on its own (bounding box -> windows -> ordered compaction -> walk; wave-level synchronisation only, its own window
+// accumulators and list), so four chains are in flight per workgroup and none of them stops the others; the arithmetic of a group
+// is that of the kernel above with an unsplit walk.  The finished sums of the round's four groups change hands through LDS, and
+// the threads finish them as (channel, group): four neighbouring lanes read the static crop of one channel row and write
+// 4 x 16 contiguous bytes of it (a 64-byte run when the round's groups are neighbours in x).
+constexpr int kWaves = 4;                            // waves of a tile workgroup = groups of a round
+constexpr int kXPad = 65;                            // row pitch (float4) of the exchange buffer: 64 channel groups + 1
+static_assert(kList / 2 >= 2 * kWinN, "the merged list must fit a wave's list");
+
+__device__ __forceinline__ void wave_sync() {        // LDS written by one lane of a wave, read by another
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int S, int TX, int TY>
+__global__ __launch_bounds__(256) void rasterize_tile_kernel(RastParams p) {
+    constexpr int GX = TX / PXB, NG = GX * TY, kRounds = NG / kWaves;
+    static_assert(TX % PXB == 0 && NG % kWaves == 0, "a tile is a whole number of rounds of 4 groups");
+    constexpr int FR = (TY + 1) * S, FC = (TX + 1) * S, kGCols = (PXB + 1) * S;
+    constexpr int kWList = 2 * kWinN;                   // entries of a wave's list = source-pixel taps of a direct-form pass
+    __shared__ float4 s_px[FR * FC];                    // per source pixel of the tile's footprint: (fx, fy, alpha, packed clamped (x0, y0))
+    __shared__ float s_upper[FR * FC];
+    __shared__ float4 s_wx[GX][kGCols];                 // column AA weights of each group's source columns for its 4 output pixels
+    __shared__ unsigned long long s_acc[kWaves][2 * kWinN * PXB];   // window sums; after the compaction, the float4 weights in place
+    __shared__ int2 s_list[kWaves][kWList];             // walk list: (texel offset pre-multiplied by C, float4 index of its weights)
+    __shared__ int s_bb[kWaves][8];
+    __shared__ float s_a[kWaves][PXB], s_u[kWaves][PXB];
+    __shared__ float4 s_x[4 * kWaves * kXPad];          // exchange: [channel of the lane's four][group of the round][lane]
+
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int res = p.res, Rt = p.Rt;
+    // Workgroup -> tile, XCD-aware as above: each XCD owns a contiguous band of tile rows
+    const int xtiles = (res + TX - 1) / TX, per_img = xtiles * ((res + TY - 1) / TY), nblk = per_img * p.B;
+    const int per_xcd = (nblk + 7) / 8;
+    const int logical = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    if (logical >= nblk) return;
+    const int b = logical / per_img, rem = logical - b * per_img;
+    const int ty0 = (rem / xtiles) * TY, tx0 = (rem % xtiles) * TX;
+
+    // ---- stage the footprint of the tile
+    int fy0, fy1, fx0, fx1;
+    {
+        int lo, hi; float c, inv, tot;
+        aa_taps(ty0, kSrc, res, fy0, hi, c, inv, tot);
+        aa_taps(min(ty0 + TY, res) - 1, kSrc, res, lo, fy1, c, inv, tot);
+        aa_taps(tx0, kSrc, res, fx0, hi, c, inv, tot);
+        aa_taps(min(tx0 + TX, res) - 1, kSrc, res, lo, fx1, c, inv, tot);
+    }
+    const int fcols = fx1 - fx0, nfp = (fy1 - fy0) * fcols;
+    const float* uvb = p.uv + (int64_t)b * kSrc * kSrc * 3;
+    const float* upb = p.upper + (int64_t)b * kSrc * kSrc;
+    for (int i = tid; i < nfp; i += 256) {
+        const int r = i / fcols, cidx = i - r * fcols;
+        const int Y = fy0 + r, X = fx0 + cidx;
+        const float* px = uvb + ((int64_t)Y * kSrc + X) * 3;
+        const float gx = px[0], gy = px[1];
+        // grid_sampler_2d, bilinear, zeros, align_corners = False
+        const float ix = (gx + 1.f) * (0.5f * (float)Rt) - 0.5f, iy = (gy + 1.f) * (0.5f * (float)Rt) - 0.5f;
+        const float x0f = floorf(ix), y0f = floorf(iy);
+        const int x0 = (int)fminf(fmaxf(x0f, -2.f), (float)Rt + 1.f), y0 = (int)fminf(fmaxf(y0f, -2.f), (float)Rt + 1.f);
+        s_px[r * FC + cidx] = make_float4(ix - x0f, iy - y0f, px[2], __int_as_float(((y0 + 2) << 16) | (x0 + 2)));
+        s_upper[r * FC + cidx] = upb[(int64_t)Y * kSrc + X];
+    }
+    for (int i = tid; i < GX * kGCols; i += 256) {
+        const int g = i / kGCols, ci = i - g * kGCols, xt = min(tx0 + g * PXB, res - 1);
+        int xlo[PXB], xhi[PXB]; float xc[PXB], xinv[PXB], xtot[PXB];
+#pragma unroll
+        for (int k = 0; k < PXB; ++k) aa_taps(min(xt + k, res - 1), kSrc, res, xlo[k], xhi[k], xc[k], xinv[k], xtot[k]);
+        const int X = xlo[0] + ci;
+        float w[PXB];
+#pragma unroll
+        for (int k = 0; k < PXB; ++k) w[k] = (X >= xlo[k] && X < xhi[k] && xt + k < res) ? aa_weight(X, xc[k], xinv[k], xtot[k]) : 0.f;
+        s_wx[g][ci] = make_float4(w[0], w[1], w[2], w[3]);
+    }
+    for (int i = tid; i < kWaves * 2 * kWinN * PXB; i += 256) (&s_acc[0][0])[i] = 0ull;
+    __syncthreads();
+
+    const float* texb = p.tex_cl + (int64_t)b * Rt * Rt * p.C;
+    const int64_t rr = (int64_t)res * res;
+    float* outb = p.out + (int64_t)b * (p.C + 1) * rr;
+    const int CV = (p.C % 4 == 0) ? 4 : 1;              // each lane owns 4 consecutive channels (one 16-byte gather per texel), else one
+    const int ncq = (p.C + CV - 1) / CV, npass = (ncq + 63) / 64;
+    const int crop_h = p.by1 - p.by0, crop_w = p.bx1 - p.bx0;
+    unsigned long long* acc_w = s_acc[wv];
+    float4* accf = reinterpret_cast<float4*>(acc_w);
+    int2* lst = s_list[wv];
+    int* bb = s_bb[wv];
+    auto cell = [&](float packed, int& x0, int& y0) { const int pk = __float_as_int(packed); x0 = (pk & 0xffff) - 2; y0 = (pk >> 16) - 2; };
+
+#pragma unroll 1
+    for (int rd = 0; rd < kRounds; ++rd) {
+        // ================= the chain of this wave's group
+        const int g = rd * kWaves + wv, ggy = g / GX, ggx = g - ggy * GX;
+        const int y = min(ty0 + ggy, res - 1), xt = min(tx0 + ggx * PXB, res - 1);   // (a group outside the image repeats the edge; it is not stored)
+        int ylo, yhi; float yc, yinv, ytot;
+        aa_taps(y, kSrc, res, ylo, yhi, yc, yinv, ytot);
+        int c0, ncols;
+        {
+            int lo, hi; float c, inv, tot;
+            aa_taps(xt, kSrc, res, c0, hi, c, inv, tot);
+            aa_taps(min(xt + PXB - 1, res - 1), kSrc, res, lo, hi, c, inv, tot);
+            ncols = hi - c0;
+        }
+        const int nrows = yhi - ylo, nsrc = nrows * ncols;
+        const int fbase = (ylo - fy0) * FC + (c0 - fx0);
+        const float4* wxg = s_wx[ggx];
+        if (lane == 0) { bb[0] = bb[1] = bb[4] = bb[5] = INT_MAX; bb[2] = bb[3] = bb[6] = bb[7] = INT_MIN; }
+        wave_sync();
+        // bounding box of the texels the footprint touches; resized alpha / upper-mouth alpha of the 4 output pixels
+        {
+            int mnx = INT_MAX, mny = INT_MAX, mxx = INT_MIN, mxy = INT_MIN;
+            float a[PXB] = {0.f, 0.f, 0.f, 0.f}, u[PXB] = {0.f, 0.f, 0.f, 0.f};
+            for (int i = lane; i < nsrc; i += 64) {
+                const int r = i / ncols, cidx = i - r * ncols, fi = fbase + r * FC + cidx;
+                const float4 q = s_px[fi];
+                int x0, y0;
+                cell(q.w, x0, y0);
+                const int ax = max(x0, 0), bx = min(x0 + 1, Rt - 1), ay = max(y0, 0), by = min(y0 + 1, Rt - 1);
+                if (ax <= bx && ay <= by) { mnx = min(mnx, ax); mxx = max(mxx, bx); mny = min(mny, ay); mxy = max(mxy, by); }
+                const float wy = aa_weight(ylo + r, yc, yinv, ytot);
+                const float4 wx = wxg[cidx];
+                const float av = q.z * wy, uvv = s_upper[fi] * wy;
+                a[0] = fmaf(av, wx.x, a[0]); a[1] = fmaf(av, wx.y, a[1]); a[2] = fmaf(av, wx.z, a[2]); a[3] = fmaf(av, wx.w, a[3]);
+                u[0] = fmaf(uvv, wx.x, u[0]); u[1] = fmaf(uvv, wx.y, u[1]); u[2] = fmaf(uvv, wx.z, u[2]); u[3] = fmaf(uvv, wx.w, u[3]);
+            }
+            if (mnx <= mxx) { atomicMin(&bb[0], mnx); atomicMin(&bb[1], mny); atomicMax(&bb[2], mxx); atomicMax(&bb[3], mxy); }
+#pragma unroll
+            for (int k = 0; k < PXB; ++k)
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) { a[k] += __shfl_xor(a[k], off); u[k] += __shfl_xor(u[k], off); }
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < PXB; ++k) { s_a[wv][k] = a[k]; s_u[wv][k] = u[k]; }
+            }
+        }
+        wave_sync();
+        const int ax0 = bb[0], ay0 = bb[1];
+        const bool none = bb[2] < bb[0];                                       // every bilinear cell lies in the zero padding
+        const bool one = none || (bb[2] - ax0 < kWinW && bb[3] - ay0 < kWinH);
+        auto in_a = [&](int x0, int y0) {
+            const int lx = max(x0, 0), hx = min(x0 + 1, Rt - 1), ly = max(y0, 0), hy = min(y0 + 1, Rt - 1);
+            return lx > hx || ly > hy || (hx - ax0 < kWinW && hy - ay0 < kWinH);
+        };
+        if (!one) {                                                            // (wave-uniform) second window: bounding box of what A leaves
+            int bnx = INT_MAX, bny = INT_MAX, bxx = INT_MIN, bxy = INT_MIN;
+            for (int i = lane; i < nsrc; i += 64) {
+                const int r = i / ncols, cidx = i - r * ncols;
+                int x0, y0;
+                cell(s_px[fbase + r * FC + cidx].w, x0, y0);
+                if (!in_a(x0, y0)) { bnx = min(bnx, max(x0, 0)); bxx = max(bxx, min(x0 + 1, Rt - 1)); bny = min(bny, max(y0, 0)); bxy = max(bxy, min(y0 + 1, Rt - 1)); }
+            }
+            if (bnx <= bxx) { atomicMin(&bb[4], bnx); atomicMin(&bb[5], bny); atomicMax(&bb[6], bxx); atomicMax(&bb[7], bxy); }
+            wave_sync();
+        }
+        const int bx0 = bb[4], by0 = bb[5];
+        const bool merged = one || (bb[6] - bx0 < kWinW && bb[7] - by0 < kWinH);
+        int nlist = 0;
+        if (merged && !none) {
+            for (int i = lane; i < nsrc; i += 64) {
+                const int r = i / ncols, cidx = i - r * ncols;
+                const float4 q = s_px[fbase + r * FC + cidx];
+                const float wy = aa_weight(ylo + r, yc, yinv, ytot);
+                const float4 wxv = wxg[cidx];
+                const float wx[PXB] = {wxv.x, wxv.y, wxv.z, wxv.w};
+                int x0, y0;
+                cell(q.w, x0, y0);
+                const bool a = one || in_a(x0, y0);
+                unsigned long long* win = acc_w + (a ? 0 : kWinN * PXB);
+                const int ox = a ? ax0 : bx0, oy = a ? ay0 : by0;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
+                    if (xi < 0 || xi >= Rt || yi < 0 || yi >= Rt) continue;
+                    const float w = ((t & 1) ? q.x : 1.f - q.x) * ((t >> 1) ? q.y : 1.f - q.y) * wy;
+                    unsigned long long* slot = win + ((yi - oy) * kWinW + (xi - ox)) * PXB;
+#pragma unroll
+                    for (int k = 0; k < PXB; ++k) {
+                        const unsigned long long v = (unsigned long long)(w * wx[k] * kFix);
+                        if (v) atomicAdd(slot + k, v);
+                    }
+                }
+            }
+            wave_sync();
+            // ordered compaction, 64 window slots a step; a slot's weights replace its sums in place (each lane its own slot)
+            for (int base = 0; base < (one ? kWinN : 2 * kWinN); base += 64) {
+                const int e = base + lane;
+                const unsigned long long a0 = acc_w[e * PXB], a1 = acc_w[e * PXB + 1], a2 = acc_w[e * PXB + 2], a3 = acc_w[e * PXB + 3];
+                const bool nz = (a0 | a1 | a2 | a3) != 0ull;
+                const unsigned long long m = __ballot(nz);
+                if (nz) {
+                    const int pos = nlist + __popcll(m & ((1ull << lane) - 1ull));
+                    const int slot = e % kWinN, ox = e < kWinN ? ax0 : bx0, oy = e < kWinN ? ay0 : by0;
+                    lst[pos] = make_int2(((oy + slot / kWinW) * Rt + ox + slot % kWinW) * p.C, 2 * e);
+                    accf[2 * e] = make_float4((float)a0 * (1.f / kFix), (float)a1 * (1.f / kFix), (float)a2 * (1.f / kFix), (float)a3 * (1.f / kFix));
+                }
+                nlist += __popcll(m);
+            }
+            wave_sync();
+        }
+
+        // add the first n entries of the wave's list for channels c .. c+CV-1
+        auto walk = [&](int c, int n, float (&acc)[4][PXB]) {
+            const float* tc = texb + c;
+            if (IA_RAST_ABLATE & 2) return;
+            if (CV == 4) {
+#pragma unroll 8
+                for (int e = 0; e < n; ++e) {
+                    const int2 en = lst[e];
+                    const float4 t = *(const float4*)(tc + en.x);
+                    const float4 w = accf[en.y];
+                    acc[0][0] = fmaf(t.x, w.x, acc[0][0]); acc[0][1] = fmaf(t.x, w.y, acc[0][1]); acc[0][2] = fmaf(t.x, w.z, acc[0][2]); acc[0][3] = fmaf(t.x, w.w, acc[0][3]);
+                    acc[1][0] = fmaf(t.y, w.x, acc[1][0]); acc[1][1] = fmaf(t.y, w.y, acc[1][1]); acc[1][2] = fmaf(t.y, w.z, acc[1][2]); acc[1][3] = fmaf(t.y, w.w, acc[1][3]);
+                    acc[2][0] = fmaf(t.z, w.x, acc[2][0]); acc[2][1] = fmaf(t.z, w.y, acc[2][1]); acc[2][2] = fmaf(t.z, w.z, acc[2][2]); acc[2][3] = fmaf(t.z, w.w, acc[2][3]);
+                    acc[3][0] = fmaf(t.w, w.x, acc[3][0]); acc[3][1] = fmaf(t.w, w.y, acc[3][1]); acc[3][2] = fmaf(t.w, w.z, acc[3][2]); acc[3][3] = fmaf(t.w, w.w, acc[3][3]);
+                }
+            } else {
+                for (int e = 0; e < n; ++e) {
+                    const int2 en = lst[e];
+                    const float t = tc[en.x];
+                    const float4 w = accf[en.y];
+                    acc[0][0] = fmaf(t, w.x, acc[0][0]); acc[0][1] = fmaf(t, w.y, acc[0][1]); acc[0][2] = fmaf(t, w.z, acc[0][2]); acc[0][3] = fmaf(t, w.w, acc[0][3]);
+                }
+            }
+        };
+
+        // ================= the finishing half of this thread: group fg of the round, channel groups fq (+ 64 a pass)
+        const int fg = tid & 3, fq = tid >> 2;
+        const int g2 = rd * kWaves + fg, g2y = g2 / GX, fy = ty0 + g2y, fxt = tx0 + (g2 - g2y * GX) * PXB;
+        const bool fvalid = fy < res && fxt < res;
+        const int fyc = min(fy, res - 1), fxc = min(fxt, res - 1);
+        const bool vec_ok = (fxt + PXB <= res) && (res % 4 == 0);
+        // static crop: 2-tap (per axis) AA up-sampling weights, identical for every channel; the (<= kSRows x kSCols) source window
+        // of the 4 output pixels and its separable weights are tabulated once (wide windows fall back to the direct double loop)
+        constexpr int kSRows = 3, kSCols = 6;
+        int sylo, syhi; float syc, syinv, sytot;
+        aa_taps(fyc, crop_h, res, sylo, syhi, syc, syinv, sytot);
+        int sxlo[PXB], sxhi[PXB]; float sxc[PXB], sxinv[PXB], sxtot[PXB];
+#pragma unroll
+        for (int k = 0; k < PXB; ++k) aa_taps(min(fxc + k, res - 1), crop_w, res, sxlo[k], sxhi[k], sxc[k], sxinv[k], sxtot[k]);
+        const int s_c0 = sxlo[0], s_nc = sxhi[PXB - 1] - sxlo[0], s_nr = syhi - sylo;
+        const bool s_tab = s_nr <= kSRows && s_nc <= kSCols && s_nc > 0;
+        float swy[kSRows], swx[PXB][kSCols];
+#pragma unroll
+        for (int r = 0; r < kSRows; ++r) swy[r] = (s_tab && r < s_nr) ? aa_weight(sylo + r, syc, syinv, sytot) : 0.f;
+#pragma unroll
+        for (int k = 0; k < PXB; ++k)
+#pragma unroll
+            for (int i = 0; i < kSCols; ++i) {
+                const int X = s_c0 + i;
+                swx[k][i] = (s_tab && X >= sxlo[k] && X < sxhi[k]) ? aa_weight(X, sxc[k], sxinv[k], sxtot[k]) : 0.f;
+            }
+        // blend channel c of the 4 output pixels with the resized static crop and store it
+        auto finish = [&](int c, const float4 rend) {
+            const float acc[PXB] = {rend.x, rend.y, rend.z, rend.w};
+            const float* sc = p.sta + (int64_t)b * p.sta_bs + (int64_t)c * p.Rs * p.Rs;
+            float o[PXB];
+            if (s_tab) {
+                float sv[PXB] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int r = 0; r < kSRows; ++r) {
+                    if (r < s_nr) {
+                        const float* row = sc + (int64_t)(p.by0 + sylo + r) * p.Rs + p.bx0 + s_c0;
+                        float h[PXB] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int i = 0; i < kSCols; ++i) {
+                            if (i < s_nc) {
+                                const float v = (IA_RAST_ABLATE & 1) ? 0.f : row[i];
+#pragma unroll
+                                for (int k = 0; k < PXB; ++k) h[k] = fmaf(v, swx[k][i], h[k]);
+                            }
+                        }
+#pragma unroll
+                        for (int k = 0; k < PXB; ++k) sv[k] = fmaf(h[k], swy[r], sv[k]);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < PXB; ++k) { const float a = s_a[fg][k]; o[k] = acc[k] * a + sv[k] * (1.f - a); }
+            } else {
+#pragma unroll
+                for (int k = 0; k < PXB; ++k) {
+                    float sv = 0.f;
+                    for (int jj = sylo; jj < syhi; ++jj) {
+                        const float wj = aa_weight(jj, syc, syinv, sytot);
+                        for (int i = sxlo[k]; i < sxhi[k]; ++i)
+                            sv = fmaf(sc[(int64_t)(p.by0 + jj) * p.Rs + p.bx0 + i], wj * aa_weight(i, sxc[k], sxinv[k], sxtot[k]), sv);
+                    }
+                    const float a = s_a[fg][k];
+                    o[k] = acc[k] * a + sv * (1.f - a);
+                }
+            }
+            if ((IA_RAST_ABLATE & 4) && p.res > 0) return;                     // (the run-time half keeps the arithmetic alive)
+            float* dst = outb + (int64_t)c * rr + (int64_t)fy * res + fxt;
+            if (vec_ok) *(float4*)dst = make_float4(o[0], o[1], o[2], o[3]);
+            else for (int k = 0; k < PXB && fxt + k < res; ++k) dst[k] = o[k];
+        };
+
+#pragma unroll 1
+        for (int pass = 0; pass < npass; ++pass) {                             // one pass per 64 channel groups
+            const int mycq = pass * 64 + lane;
+            const bool active = mycq < ncq;
+            float acc[4][PXB];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int k = 0; k < PXB; ++k) acc[j][k] = 0.f;
+            if (merged) {
+                if (active) walk(mycq * CV, nlist, acc);
+            } else {
+                // direct form: the footprint touches more texels than the windows hold (a seam or the silhouette of the UV map):
+                // every (source pixel, bilinear tap) becomes its own list entry, one source pixel per lane a pass; the weights
+                // take the place of the (unused) window sums
+                for (int base = 0; base < nsrc; base += 64) {
+                    const int cnt = min(64, nsrc - base);
+                    wave_sync();
+                    if (lane < cnt) {
+                        const int i = base + lane, r = i / ncols, cidx = i - r * ncols;
+                        const float4 q = s_px[fbase + r * FC + cidx];
+                        const float wy = aa_weight(ylo + r, yc, yinv, ytot);
+                        const float4 wxv = wxg[cidx];
+                        int x0, y0;
+                        cell(q.w, x0, y0);
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const int xi = x0 + (t & 1), yi = y0 + (t >> 1);
+                            const bool ok = xi >= 0 && xi < Rt && yi >= 0 && yi < Rt;
+                            const float w = ok ? ((t & 1) ? q.x : 1.f - q.x) * ((t >> 1) ? q.y : 1.f - q.y) * wy : 0.f;
+                            lst[4 * lane + t] = make_int2(ok ? (yi * Rt + xi) * p.C : 0, 4 * lane + t);
+                            accf[4 * lane + t] = make_float4(w * wxv.x, w * wxv.y, w * wxv.z, w * wxv.w);
+                        }
+                    }
+                    wave_sync();
+                    if (active) walk(mycq * CV, 4 * cnt, acc);
+                }
+            }
+            // the sums of the round's four groups change hands
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_x[(j * kWaves + wv) * kXPad + lane] = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+            __syncthreads();
+            const int cq = pass * 64 + fq;
+            if (fvalid && cq < ncq)
+                for (int j = 0; j < CV; ++j) finish(cq * CV + j, s_x[(j * kWaves + fg) * kXPad + fq]);
+            if (pass == 0 && tid < kWaves * PXB) {                             // the resized upper-mouth alpha: channel C
+                const int ug = tid >> 2, uk = tid & 3, g3 = rd * kWaves + ug, g3y = g3 / GX;
+                const int uy = ty0 + g3y, ux = tx0 + (g3 - g3y * GX) * PXB + uk;
+                if (uy < res && ux < res) outb[(int64_t)p.C * rr + (int64_t)uy * res + ux] = s_u[ug][uk];
+            }
+            __syncthreads();                                                   // s_x, s_a and s_u have been read
+        }
+        // the window sums are zero again for the wave's next group
+        if (kRounds > 1 && rd + 1 < kRounds) {
+            wave_sync();
+            if (merged) {
+                for (int e = lane; e < nlist; e += 64) { const int f = lst[e].y; accf[f] = make_float4(0.f, 0.f, 0.f, 0.f); accf[f + 1] = make_float4(0.f, 0.f, 0.f, 0.f); }
+            } else {
+                for (int e = lane; e < kWList; e += 64) accf[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+}
+
 struct BlendParams {
     const float* stitch;     // [B][32][256][256]
     const float* alpha;      // [B][256][256]      full (mouth-filled) alpha
@@ -460,6 +832,18 @@ extern "C" int ia_rasterize_level(const float* tex_cl, const float* uv, const fl
     if (res > kSrc || kSrc % res != 0 || kSrc / res > kMaxScale || kSrc / res < 2)
         return ia::fail(IA_ERR_UNSUPPORTED, "rasterize level resolution %d: supported are 32, 64, 128 (256 -> res by 8, 4, 2)", res);
     RastParams p{tex_cl, uv, upper_alpha, sta, out, sta_batch_stride, B, C, tex_res, sta_res, res, by0, by1, bx0, bx1};
+    const hipStream_t s = (hipStream_t)stream;
+    // 64^2 and 128^2: tiles of 16 x 1 output pixels (a 64^2 level has 256 of them, one per CU; a 32^2 level has 256
+    // groups in all and stays with one group per workgroup)
+    if (kSrc / res == 4 || kSrc / res == 2) {
+        constexpr int TX = 16, TY4 = IA_RAST_TY64, TY2 = IA_RAST_TY128;
+        const int ty = kSrc / res == 4 ? TY4 : TY2;
+        const int ntile = ((res + TX - 1) / TX) * ((res + ty - 1) / ty) * B;
+        dim3 tgrid(((ntile + 7) / 8) * 8);
+        if (kSrc / res == 4) hipLaunchKernelGGL((rasterize_tile_kernel<4, TX, TY4>), tgrid, dim3(64 * kWaves), 0, s, p);
+        else hipLaunchKernelGGL((rasterize_tile_kernel<2, TX, TY2>), tgrid, dim3(64 * kWaves), 0, s, p);
+        return ia::check_launch("ia_rasterize_level");
+    }
     const int nblk = ((res + PXB - 1) / PXB) * res * B;
     dim3 grid(((nblk + 7) / 8) * 8);
     // one thread per group of 4 channels (64 .. 256 threads); spare threads split the walk list up to 8 ways
@@ -468,12 +852,7 @@ extern "C" int ia_rasterize_level(const float* tex_cl, const float* uv, const fl
     const int lanes = ncq < threads ? ncq : threads;
     const int nsplit = threads / lanes < 8 ? threads / lanes : 8;
     const size_t red_bytes = nsplit > 1 ? (size_t)nsplit * lanes * 16 * sizeof(float) : 0;
-    const hipStream_t s = (hipStream_t)stream;
-    switch (kSrc / res) {
-        case 8: hipLaunchKernelGGL(rasterize_level_kernel<8>, grid, dim3(threads), red_bytes, s, p); break;
-        case 4: hipLaunchKernelGGL(rasterize_level_kernel<4>, grid, dim3(threads), red_bytes, s, p); break;
-        default: hipLaunchKernelGGL(rasterize_level_kernel<2>, grid, dim3(threads), red_bytes, s, p); break;
-    }
+    hipLaunchKernelGGL(rasterize_level_kernel<8>, grid, dim3(threads), red_bytes, s, p);
     return ia::check_launch("ia_rasterize_level");
 }
 

@@ -1216,6 +1216,43 @@ int ia_closest_point_tree(const float* points, int64_t N, const void* sorted, co
                           int64_t n_nodes, float mesh_extent, float* dist, int* face, float* point, int* counts, void* stream);
 
 /*
+ * Rays against the mesh on the cluster tree (csrc/ray_tree.hip; no counterpart in the reference; definition:
+ * geometry._ray_mesh_numpy, the walk geometry._ray_tree_numpy).  Additive entry points: the ABI version is unchanged.
+ *
+ * Rays: origins and dirs float32 [N,3], t_lo and t_hi float32 [N] (the ray's own interval; +-inf allowed).  Per triangle, in fp32 with
+ * every operation rounded on its own and dot products (x + y) + z, relative to the origin (a = A - o, ...): wa = d . (b x c),
+ * wb = d . (c x a), wc = d . (a x b); inside = all three >= 0 or all three <= 0; n = (b - a) x (c - a), den = n . d, t = (n . a) / den.
+ * The triangle is accepted iff inside, den != 0, t is finite, t_lo <= t <= t_hi and the point o + t d lies in the
+ * triangle's own bounding box grown on every side by 2^-14 max(|o|_inf, |A|_inf, |B|_inf, |C|_inf) (without this clause the edge
+ * functions accept, from far away, small triangles that the ray misses by any distance).  The test is NOT watertight: the signs of one
+ * triangle are rounded separately, so a ray aimed at a shared edge or vertex can miss both neighbours.
+ * first hit (any = 0): the smallest pair (t, input face index) over all accepted usable triangles: hit uint8 [N], t float32 [N],
+ * face int32 [N] (order[sorted position]), bary float32 [N,3] = (wa, wb, wc) / ((wa + wb) + wc), point float32 [N,3] = o + t d.
+ * No accepted triangle: 0 / +inf / -1 / NaN / NaN.  A ray with a non-finite origin or direction or a NaN interval end: 0 / NaN / -1 /
+ * NaN / NaN.  any hit (any = 1): hit only; t, face, bary and point may be NULL and are not written.
+ * ia_ray_mesh_brute: every ray against every sorted usable triangle (the triangles of ia_winding_tree_gather): the definition.
+ * ia_ray_mesh_tree: the same bits by the walk of ia_closest_point_tree over the boxes of ia_tree_boxes, children in index order.  A
+ * node is skipped iff a slab test on its box, grown on every side by s = 2^-12 M with M = max(|o|_inf, mesh_extent),
+ * leaves no t in [t_lo, min(t_hi, best t)]: per axis t0 = ((lo - o) - s) (1 / d), t1 = ((hi - o) + s) (1 / d), every t when either is
+ * a NaN, 1 / d overflowed for d != 0, or |t0|, |t1| or |1 / d| is below 2^-100; near = the largest min(t0, t1), far = the smallest max(t0, t1), each moved outward by the
+ * factor 1 +- 2^-20; skipped iff near > far or near > min(t_hi, best t) or far < t_lo (a NaN compares false: entered).  In the any mode
+ * a ray that has a hit tests nothing more.  counts (int32 [N,2], or NULL): boxes tested and ray-triangle pairs of the leaves entered.
+ * N >= 0 with 3 N < 2^31, 0 <= F_usable <= 2^25, n_nodes that of ia_winding_tree_plan.
+ * ia_ao_rays: for V vertices (verts, normals float32 [V,3], unit normals) and a table float32 [S,3] of local directions (z up), ray
+ * v S + s: origin = v + bias n, direction = (t1 x + t2 y) + n z per component with sign = copysign(1, n.z), a = -1 / (sign + n.z),
+ * b = (n.x n.y) a, t1 = (1 + ((sign n.x) n.x) a, sign b, -(sign n.x)), t2 = (b, sign + (n.y n.y) a, -n.y) (Duff et al. 2017).  A
+ * non-finite normal gives NaN rays.  3 V S < 2^31, 1 <= S <= 65536.
+ */
+int ia_ray_mesh_brute(const float* origins, const float* dirs, const float* t_lo, const float* t_hi, int64_t N, const void* sorted,
+                      const int* order, int64_t F_usable, int any, unsigned char* hit, float* t, int* face, float* bary, float* point,
+                      void* stream);
+int ia_ray_mesh_tree(const float* origins, const float* dirs, const float* t_lo, const float* t_hi, int64_t N, const void* sorted,
+                     const int* order, int64_t F_usable, const void* boxes, int64_t n_nodes, float mesh_extent, int any,
+                     unsigned char* hit, float* t, int* face, float* bary, float* point, int* counts, void* stream);
+int ia_ao_rays(const float* verts, const float* normals, int64_t V, const float* table, int S, float bias, float* origins, float* dirs,
+               void* stream);
+
+/*
  * Texture atlas of a triangle mesh (csrc/texture.hip; no counterpart in the reference; definition: geometry.TextureAtlas,
  * atlas_points, project_texture and sample_texture with their NumPy restatements).  Additive entry points: the ABI
  * version is unchanged.  The texture is size x size texels (4 <= size <= 16384), texel (i, j) = column i, row j, stored [j][i]; faces

@@ -177,6 +177,9 @@ _SIGNATURES = {
     'ia_tree_boxes': [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
     'ia_closest_point_tree': [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p],
+    'ia_ray_mesh_brute': [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 6,
+    'ia_ray_mesh_tree': [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_int] + [c_void_p] * 7,
+    'ia_ao_rays': [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
     'ia_atlas_points': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 7,
     'ia_texture_project': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                            c_float, ctypes.c_double, c_float, c_int] + [c_void_p] * 6,

@@ -149,6 +149,30 @@ __device__ __forceinline__ float tri_dist(Vec3<float> p, Vec3<float> A, Vec3<flo
     return d;
 }
 
+// The per-triangle function of the ray queries (ray_tree.hip), every operation rounded on its own: the ray o + t d against the closed
+// triangle ABC, both orientations.  Relative to the origin, w = the three edge functions (d . (b x c), d . (c x a), d . (a x b)); the
+// ray is inside iff none is negative or none is positive; t = (n . a) / (n . d) with n = (b - a) x (c - a).  Accepted iff inside,
+// n . d != 0, t finite, t_lo <= t <= t_hi (a NaN compares false) and the point p = o + t d lies in the triangle's own bounding box
+// grown by g = 2^-14 max(|o|_inf, |A|_inf, |B|_inf, |C|_inf) on every side.  The last clause is what makes pruning by boxes sound at
+// all: far from the origin of the ray the edge functions accept small triangles that the ray misses by any distance.
+// The barycentrics are w / ((w.x + w.y) + w.z), the caller's.  Not watertight: the three signs of one triangle are rounded separately.
+__device__ __forceinline__ float max_abs(Vec3<float> v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)); }
+__device__ __forceinline__ bool ray_tri(Vec3<float> o, Vec3<float> d, float t_lo, float t_hi, Vec3<float> A, Vec3<float> B, Vec3<float> C,
+                                        float& t, Vec3<float>& w) {
+    const Vec3<float> a = sub(A, o), b = sub(B, o), c = sub(C, o);
+    w = {dot(d, cross(b, c)), dot(d, cross(c, a)), dot(d, cross(a, b))};
+    const bool inside = (w.x >= 0.f && w.y >= 0.f && w.z >= 0.f) || (w.x <= 0.f && w.y <= 0.f && w.z <= 0.f);
+    const Vec3<float> n = cross(sub(b, a), sub(c, a));
+    const float den = dot(n, d);
+    t = dot(n, a) / den;
+    const float g = 6.103515625e-5f * fmaxf(fmaxf(max_abs(o), max_abs(A)), fmaxf(max_abs(B), max_abs(C)));          // 2^-14
+    const Vec3<float> p = {o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
+    const bool boxed = fminf(fminf(A.x, B.x), C.x) - g <= p.x && p.x <= fmaxf(fmaxf(A.x, B.x), C.x) + g &&
+                       fminf(fminf(A.y, B.y), C.y) - g <= p.y && p.y <= fmaxf(fmaxf(A.y, B.y), C.y) + g &&
+                       fminf(fminf(A.z, B.z), C.z) - g <= p.z && p.z <= fmaxf(fmaxf(A.z, B.z), C.z) + g;
+    return inside && den != 0.f && isfinite(t) && t_lo <= t && t <= t_hi && boxed;
+}
+
 // Cell of coordinate x along an axis of n cells that starts at lo, inv = 1 / cell size; a NaN lands in cell 0.
 __device__ __forceinline__ int cell_of(float x, float lo, float inv, int n) {
     return (int)fminf(fmaxf(floorf((x - lo) * inv), 0.f), (float)(n - 1));

@@ -21,7 +21,9 @@ Hausdorff distances beside the cell diagonal and writes them into ``seed%04d_geo
 Taubin pairs (``geometry.smooth_mesh``, after ``--keep`` and ``--simplify``; ``--smooth-lambda``, ``--smooth-mu`` (``none``: plain Laplacian
 steps) and ``--smooth-weights`` set its arguments; normals then come from the mesh) and prints the boundary and non-manifold edge counts;
 ``--smooth-check`` prints the signed volume before and after and both directed Hausdorff distances between the smoothed and the
-unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  ``--mesh-views N`` renders the FINAL mesh (after ``--keep``,
+unsmoothed mesh, and writes them into ``seed%04d_geometry.json``.  ``--ao SAMPLES`` shoots SAMPLES cosine-weighted rays from every vertex of the FINAL mesh
+(``geometry.ambient_occlusion``), writes ``seed%04d_ao.ply`` with grey vertex colours ``round(255 ao)``, prints the mean and adds an
+``ambient_occlusion`` block to ``seed%04d_geometry.json``.  ``--mesh-views N`` renders the FINAL mesh (after ``--keep``,
 ``--simplify`` and ``--smooth``) from the same orbit through ``geometry.rasterize_mesh`` and writes the shaded views as
 ``seed%04d_meshview%02d.png``, the coloured ones as ``seed%04d_meshrgb%02d.png`` (unless ``--no-colors``) and, with ``--compare
 --error-ply``, the error-coloured mesh as ``seed%04d_errorview%02d.png``; ``--save-depth`` adds ``seed%04d_meshdepth.npy``; a line per
@@ -115,6 +117,7 @@ def main(argv=None):
     ap.add_argument('--smooth-mu', type=parse_mu, default=-0.53, help="the negative factor of a pair, or 'none' for plain Laplacian steps")
     ap.add_argument('--smooth-weights', default='uniform', choices=['uniform', 'cotangent'])
     ap.add_argument('--smooth-check', action='store_true', help='with --smooth: signed volume before and after, distance to the unsmoothed mesh')
+    ap.add_argument('--ao', type=int, default=None, metavar='SAMPLES', help='ambient occlusion of the final mesh with SAMPLES rays per vertex; writes _ao.ply')
     ap.add_argument('--texture', type=int, default=None, metavar='SIZE', help='bake the colours of the final mesh into a SIZE^2 texture atlas; writes .obj/.mtl/.png')
     ap.add_argument('--texture-source', default='decoder', choices=['decoder', 'views'], help='colours from the decoder, or projected from rendered views')
     ap.add_argument('--texture-views', type=int, default=8, help='with --texture-source views: the number of views of the yaw orbit')
@@ -219,6 +222,21 @@ def main(argv=None):
             if args.align:
                 print(f'seed {seed}: {geometry_metrics.alignment_summary(out["metrics"]["alignment"])}')
             print(f'seed {seed}: against {args.compare}: {geometry_metrics.summary(out["metrics"])}')
+        if args.ao is not None:
+            ao = geometry.ambient_occlusion(out['verts'], out['faces'], samples=args.ao)
+            grey = (ao['ao'] * 255.0).round().to(torch.uint8)[:, None].expand(-1, 3).cpu().numpy()
+            apath = os.path.join(args.outdir, f'seed{seed:04d}_ao.ply')
+            geometry.write_ply(apath, out['verts'].cpu().numpy(), out['faces'].cpu().numpy(), colors=grey)
+            out['ambient_occlusion'] = {'samples': ao['samples'], 'seed': 0, 'mean': float(ao['ao'].double().mean()) if ao['ao'].numel() else 0.0,
+                                        'min': float(ao['ao'].min()) if ao['ao'].numel() else 0.0, 'ply': os.path.basename(apath)}
+            gpath = os.path.join(args.outdir, f'seed{seed:04d}_geometry.json')
+            meta = {}
+            if os.path.exists(gpath) and any(k in out for k in ('simplify', 'smooth', 'metrics')):
+                with open(gpath) as fh:
+                    meta = json.load(fh)
+            with open(gpath, 'w') as fh:
+                json.dump(dict(meta, ambient_occlusion=out['ambient_occlusion']), fh, indent=1)
+            print(f'seed {seed}: ambient occlusion with {ao["samples"]} samples per vertex, mean {out["ambient_occlusion"]["mean"]:.4f} -> {apath}')
         if args.views > 0:
             from PIL import Image
             cams = orbit_cameras(G, args.views, device=args.device)[None]

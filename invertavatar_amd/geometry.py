@@ -1658,6 +1658,214 @@ def _closest_tree_numpy(points, tree, dtype=np.float64, slack=None):
     return best_d, best_f.astype(np.int32), point, np.stack([n_box, n_pair], -1)
 
 
+# ---- rays against the mesh on the same tree (csrc/ray_tree.hip)
+
+_RAY_MODES = ('first', 'any')
+_RAY_GUARD = 2.0 ** -14      # ray_tri: the hit point lies in the triangle's box grown by this times the largest |coordinate|
+_RAY_SLACK = 2.0 ** -12      # the boxes of the tree grow by this times M = max(|o|_inf, extent): DESIGN.md 4.28
+_RAY_TINY = 2.0 ** -100      # a slab product or reciprocal below this is not trusted: the axis admits every t
+_RAY_IN, _RAY_OUT = 1.0 - 2.0 ** -20, 1.0 + 2.0 ** -20     # the slab interval's ends are moved outward by these factors
+_AO_MAX_RAYS = 1 << 22
+
+
+def _ray_mode(mode):
+    if mode not in _RAY_MODES:
+        raise ValueError(f'mode must be one of {_RAY_MODES}, got {mode!r}')
+    return mode
+
+
+def _ray_tri(o, d, A, B, C, dtype=np.float64):
+    """The per-triangle function of the ray queries (csrc/geom_common.h ray_tri) in ``dtype`` on broadcastable [..., 3] arrays:
+    ``(t, w, ok)``.  Relative to the origin (``a = A - o`` ...), ``w = (d . (b x c), d . (c x a), d . (a x b))``; the ray is inside iff
+    no ``w`` is negative or none is positive (closed edges, both orientations); ``t = (n . a) / (n . d)`` with ``n = (b - a) x (c - a)``;
+    ``ok = inside and n . d != 0 and t finite`` and the point ``o + t d`` lies in the triangle's own bounding box grown by ``2^-14
+    max(|o|_inf, |A|_inf, |B|_inf, |C|_inf)`` on every side (far from the ray's origin the edge functions alone accept small triangles
+    that the ray misses by any distance; with this clause a box that the ray misses holds no accepted triangle).  The caller adds the ray's interval ``t_lo <= t <= t_hi`` and forms the barycentrics
+    ``w / ((w0 + w1) + w2)``.  Every operation is rounded on its own, so the float32 run follows the kernel operation by operation.
+    Not watertight: the three signs of one triangle are rounded separately."""
+    o, d, A, B, C = (np.asarray(x, dtype=dtype) for x in (o, d, A, B, C))
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore', under='ignore'):
+        a, b, c = A - o, B - o, C - o
+        a, b, c, d = np.broadcast_arrays(a, b, c, d)
+        w = np.stack([_dot3(d, _cross3(b, c)), _dot3(d, _cross3(c, a)), _dot3(d, _cross3(a, b))], -1)
+        inside = (w >= 0).all(-1) | (w <= 0).all(-1)
+        n = _cross3(b - a, c - a)
+        den = _dot3(n, d)
+        t = _dot3(n, a) / den
+        g = dtype(_RAY_GUARD) * np.maximum(np.maximum(np.abs(o).max(-1), np.abs(A).max(-1)), np.maximum(np.abs(B).max(-1), np.abs(C).max(-1)))
+        p = o + t[..., None] * d
+        lo, hi = np.minimum(np.minimum(A, B), C) - g[..., None], np.maximum(np.maximum(A, B), C) + g[..., None]
+        boxed = ((lo <= p) & (p <= hi)).all(-1)
+    return t, w, inside & (den != 0) & np.isfinite(t) & boxed
+
+
+def _ray_rows(origins, dirs, t_min, t_max):
+    """(origins, dirs float32 [N,3], t_lo, t_hi float32 [N], walked bool [N]): scalars or per-ray intervals; a ray with a non-finite
+    origin or direction or a NaN interval end is not walked."""
+    o = np.asarray(origins, dtype=F32).reshape(-1, 3)
+    d = np.asarray(dirs, dtype=F32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f'origins and dirs must have the same shape, got {o.shape} and {d.shape}')
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=F32).reshape(-1), (o.shape[0],)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=F32).reshape(-1), (o.shape[0],)))
+    return o, d, lo, hi, np.isfinite(o).all(1) & np.isfinite(d).all(1) & ~np.isnan(lo) & ~np.isnan(hi)
+
+
+def _ray_result(o, d, tris, at, hit, ok, dtype):
+    """(t, bary, point) of rays against their winning triangles ``tris[at]`` (where ``hit``); +inf / NaN / NaN without a hit, NaN
+    for a ray that was not walked."""
+    n = o.shape[0]
+    t = np.where(ok, np.inf, np.nan).astype(dtype)
+    bary, point = np.full((n, 3), np.nan, dtype=dtype), np.full((n, 3), np.nan, dtype=dtype)
+    r = np.flatnonzero(hit)
+    if r.size:
+        with np.errstate(invalid='ignore', divide='ignore', over='ignore', under='ignore'):
+            tr = tris[at[r]]
+            tt, w, _ = _ray_tri(o[r], d[r], tr[:, 0], tr[:, 1], tr[:, 2], dtype)
+            t[r] = tt
+            bary[r] = w / ((w[:, 0] + w[:, 1]) + w[:, 2])[:, None]
+            point[r] = o[r] + tt[:, None] * d[r]
+    return t, bary, point
+
+
+def _ray_leaf(o, d, lo, hi, tris, faces, dtype):
+    """Rays [n] against triangles [m] with input indices ``faces``: (accepted [n,m], t [n,m], per ray the smallest accepted t (+inf
+    without one), the lowest face among those that attain it, and its column)."""
+    t, _, acc = _ray_tri(o[:, None, :], d[:, None, :], tris[None, :, 0], tris[None, :, 1], tris[None, :, 2], dtype)
+    acc = acc & (lo[:, None] <= t) & (t <= hi[:, None])
+    tv = np.where(acc, t, np.inf)
+    tm = tv.min(1) if tv.shape[1] else np.full(o.shape[0], np.inf, dtype=dtype)
+    tie = acc & (tv == tm[:, None])
+    fm = np.where(tie, faces[None, :], np.iinfo(np.int64).max).min(1) if tv.shape[1] else np.full(o.shape[0], -1, dtype=np.int64)
+    col = np.argmax(tie & (faces[None, :] == fm[:, None]), axis=1) if tv.shape[1] else np.zeros(o.shape[0], dtype=np.int64)
+    return acc, tm, fm, col
+
+
+def _ray_mesh_numpy(origins, dirs, verts, faces, t_min=0.0, t_max=np.inf, dtype=np.float64, pairs=1 << 20):
+    """The definition of the ray queries, and the NumPy restatement of ia_ray_mesh_brute in ``dtype``: every ray against every usable
+    triangle with ``_ray_tri``; the first hit is the smallest pair (t, input face index) over the triangles accepted within the ray's
+    own interval.  ``(hit bool [N], t [N], face int32 [N], bary [N,3], point [N,3])``: +inf / -1 / NaN / NaN without an accepted
+    triangle, NaN / -1 / NaN / NaN for a ray that is not walked (``_ray_rows``); the any-hit answer is ``hit``."""
+    o32, d32, lo32, hi32, ok = _ray_rows(origins, dirs, t_min, t_max)
+    o, d, lo, hi = (x.astype(dtype) for x in (o32, d32, lo32, hi32))
+    v = np.asarray(verts, dtype=F32).reshape(-1, 3).astype(dtype)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    n = o.shape[0]
+    in_range = ((f >= 0) & (f < v.shape[0])).all(1)
+    tri = v[np.where(in_range[:, None], f, 0)] if v.shape[0] else np.zeros((f.shape[0], 3, 3), dtype=dtype)
+    usable = np.flatnonzero(in_range & np.isfinite(tri).all((1, 2)))
+    tri = tri[usable]
+    hit, face, at = np.zeros(n, dtype=bool), np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.int64)
+    rows = np.flatnonzero(ok)
+    if usable.size and rows.size:
+        step = max(1, pairs // usable.size)
+        for s in range(0, rows.size, step):
+            r = rows[s:s + step]
+            acc, _, fm, col = _ray_leaf(o[r], d[r], lo[r], hi[r], tri, usable, dtype)
+            has = acc.any(1)
+            hit[r], face[r], at[r] = has, np.where(has, fm, -1), col
+    t, bary, point = _ray_result(o, d, tri, at, hit, ok, dtype)
+    return hit, t, face, bary, point
+
+
+def _ray_slab_skip(o, d, inv, slack, row, t_lo, t_max):
+    """The skip test of ia_ray_mesh_tree for rays [n] at one box row (lo.xyz, 0, hi.xyz, 0), in the dtype of the arrays."""
+    one = o.dtype.type
+    tiny = one(_RAY_TINY)
+    near, far = np.full(o.shape[0], -np.inf, dtype=o.dtype), np.full(o.shape[0], np.inf, dtype=o.dtype)
+    for k in range(3):
+        t0, t1 = ((row[k] - o[:, k]) - slack) * inv[:, k], ((row[4 + k] - o[:, k]) + slack) * inv[:, k]
+        free = np.isnan(t0) | np.isnan(t1) | ((d[:, k] != 0) & np.isinf(inv[:, k])) | (np.minimum(np.minimum(np.abs(t0), np.abs(t1)), np.abs(inv[:, k])) < tiny)
+        t0, t1 = np.where(free, -np.inf, t0).astype(o.dtype), np.where(free, np.inf, t1).astype(o.dtype)
+        near, far = np.maximum(near, np.minimum(t0, t1)), np.minimum(far, np.maximum(t0, t1))
+    near = near * np.where(near > 0, one(_RAY_IN), one(_RAY_OUT))
+    far = far * np.where(far > 0, one(_RAY_OUT), one(_RAY_IN))
+    return (near > far) | (near > t_max) | (far < t_lo)
+
+
+def _ray_tree_numpy(origins, dirs, tree, t_min=0.0, t_max=np.inf, mode='first', dtype=np.float64):
+    """NumPy restatement of ia_ray_mesh_tree in ``dtype`` on a host ``WindingTree``: ``(hit, t, face int32, bary, point, counts int64
+    [N,2] = boxes tested, ray-triangle pairs of the leaves entered)``.  Depth first from the root, children in index order; ``best =
+    (t, face)`` is ordered lexicographically and starts at ``(+inf, -1)``; an entered leaf evaluates ``_ray_tri`` for its faces and
+    keeps the smaller accepted pair.  A node is skipped iff the slab test on its box, grown by ``slack = 2^-12 M``
+    with ``M = max(|o|_inf, tree.extent)``, leaves no t in ``[t_lo, min(t_hi, best.t)]`` (``_ray_slab_skip``; any NaN enters).  With
+    ``mode='any'`` a ray that has a hit tests nothing more, and everything but ``hit`` and ``counts`` is what no hit gives.  The
+    result equals ``_ray_mesh_numpy`` in the same ``dtype``: the tree only prunes (DESIGN.md 4.28 states on what that rests)."""
+    if tree.device is not None:
+        raise ValueError('_ray_tree_numpy restates the query on a host WindingTree')
+    any_hit = _ray_mode(mode) == 'any'
+    o32, d32, lo32, hi32, ok = _ray_rows(origins, dirs, t_min, t_max)
+    o, d, lo, hi = (x.astype(dtype) for x in (o32, d32, lo32, hi32))
+    tris = np.asarray(tree.tris, dtype=F32).reshape(-1, 3, 3).astype(dtype)
+    order = np.asarray(tree.order, dtype=np.int64)
+    counts, boxes = list(tree.counts), np.asarray(tree.boxes, dtype=F32).astype(dtype)
+    n, fu = o.shape[0], tris.shape[0]
+    best_t, best_f, best_at = np.full(n, np.inf, dtype=dtype), np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    n_box, n_pair = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore', divide='ignore'):
+        ext = dtype(tree.extent)
+        big = np.maximum(np.abs(o).max(1) if n else np.zeros(0, dtype=dtype), ext)
+        slack = (dtype(_RAY_SLACK) * big).astype(dtype)
+        inv = (dtype(1) / d).astype(dtype)
+
+        def visit(lvl, j, at, idx):
+            if any_hit:
+                idx = idx[best_f[idx] < 0]
+            n_box[idx] += 1
+            skip = _ray_slab_skip(o[idx], d[idx], inv[idx], slack[idx], boxes[at], lo[idx], np.minimum(hi[idx], best_t[idx]))
+            r = idx[~skip]
+            if lvl == 0 and r.size:
+                sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, fu))
+                acc, tm, fm, col = _ray_leaf(o[r], d[r], lo[r], hi[r], tris[sl], order[sl], dtype)
+                take = acc.any(1) & ((tm < best_t[r]) | ((tm == best_t[r]) & (fm < best_f[r])))
+                rr = r[take]
+                best_t[rr], best_f[rr], best_at[rr] = tm[take], fm[take], sl.start + col[take]
+                n_pair[r] += sl.stop - sl.start
+            return r
+
+        _tree_walk(counts, np.flatnonzero(ok), visit)
+    hit = best_f >= 0
+    if any_hit:
+        hit, best_f = hit.copy(), np.full(n, -1, dtype=np.int64)
+        t, bary, point = _ray_result(o, d, tris, best_at, np.zeros(n, dtype=bool), ok, dtype)
+    else:
+        t, bary, point = _ray_result(o, d, tris, best_at, hit, ok, dtype)
+    return hit, t, best_f.astype(np.int32), bary, point, np.stack([n_box, n_pair], -1)
+
+
+def _ao_table(samples, seed):
+    """``samples`` cosine-weighted directions of the upper hemisphere (z up), float32 [S,3]: made in float64 from ``seed``
+    (``r = sqrt(u1)``, ``phi = 2 pi u2``, ``(r cos phi, r sin phi, sqrt(1 - u1))``) and cast once."""
+    samples = int(samples)
+    if samples < 1 or samples > 65536:
+        raise ValueError(f'samples must be in [1, 65536], got {samples}')
+    u = np.random.RandomState(int(seed)).random_sample((samples, 2))
+    r, phi = np.sqrt(u[:, 0]), 2.0 * np.pi * u[:, 1]
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u[:, 0])], -1).astype(F32)
+
+
+def _ao_rays_numpy(verts, normals, table, bias):
+    """NumPy restatement of ia_ao_rays in float32: ``(origins, dirs)`` float32 [V S, 3], ray ``v S + s``: origin ``v + bias n``,
+    direction ``(t1 x + t2 y) + n z`` per component for the table's ``(x, y, z)`` with the branch-free basis of Duff et al. (2017):
+    ``sign = copysign(1, n.z)``, ``a = -1 / (sign + n.z)``, ``b = (n.x n.y) a``, ``t1 = (1 + ((sign n.x) n.x) a, sign b, -(sign
+    n.x))``, ``t2 = (b, sign + (n.y n.y) a, -n.y)``.  A non-finite normal gives NaN rays."""
+    p, n, c = (np.asarray(x, dtype=F32).reshape(-1, 3) for x in (verts, normals, table))
+    bias = F32(bias)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore', divide='ignore'):
+        sign = np.copysign(F32(1), n[:, 2])
+        a = F32(-1) / (sign + n[:, 2])
+        b = (n[:, 0] * n[:, 1]) * a
+        sx = sign * n[:, 0]
+        t1 = np.stack([F32(1) + (sx * n[:, 0]) * a, sign * b, -sx], -1)[:, None, :]
+        t2 = np.stack([b, sign + (n[:, 1] * n[:, 1]) * a, -n[:, 1]], -1)[:, None, :]
+        nn = n[:, None, :]
+        dirs = (t1 * c[None, :, 0:1] + t2 * c[None, :, 1:2]) + nn * c[None, :, 2:3]
+        origins = np.broadcast_to((p + bias * n)[:, None, :], dirs.shape)
+        bad = ~np.isfinite(n).all(1)
+        origins, dirs = np.where(bad[:, None, None], F32(np.nan), origins), np.where(bad[:, None, None], F32(np.nan), dirs)
+    return origins.reshape(-1, 3).astype(F32), dirs.reshape(-1, 3).astype(F32)
+
+
 class WindingTree:
     """The cluster tree of one mesh for ``winding_number(method='tree')``, built once: ``order`` (sorted position -> input face: the
     usable faces by the 30-bit Morton key of their centroid, ties by face index, then the unusable ones), ``tris`` (the triangles in
@@ -1697,16 +1905,17 @@ class WindingTree:
         """The tree of the mesh of a ``TriangleGrid``, from its packed triangles."""
         return cls(None, None, grid=grid)
 
-    def _sorted(self, points, sort, fn):
-        """``list(fn(hipops, pts))`` for device points as float32 [N,3], Morton-sorted if ``sort`` and N > 64; unsorted on return."""
+    def _sorted(self, points, sort, fn, *rows):
+        """``list(fn(hipops, pts, *rows))`` for device points as float32 [N,3], Morton-sorted if ``sort`` and N > 64; unsorted on
+        return.  ``rows``: device tensors with one row per point, taken along in the points' order."""
         from . import hipops
         pts = torch.as_tensor(points).detach().to(self.device).float().reshape(-1, 3).contiguous()
         if not (sort and pts.shape[0] > 64):
-            return list(fn(hipops, pts))
+            return list(fn(hipops, pts, *rows))
         perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
         back = torch.empty_like(perm)
         back[perm] = torch.arange(perm.numel(), device=perm.device)
-        return [None if x is None else x[back] for x in fn(hipops, pts[perm].contiguous())]
+        return [None if x is None else x[back] for x in fn(hipops, pts[perm].contiguous(), *[x[perm].contiguous() for x in rows])]
 
     def query(self, points, beta=2.0, return_bound=False, return_counts=False, sort=True):
         """Winding numbers float64 [...] of points [..., 3]; with ``return_bound`` also the truncation bound, with ``return_counts``
@@ -1763,6 +1972,60 @@ class WindingTree:
                    'point': _as_out(point.reshape(lead + (3,)), points)}
             if return_counts:
                 out['counts'] = _as_out(cnt.reshape(lead + (2,)), points, np.int64)
+        return out
+
+    def _ray_rows_device(self, origins, dirs, t_min, t_max):
+        o = torch.as_tensor(origins).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        d = torch.as_tensor(dirs).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        if o.shape != d.shape:
+            raise ValueError(f'origins and dirs must have the same shape, got {tuple(o.shape)} and {tuple(d.shape)}')
+        ends = [torch.as_tensor(x, dtype=torch.float32).to(self.device).reshape(-1).expand(o.shape[0]).contiguous() for x in (t_min, t_max)]
+        if self._order32 is None:
+            self._order32 = self.order.int().contiguous()
+        return o, d, ends[0], ends[1]
+
+    def rays(self, origins, dirs, t_min=0.0, t_max=float('inf'), mode='first', return_counts=False, sort=True, brute=False):
+        """Rays ``origins + t dirs`` [..., 3] against the mesh, ``t_min <= t <= t_max`` (scalars or per-ray arrays [...]):
+        ``mode='first'`` -> ``{'hit' bool, 't', 'face' int64, 'bary' [..., 3], 'point' [..., 3]}`` of the first hit, the smallest pair
+        (t, input face index) over the triangles that ``_ray_tri`` accepts (``_ray_mesh_numpy`` is the definition; +inf / -1 / NaN /
+        NaN without one, NaN / -1 / NaN / NaN for a ray with a non-finite origin or direction or a NaN interval end);
+        ``mode='any'`` -> ``{'hit'}``.  The tree only prunes.  With ``return_counts`` also ``'counts'`` int [..., 2] (boxes tested,
+        ray-triangle pairs of the leaves entered).  ``sort`` (device): query in Morton order of the origins and return in the
+        caller's order; it changes no result.  ``brute``: every ray against every usable triangle instead, on host and device (no counts; what
+        ``ray_mesh(brute=True)`` takes on the device).  A host tree answers in float64.  The per-triangle test is not watertight: a ray aimed at a shared edge or vertex can miss both neighbours."""
+        any_hit = _ray_mode(mode) == 'any'
+        lead = tuple(origins.shape[:-1])
+        if self.device is not None:
+            o, d, lo, hi = self._ray_rows_device(origins, dirs, t_min, t_max)
+            if brute:
+                def run(hipops, o, d, lo, hi):
+                    return hipops.ray_mesh_brute(o, d, lo, hi, self.tris, self._order32, self.usable, any_hit=any_hit) + (None,)
+            else:
+                def run(hipops, o, d, lo, hi):
+                    return hipops.ray_mesh_tree(o, d, lo, hi, self.tris, self._order32, self.boxes, self.usable, self.extent, any_hit=any_hit,
+                                                counts=return_counts)
+            hit, t, face, bary, point, cnt = self._sorted(o, sort and not brute, run, d, lo, hi)
+            out = {'hit': hit.reshape(lead)}
+            if not any_hit:
+                out.update(t=t.reshape(lead), face=face.long().reshape(lead), bary=bary.reshape(lead + (3,)), point=point.reshape(lead + (3,)))
+            if return_counts and not brute:
+                out['counts'] = cnt.reshape(lead + (2,))
+        else:
+            if brute:                                                                  # the usable triangles in input order
+                order = np.asarray(self.order, dtype=np.int64)[:self.usable]
+                back = np.argsort(order)
+                tri = np.asarray(self.tris, dtype=F32).reshape(-1, 3, 3)[back]
+                hit, t, face, bary, point = _ray_mesh_numpy(_np(origins), _np(dirs), tri.reshape(-1, 3), np.arange(3 * back.size).reshape(-1, 3),
+                                                            _np(t_min), _np(t_max))
+                face, cnt = np.where(hit, order[back][np.maximum(face, 0)], -1), None
+            else:
+                hit, t, face, bary, point, cnt = _ray_tree_numpy(_np(origins), _np(dirs), self, _np(t_min), _np(t_max), mode)
+            out = {'hit': _as_out(hit.reshape(lead), origins, bool)}
+            if not any_hit:
+                out.update(t=_as_out(t.reshape(lead), origins), face=_as_out(face.reshape(lead), origins, np.int64),
+                           bary=_as_out(bary.reshape(lead + (3,)), origins), point=_as_out(point.reshape(lead + (3,)), origins))
+            if return_counts and not brute:
+                out['counts'] = _as_out(cnt.reshape(lead + (2,)), origins, np.int64)
         return out
 
 
@@ -1832,6 +2095,81 @@ def signed_distance(points, verts, faces, grid=None, threshold=0.5, method='exac
     neg = w >= threshold
     sdf = torch.where(neg, -r['dist'], r['dist']) if isinstance(neg, torch.Tensor) else np.where(neg, -r['dist'], r['dist'])
     return {'sdf': sdf, 'dist': r['dist'], 'face': r['face'], 'point': r['point'], 'winding': w}
+
+
+def ray_mesh(origins, dirs, verts, faces, t_min=0.0, t_max=float('inf'), mode='first', brute=False, tree=None):
+    """What the rays ``origins + t dirs`` [..., 3], ``t_min <= t <= t_max`` (scalars or per-ray arrays), hit on the triangle mesh
+    (verts float32 [V,3], faces [F,3]): ``{'hit' bool [...], 't' float32, 'face' int64, 'bary' [..., 3], 'point' [..., 3]}`` of the
+    first hit, the smallest pair (t, input face index) over the triangles ``_ray_tri`` accepts; ``mode='any'`` returns ``{'hit'}``
+    only and stops at the first triangle found.  ``dirs`` need not have unit length: ``t`` is in units of ``|dirs|``.  Both sides of a
+    triangle are hit; a triangle without area or with a non-finite vertex never is.  No hit: ``t = +inf``, ``face = -1``, NaN
+    ``bary`` and ``point``; a ray with a non-finite origin or direction or a NaN interval end: ``t = NaN`` as well.  The per-triangle
+    test is fp32 and not watertight: a ray aimed exactly at a shared edge or vertex can slip between the neighbours.  Device tensors
+    run on ia_ray_mesh_tree over a ``WindingTree`` (``tree``, or built here) or, with ``brute=True``, on ia_ray_mesh_brute: the same
+    bits.  CPU tensors and NumPy arrays take the NumPy restatements in float64."""
+    _mesh_args(verts, faces)
+    _ray_mode(mode)
+    if _is_device(verts) or not brute:
+        return _winding_tree_for(verts, faces, None, tree).rays(origins, dirs, t_min, t_max, mode=mode, brute=brute)
+    lead = tuple(origins.shape[:-1])
+    hit, t, face, bary, point = _ray_mesh_numpy(_np(origins), _np(dirs), _np(verts), _np(faces), _np(t_min), _np(t_max))
+    out = {'hit': _as_out(hit.reshape(lead), origins, bool)}
+    if mode == 'first':
+        out.update(t=_as_out(t.reshape(lead), origins), face=_as_out(face.reshape(lead), origins, np.int64),
+                   bary=_as_out(bary.reshape(lead + (3,)), origins), point=_as_out(point.reshape(lead + (3,)), origins))
+    return out
+
+
+def occluded(a, b, verts, faces, margin=1e-4, tree=None):
+    """bool [...]: does the mesh meet the segment from ``a`` to ``b`` [..., 3] strictly between its ends?  ``ray_mesh(a, b - a,
+    t_min=margin, t_max=1 - margin, mode='any')['hit']`` with ``b - a`` in float32: ``margin`` (a fraction of the segment) keeps a
+    surface that an end lies on from counting."""
+    if isinstance(a, torch.Tensor):
+        d = torch.as_tensor(b).to(a.device).float() - a.float()
+    else:
+        d = np.asarray(_np(b), dtype=F32) - np.asarray(a, dtype=F32)
+    return ray_mesh(a, d, verts, faces, t_min=margin, t_max=1.0 - margin, mode='any', tree=tree)['hit']
+
+
+def ambient_occlusion(verts, faces, samples=64, radius=None, bias=None, normals=None, seed=0, tree=None):
+    """Ambient occlusion per vertex: ``{'ao' float32 [V], 'unoccluded' int32 [V], 'samples'}`` with ``ao = unoccluded / samples``,
+    the share of ``samples`` cosine-weighted directions of the hemisphere about the vertex normal along which nothing of the mesh
+    lies within ``radius`` (None: no limit).  The directions are one table for all vertices (``_ao_table(samples, seed)``, float64
+    cast to float32), turned into the frame of each normal (``_ao_rays_numpy``); the rays start at ``v + bias n`` (``bias`` None:
+    ``2^-12`` times the largest |coordinate| of the mesh) and are any-hit queries on the tree.  ``normals``: unit vertex normals
+    (None: ``mesh_normals(weighting='area')``).  A vertex with a non-finite position or normal counts as unoccluded.  The counts are
+    integer sums: the same from run to run, and the host route (the float32 restatements) gives the device's integers.  At most
+    about 2^22 rays are alive at once."""
+    _mesh_args(verts, faces)
+    table = _ao_table(samples, seed)
+    s = table.shape[0]
+    tree = _winding_tree_for(verts, faces, None, tree)
+    bias = float(F32(2.0 ** -12) * F32(tree.extent)) if bias is None else float(bias)
+    t_max = float('inf') if radius is None else float(radius)
+    if normals is None:
+        normals = mesh_normals(verts, faces, weighting='area')
+    if tuple(normals.shape) != tuple(verts.shape):
+        raise ValueError(f'normals must be [V,3] like verts, got {tuple(normals.shape)}')
+    nv = verts.shape[0]
+    step = max(1, _AO_MAX_RAYS // s)
+    if tree.device is not None:
+        from . import hipops
+        v = verts.detach().to(tree.device).float().contiguous()
+        n = torch.as_tensor(normals).detach().to(tree.device).float().contiguous()
+        tab = torch.from_numpy(table).to(tree.device)
+        free = torch.empty(nv, dtype=torch.int32, device=tree.device)
+        for at in range(0, nv, step):
+            o, d = hipops.ao_rays(v[at:at + step].contiguous(), n[at:at + step].contiguous(), tab, bias)
+            hit = tree.rays(o, d, 0.0, t_max, mode='any')['hit']
+            free[at:at + step] = (s - hit.view(-1, s).sum(1)).int()
+        return {'ao': free.float() / float(s), 'unoccluded': free, 'samples': s}
+    v, n = np.asarray(_np(verts), dtype=F32), np.asarray(_np(normals), dtype=F32)
+    free = np.zeros(nv, dtype=np.int32)
+    for at in range(0, nv, step):
+        o, d = _ao_rays_numpy(v[at:at + step], n[at:at + step], table, bias)
+        hit = _ray_tree_numpy(o, d, tree, 0.0, t_max, 'any', dtype=F32)[0]
+        free[at:at + step] = s - hit.reshape(-1, s).sum(1)
+    return {'ao': _as_out(free.astype(F32) / F32(s), verts), 'unoccluded': _as_out(free, verts, np.int32), 'samples': s}
 
 
 def _finite_box(*vert_sets):

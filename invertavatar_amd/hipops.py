@@ -1965,6 +1965,79 @@ def closest_point_tree(points, sorted_tris, order, boxes, n_usable, mesh_extent,
     return dist, face, point, cnt
 
 
+# ------------------------------------------------------------------ rays against the mesh on the tree (csrc/ray_tree.hip)
+
+def _ray_args(origins, dirs, t_lo, t_hi, sorted_tris, order, n_usable):
+    for x, name in ((origins, 'origins'), (dirs, 'dirs'), (t_lo, 't_lo'), (t_hi, 't_hi')):
+        _f32c(x, name)
+    _tris_checked(sorted_tris)
+    _i32c(order, 'order')
+    dev, n = origins.device, origins.shape[0]
+    if origins.dim() != 2 or origins.shape[1] != 3 or tuple(dirs.shape) != (n, 3) or tuple(t_lo.shape) != (n,) or tuple(t_hi.shape) != (n,):
+        raise RuntimeError(f'origins and dirs must be [N,3], t_lo and t_hi [N], got {tuple(origins.shape)}, {tuple(dirs.shape)}, '
+                           f'{tuple(t_lo.shape)}, {tuple(t_hi.shape)}')
+    if any(t.device != dev for t in (dirs, t_lo, t_hi, sorted_tris, order)):
+        raise RuntimeError(f'the rays must be on the device of the tree, got {dev}')
+    if not 0 <= int(n_usable) <= min(sorted_tris.shape[0], order.numel()):
+        raise RuntimeError(f'n_usable must be within the triangles and the order, got {n_usable}')
+    return dev, n
+
+
+def _ray_outputs(n, dev, any_hit):
+    hit = torch.empty(n, dtype=torch.uint8, device=dev)
+    if any_hit:
+        return hit, None, None, None, None
+    return (hit, torch.empty(n, device=dev), torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, 3, device=dev),
+            torch.empty(n, 3, device=dev))
+
+
+def ray_mesh_brute(origins, dirs, t_lo, t_hi, sorted_tris, order, n_usable, any_hit=False):
+    """Every ray against every usable triangle (see ia_ray_mesh_brute): origins, dirs float32 [N,3], t_lo, t_hi float32 [N],
+    ``sorted_tris`` / ``n_usable`` from ``winding_tree_build``, ``order`` int32 -> (hit bool [N], t [N], face int32 [N]: input face
+    indices, bary [N,3], point [N,3]); with ``any_hit`` everything but ``hit`` is None."""
+    dev, n = _ray_args(origins, dirs, t_lo, t_hi, sorted_tris, order, n_usable)
+    hit, t, face, bary, point = _ray_outputs(n, dev, any_hit)
+    with torch.cuda.device(dev), _Timed('ray_mesh_brute', 0.0, 64.0 * n, f'N={n} F={int(n_usable)} any={int(any_hit)}'):
+        st = _lib.load().ia_ray_mesh_brute(_p(origins), _p(dirs), _p(t_lo), _p(t_hi), n, _p(sorted_tris), _p(order), int(n_usable), int(any_hit),
+                                           _p(hit), _p(t), _p(face), _p(bary), _p(point), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_ray_mesh_brute')
+    return hit.bool(), t, face, bary, point
+
+
+def ray_mesh_tree(origins, dirs, t_lo, t_hi, sorted_tris, order, boxes, n_usable, mesh_extent, any_hit=False, counts=False):
+    """The same through the tree (see ia_ray_mesh_tree): ``boxes`` from ``tree_boxes`` -> (hit, t, face, bary, point, counts int32
+    [N,2] or None)."""
+    dev, n = _ray_args(origins, dirs, t_lo, t_hi, sorted_tris, order, n_usable)
+    _f32c(boxes, 'boxes')
+    if boxes.dim() != 2 or boxes.shape[1] != TREE_BOX_ROW or boxes.device != dev:
+        raise RuntimeError(f'boxes must be [n,{TREE_BOX_ROW}] on the device of the rays, got {tuple(boxes.shape)} on {boxes.device}')
+    hit, t, face, bary, point = _ray_outputs(n, dev, any_hit)
+    cnt = torch.empty(n, 2, dtype=torch.int32, device=dev) if counts else None
+    with torch.cuda.device(dev), _Timed('ray_mesh_tree', 0.0, 64.0 * n, f'N={n} F={int(n_usable)} any={int(any_hit)}'):
+        st = _lib.load().ia_ray_mesh_tree(_p(origins), _p(dirs), _p(t_lo), _p(t_hi), n, _p(sorted_tris), _p(order), int(n_usable), _p(boxes),
+                                          boxes.shape[0], float(mesh_extent), int(any_hit), _p(hit), _p(t), _p(face), _p(bary), _p(point),
+                                          _p(cnt), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_ray_mesh_tree')
+    return hit.bool(), t, face, bary, point, cnt
+
+
+def ao_rays(verts, normals, table, bias):
+    """The rays of the ambient-occlusion estimate (see ia_ao_rays): verts, normals float32 [V,3], table float32 [S,3] -> (origins,
+    dirs) float32 [V S, 3], ray v S + s."""
+    for x, name in ((verts, 'verts'), (normals, 'normals'), (table, 'table')):
+        _f32c(x, name)
+    dev, v, s = verts.device, verts.shape[0], table.shape[0]
+    if verts.dim() != 2 or verts.shape[1] != 3 or tuple(normals.shape) != (v, 3) or table.dim() != 2 or table.shape[1] != 3:
+        raise RuntimeError(f'verts and normals must be [V,3] and table [S,3], got {tuple(verts.shape)}, {tuple(normals.shape)}, {tuple(table.shape)}')
+    if normals.device != dev or table.device != dev:
+        raise RuntimeError(f'normals and table must be on the device of verts, got {normals.device} and {table.device}')
+    origins, dirs = torch.empty(v * s, 3, device=dev), torch.empty(v * s, 3, device=dev)
+    with torch.cuda.device(dev), _Timed('ao_rays', 0.0, 24.0 * v + 24.0 * v * s, f'V={v} S={s}'):
+        st = _lib.load().ia_ao_rays(_p(verts), _p(normals), v, _p(table), s, float(bias), _p(origins), _p(dirs), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_ao_rays')
+    return origins, dirs
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

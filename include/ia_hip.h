@@ -1398,6 +1398,41 @@ int ia_cx_cols(const float* xh, const float* yh, const float* m, const double* s
                double* colmax, void* stream);
 int ia_cx_finish(const double* colmax, int N, int64_t P, float* cx, float* cx_loss, void* stream);
 
+/* ---- non-rigid fitting of a template mesh (csrc/nonrigid.hip; the definition is geometry.nonrigid_align) ----
+ * The unknown is one displacement d_i (double) per template vertex x_i (float32 [V,3]); V <= 2^28.
+ * ia_nonrigid_terms: the terms of one pairing.  p = fl32(x + d), (dist, face, q) its closest points on the target.  Pair i counts iff
+ * dist[i] is finite, face[i] >= 0, dist[i] <= h_max_dist (fp32; +inf: none), pinned[i] == 0, for mode 1 (plane) or use_cos face[i] < Fb
+ * with a finite non-zero normal in face_normals [Fb,3], and with use_cos source_normals[i] finite, non-zero and
+ * source_normals[i] . face_normals[face[i]] >= normal_cos (in double).  Writes c [V] (1 | 0), n [V,3] (the face normal for a counting
+ * pair of mode 1, else 0) and b [V,3] = c (q - x) (mode 0) or c (n (n . (q - x)) + point_share (q - x)) (mode 1), plus beta[i] land[i]
+ * where beta (double [V], or NULL) is not 0 and the vertex not pinned; out[0] = sum c |p - q|^2, out[1] = sum c, in double: per
+ * workgroup of 256 vertices the butterfly per wave and the waves in order, the workgroups by a second launch in one fixed order.
+ * scratch: ia_nonrigid_terms_scratch_bytes(V) bytes.
+ * ia_nonrigid_rhs: b from weights c [V], offsets t [V,3], normals n [V,3] (NULL: point), beta / land (or NULL) by the same formulas
+ * (an offset with weight 0 is not read into b; pinned rows are 0).
+ * ia_nonrigid_solve: conjugate gradients in double on (C + a L + B) x = b from x (in / out, [V,3]; 0 at pinned vertices), for exactly
+ * cg_iterations steps of three launches each (four with heavy vertices), no host synchronisation: (L x)_i = deg_i x_i - sum_j x_j over
+ * the CSR row (offsets [V+1], neighbors [E]) in ascending j, vertices of degree > 64 (heavy [n_heavy]) by one wave each; C_i = c_i I
+ * (n NULL) or c_i (n_i n_i^T + point_share I); B_i = beta_i I; pinned rows and columns are taken out.  Once |r|^2 <= cg_tol^2 |b|^2, or
+ * p.Ap <= 0, or a scalar is not finite, every later step changes nothing.  out [5] (device): the energy 1/2 x.Ax - b.x at the start and
+ * at the end, the steps taken, |r| / |b|, the freeze flag.  Dot products are per-workgroup partials added again by every workgroup of
+ * the next launch in one fixed order: no floating-point atomics, bit-equal run to run.  scratch: ia_nonrigid_solve_scratch_bytes(V).
+ * ia_nonrigid_apply: verts[i] = x[i] where pinned or d[i] == 0 (per coordinate), else fl32(x[i] + d[i]).
+ */
+int ia_nonrigid_terms_scratch_bytes(int64_t V, size_t* h_bytes);
+int ia_nonrigid_terms(const float* x, const float* p, const float* q, const float* dist, const int* face, int64_t V,
+                      const float* face_normals, int64_t Fb, const float* source_normals, float h_max_dist, int mode, int use_cos,
+                      double normal_cos, double point_share, const unsigned char* pinned, const double* beta, const double* land,
+                      double* c, double* n, double* b, void* scratch, size_t scratch_bytes, double* out, void* stream);
+int ia_nonrigid_rhs(int64_t V, const double* c, const double* t, const double* n, double point_share, const double* beta,
+                    const double* land, const unsigned char* pinned, double* b, void* stream);
+int ia_nonrigid_solve_scratch_bytes(int64_t V, size_t* h_bytes);
+int ia_nonrigid_solve(int64_t V, const int* offsets, const int* neighbors, int64_t E, const int* heavy, int n_heavy, const double* c,
+                      const double* n, const double* beta, const unsigned char* pinned, const double* b, double stiffness,
+                      double point_share, double* x, int cg_iterations, double cg_tol, void* scratch, size_t scratch_bytes,
+                      double* out, void* stream);
+int ia_nonrigid_apply(const float* x, const double* d, const unsigned char* pinned, int64_t V, float* verts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,14 @@ _SIGNATURES = {
     'ia_cx_rows': [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p],
     'ia_cx_cols': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_void_p],
     'ia_cx_finish': [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p],
+    'ia_nonrigid_terms_scratch_bytes': [c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_nonrigid_terms': [c_void_p] * 5 + [c_int64, c_void_p, c_int64, c_void_p, c_float, c_int, c_int, ctypes.c_double, ctypes.c_double] +
+                         [c_void_p] * 7 + [ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_nonrigid_rhs': [c_int64, c_void_p, c_void_p, c_void_p, ctypes.c_double] + [c_void_p] * 5,
+    'ia_nonrigid_solve_scratch_bytes': [c_int64, ctypes.POINTER(ctypes.c_size_t)],
+    'ia_nonrigid_solve': [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int] + [c_void_p] * 5 + [ctypes.c_double, ctypes.c_double, c_void_p,
+                         c_int, ctypes.c_double, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_nonrigid_apply': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
 }
 
 

@@ -32,7 +32,12 @@ the FINAL mesh into a SIZE^2 texture atlas (``geometry.TextureAtlas``) and write
 ``--texture-source decoder`` (default) queries the decoder at every texel, ``views`` projects ``--texture-views`` rendered images of the
 orbit onto the mesh (``--texture-mode blend|best``) with the decoder bake as the fallback; with ``--mesh-views`` the mesh is also rendered
 through the texture (``seed%04d_meshtex%02d.png``); a line per seed reports the block side, the share of filled texels and the views per
-texel.  Runs on the device when there is one."""
+texel.  ``--fit-template T.ply`` wraps the template mesh ``T.ply`` onto the FINAL mesh of every seed (``geometry.nonrigid_align``;
+``--fit-align rigid|similarity`` first moves it there with ``geometry.align_mesh`` from the centroids; ``--fit-metric``, ``--fit-stiffness``,
+``--fit-iterations`` and ``--fit-normal-cos`` as in ``geometry_metrics``) and writes ``seed%04d_template.ply``: the template's own faces on
+the avatar's shape, so every seed has the same topology, with colours queried at the fitted vertices unless ``--no-colors``; a line per
+seed reports the template's vertices, the rms before and after, the inliers and the largest displacement, and ``seed%04d_geometry.json``
+gains a ``template`` block.  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -122,6 +127,9 @@ def main(argv=None):
     ap.add_argument('--texture-source', default='decoder', choices=['decoder', 'views'], help='colours from the decoder, or projected from rendered views')
     ap.add_argument('--texture-views', type=int, default=8, help='with --texture-source views: the number of views of the yaw orbit')
     ap.add_argument('--texture-mode', default='blend', choices=['blend', 'best'], help='with --texture-source views: blend the views or take the best')
+    ap.add_argument('--fit-template', default=None, metavar='T.ply', help='wrap this template mesh onto the final mesh; writes _template.ply')
+    ap.add_argument('--fit-align', default=None, choices=geometry_metrics.ALIGN_MODES, help='with --fit-template: align the template first (from the centroids)')
+    geometry_metrics.add_fit_arguments(ap, flag=False)
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     G = build_generator(args.network, args.width, device=args.device)
@@ -143,6 +151,13 @@ def main(argv=None):
     texture = {}
     if args.texture is not None:
         texture = {'texture': {'size': args.texture, 'source': args.texture_source, 'n_views': args.texture_views, 'mode': args.texture_mode}}
+    if args.fit_align and not args.fit_template:
+        ap.error('--fit-align needs --fit-template')
+    if args.fit_template:
+        tv, tf, _ = geometry.read_ply(args.fit_template)
+        texture['fit_template'] = {'verts': torch.from_numpy(tv).to(args.device), 'faces': torch.from_numpy(tf).to(args.device),
+                                   **({'align': args.fit_align} if args.fit_align else {}), **geometry_metrics.fit_options_of(args),
+                                   **({'search': args.search} if args.search != 'grid' else {})}
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,
                                  with_normals=args.normals, keep=args.keep, min_voxels=args.min_voxels, simplify=simplify, smooth=smooth, noise_mode='const',
@@ -237,6 +252,22 @@ def main(argv=None):
             with open(gpath, 'w') as fh:
                 json.dump(dict(meta, ambient_occlusion=out['ambient_occlusion']), fh, indent=1)
             print(f'seed {seed}: ambient occlusion with {ao["samples"]} samples per vertex, mean {out["ambient_occlusion"]["mean"]:.4f} -> {apath}')
+        if 'template' in out:
+            tpl = out['template']
+            tpath = os.path.join(args.outdir, f'seed{seed:04d}_template.ply')
+            geometry.write_ply(tpath, tpl['verts'], tpl['faces'], tpl.get('colors'))
+            block = geometry_metrics.nonrigid_block(tpl['fit'])
+            if 'alignment' in tpl:
+                block['alignment'] = geometry_metrics.alignment_block(tpl['alignment'])
+            gpath = os.path.join(args.outdir, f'seed{seed:04d}_geometry.json')
+            meta = {}
+            if os.path.exists(gpath) and any(k in out for k in ('simplify', 'smooth', 'metrics', 'ambient_occlusion')):
+                with open(gpath) as fh:
+                    meta = json.load(fh)
+            with open(gpath, 'w') as fh:
+                json.dump(dict(meta, template=block), fh, indent=1)
+            what = f'template of {tpl["verts"].shape[0]} vertices'
+            print(f'seed {seed}: {geometry_metrics.nonrigid_summary(block, what)} -> {tpath}')
         if args.views > 0:
             from PIL import Image
             cams = orbit_cameras(G, args.views, device=args.device)[None]

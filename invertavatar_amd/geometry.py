@@ -2956,6 +2956,417 @@ def mesh_normals(verts, faces, weighting='area', adjacency=None):
     return _as_out(_mesh_normals_numpy(v, adj.faces, adj._state, weighting), verts)
 
 
+# ------------------------------------------------------------------ non-rigid fitting (csrc/nonrigid.hip)
+
+def _seq_sum(v, reverse=False):
+    """The sum of a float64 vector added in index order (``reverse``: from the last entry)."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if not v.size:
+        return np.float64(0.0)
+    return np.cumsum(v[::-1] if reverse else v)[-1]
+
+
+def _data_term(c, n, share, t):
+    """``C_i t_i`` per vertex: ``c t`` (point, ``n`` None) or ``c (n (n . t) + share t)`` (plane)."""
+    if n is None:
+        return c[:, None] * t
+    return c[:, None] * (n * _dot3(n, t)[:, None] + share * t)
+
+
+def _nonrigid_rhs_numpy(c, t, n, share, beta, land, pinned):
+    """``b = C t + B l``: an offset with weight 0 is not read, pinned rows are 0."""
+    with np.errstate(all='ignore'):
+        b = _data_term(c, n, share, np.where((c != 0)[:, None], t, 0.0))
+        if beta is not None:
+            use = (beta != 0)[:, None]
+            b = np.where(use, b + beta[:, None] * np.where(use, land, 0.0), b)
+    return np.where(pinned[:, None], 0.0, b)
+
+
+def _nonrigid_operator(adj, c, n, share, beta, pinned, a, reverse=False):
+    """``x -> (C + a L + B) x`` on float64 [V,3] with the pinned rows taken out; the neighbour sums in ascending j (``reverse``:
+    descending, for the restatement's own sensitivity to the order)."""
+    nv = c.shape[0]
+    row, nbr = adj['row'].astype(np.int64), adj['neighbors'].astype(np.int64)
+    if reverse:
+        row, nbr = row[::-1], nbr[::-1]
+    deg = np.diff(adj['offsets'].astype(np.int64)).astype(np.float64)[:, None]
+    bt = np.zeros(nv) if beta is None else beta
+    free = ~pinned[:, None]
+
+    def apply(x):
+        s = _segment_sums(row, x[nbr], nv) if nbr.size else np.zeros((nv, 3))
+        return np.where(free, (_data_term(c, n, share, x) + a * (deg * x - s)) + bt[:, None] * x, 0.0)
+    return apply
+
+
+def _nonrigid_cg_numpy(apply, b, x0, pinned, iterations, tol, reverse=False, trace=None):
+    """Plain conjugate gradients with the freeze rule of ``nonrigid_align`` -> (x, steps, |r| / |b|, energy at the start, at the end).
+    ``trace`` (a list) receives ``|r|^2 / |b|^2`` before the first step and after every step."""
+    def dot(u, v):
+        return _seq_sum(_dot3(u, v), reverse)
+    x = np.where(pinned[:, None], 0.0, x0)
+    ax = apply(x)
+    e0 = 0.5 * dot(x, ax) - dot(b, x)
+    r = b - ax
+    p = r.copy()
+    rr, bb, tol2 = dot(r, r), dot(b, b), np.float64(tol) * np.float64(tol)
+    steps = 0
+    with np.errstate(all='ignore'):
+        frozen = not np.isfinite(rr) or not np.isfinite(bb) or bool(rr <= tol2 * bb)
+        if trace is not None:
+            trace.append(float(rr / bb) if bb > 0 else 0.0)
+        for _ in range(iterations):
+            if frozen:
+                break
+            ap = apply(p)
+            pap = dot(p, ap)
+            alpha = rr / pap
+            if not pap > 0 or not np.isfinite(alpha):
+                break
+            x = x + alpha * p
+            r = r - alpha * ap
+            rr_new = dot(r, r)
+            p = r + (rr_new / rr) * p
+            rr = rr_new
+            steps += 1
+            if trace is not None:
+                trace.append(float(rr / bb))
+            frozen = not np.isfinite(rr) or bool(rr <= tol2 * bb)
+        e1 = 0.5 * dot(x, apply(x)) - dot(b, x)
+        res = float(np.sqrt(rr / bb)) if bb > 0 else 0.0
+    return x, steps, res, float(e0), float(e1)
+
+
+def _landmark_rows(landmarks, nv, what='position'):
+    """``(index int64 [K], rows float64 [K,3], weight float64 [K])`` of a landmark triple, checked."""
+    if not isinstance(landmarks, (tuple, list)) or len(landmarks) != 3:
+        raise ValueError(f'landmarks must be (index [K], {what} [K,3], weight), got {type(landmarks).__name__}')
+    idx = np.asarray(_np(landmarks[0]))
+    if idx.ndim != 1 or idx.dtype.kind not in 'iu':
+        raise ValueError(f'the landmark index must be integers [K], got {idx.dtype} {idx.shape}')
+    idx = idx.astype(np.int64)
+    rows = np.asarray(_np(landmarks[1]), dtype=np.float64)
+    if rows.shape != (idx.size, 3):
+        raise ValueError(f'the landmark {what} must be [{idx.size},3], got {rows.shape}')
+    w = np.asarray(_np(landmarks[2]), dtype=np.float64)
+    if w.ndim == 0:
+        w = np.full(idx.size, float(w))
+    if w.shape != (idx.size,):
+        raise ValueError(f'the landmark weight must be a scalar or [{idx.size}], got {w.shape}')
+    if idx.size and (idx.min() < 0 or idx.max() >= nv):
+        raise ValueError(f'landmark indices outside [0, {nv})')
+    if np.unique(idx).size != idx.size:
+        raise ValueError('a landmark index appears twice')
+    if not (np.isfinite(rows).all() and np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f'landmark {what}s and weights must be finite, the weights >= 0')
+    return idx, rows, w
+
+
+def _mask_checked(mask, nv, what):
+    if mask is None:
+        return None
+    if tuple(mask.shape) != (nv,):
+        raise ValueError(f'{what} must be a bool mask [{nv}], got {tuple(mask.shape)}')
+    return mask
+
+
+def _cg_args(cg_iterations, cg_tol):
+    if int(cg_iterations) < 1:
+        raise ValueError(f'cg_iterations must be >= 1, got {cg_iterations}')
+    if not (np.isfinite(cg_tol) and float(cg_tol) >= 0):
+        raise ValueError(f'cg_tol must be finite and >= 0, got {cg_tol}')
+    return int(cg_iterations), float(cg_tol)
+
+
+def nonrigid_solve(adjacency, weight, target_offset, stiffness, normals=None, point_share=0.1, pinned=None, x0=None, cg_iterations=100,
+                   cg_tol=1e-6, landmarks=None):
+    """The linear solve of ``nonrigid_align`` on its own: ``(C + a L + B) x = b`` for one displacement per vertex of ``adjacency`` (a
+    ``MeshAdjacency``), by ``cg_iterations`` steps of conjugate gradients in float64 from ``x0`` (0 if None).  ``weight`` [V] >= 0 is
+    c, ``target_offset`` [V,3] the offsets t the data term pulls to, ``stiffness`` the factor a of the uniform graph Laplacian
+    ``(L x)_i = deg_i x_i - sum_j x_j``; ``normals`` [V,3] (unit) selects the plane form ``C_i = c_i (n_i n_i^T + point_share I)``,
+    None the point form ``C_i = c_i I``; ``b_i = C_i t_i`` (plus ``w_k l_k`` for ``landmarks = (index [K], offset [K,3], weight)``,
+    which add ``w_k I`` to the diagonal).  ``pinned`` [V] (bool) vertices have x = 0 and leave the system.  See ``nonrigid_align`` for
+    the freeze rule.  Returns ``{'x' float64 [V,3], 'cg_steps', 'cg_residual' (|r| / |b|), 'energy_start', 'energy_end'}``, the
+    energies ``1/2 x.Ax - b.x`` before and after.  A device adjacency runs on ia_nonrigid_solve, the others on the NumPy restatement."""
+    nv = adjacency.n_verts
+    if tuple(weight.shape) != (nv,) or tuple(target_offset.shape) != (nv, 3):
+        raise ValueError(f'weight must be [{nv}] and target_offset [{nv},3], got {tuple(weight.shape)} and {tuple(target_offset.shape)}')
+    if normals is not None and tuple(normals.shape) != (nv, 3):
+        raise ValueError(f'normals must be [{nv},3], got {tuple(normals.shape)}')
+    if x0 is not None and tuple(x0.shape) != (nv, 3):
+        raise ValueError(f'x0 must be [{nv},3], got {tuple(x0.shape)}')
+    _mask_checked(pinned, nv, 'pinned')
+    if not (np.isfinite(stiffness) and float(stiffness) >= 0):
+        raise ValueError(f'stiffness must be finite and >= 0, got {stiffness}')
+    if normals is not None and not float(point_share) > 0:
+        raise ValueError(f'point_share must be > 0 with normals, got {point_share}')
+    cg_iterations, cg_tol = _cg_args(cg_iterations, cg_tol)
+    lm = None if landmarks is None else _landmark_rows(landmarks, nv, 'offset')
+    keys = ('energy_start', 'energy_end', 'cg_steps', 'cg_residual')
+    if adjacency.device:
+        from . import hipops
+        dev = adjacency.verts.device
+        f64 = lambda t: None if t is None else torch.as_tensor(t).to(device=dev, dtype=torch.float64).contiguous()      # noqa: E731
+        pin = torch.zeros(nv, dtype=torch.bool, device=dev) if pinned is None else torch.as_tensor(pinned).to(device=dev, dtype=torch.bool).contiguous()
+        beta = land = None
+        if lm is not None:
+            beta, land = torch.zeros(nv, dtype=torch.float64, device=dev), torch.zeros(nv, 3, dtype=torch.float64, device=dev)
+            beta[torch.as_tensor(lm[0], device=dev)] = f64(lm[2])
+            land[torch.as_tensor(lm[0], device=dev)] = f64(lm[1])
+        c, n = f64(weight), f64(normals)
+        b = hipops.nonrigid_rhs(c, f64(target_offset), pin, n, point_share, beta, land)
+        x, out = hipops.nonrigid_solve(adjacency._state, c, b, stiffness, pin, n, point_share, beta, f64(x0), cg_iterations, cg_tol)
+        e0, e1, steps, res = out.cpu().tolist()[:4]
+        return dict(zip(keys, (e0, e1, int(steps), res)), x=x)
+    c = np.asarray(_np(weight), dtype=np.float64)
+    n = None if normals is None else np.asarray(_np(normals), dtype=np.float64)
+    pin = np.zeros(nv, dtype=bool) if pinned is None else _np(pinned).astype(bool)
+    beta = land = None
+    if lm is not None:
+        beta, land = np.zeros(nv), np.zeros((nv, 3))
+        beta[lm[0]], land[lm[0]] = lm[2], lm[1]
+    b = _nonrigid_rhs_numpy(c, np.asarray(_np(target_offset), dtype=np.float64), n, float(point_share), beta, land, pin)
+    start = np.zeros((nv, 3)) if x0 is None else np.asarray(_np(x0), dtype=np.float64)
+    x, steps, res, e0, e1 = _nonrigid_cg_numpy(_nonrigid_operator(adjacency._state, c, n, float(point_share), beta, pin, float(stiffness)), b,
+                                               start, pin, cg_iterations, cg_tol)
+    return dict(zip(keys, (e0, e1, steps, res)), x=_as_out(x, weight, np.float64))
+
+
+def _moved_numpy(x, d, pinned):
+    """``fl32(x + d)``; the input bits where the vertex is pinned or the displacement is 0."""
+    with np.errstate(all='ignore'):
+        return np.where(pinned[:, None] | (d == 0), x, (x.astype(np.float64) + d).astype(F32))
+
+
+def _nonrigid_terms_numpy(x, p, q, dist, face, pinned, thr, metric, fnormals, snormals, normal_cos, share, beta, land):
+    """NumPy restatement of ia_nonrigid_terms -> (c [V], n [V,3] or None, b [V,3], sum c |p - q|^2, sum c)."""
+    nv = x.shape[0]
+    x64, p64, q64 = (np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in (x, p, q))
+    d, f = np.asarray(dist).astype(F32).reshape(-1), np.asarray(face).astype(np.int64).reshape(-1)
+    plane = metric == 'plane'
+    with np.errstate(all='ignore'):
+        ok = np.isfinite(d) & (f >= 0) & (d <= F32(thr)) & ~pinned
+        nf = np.zeros((nv, 3))
+        if plane or normal_cos is not None:
+            nrm = np.asarray(fnormals, dtype=F32).reshape(-1, 3)
+            ok &= f < nrm.shape[0]
+            nf = nrm[np.where(ok, f, 0)].astype(np.float64) if nrm.shape[0] else nf
+            ok &= np.isfinite(nf).all(1) & (nf != 0).any(1)
+        if normal_cos is not None:
+            ns = np.asarray(snormals, dtype=F32).astype(np.float64).reshape(-1, 3)
+            ok &= np.isfinite(ns).all(1) & (ns != 0).any(1)
+            ok &= _dot3(ns, np.where(ok[:, None], nf, 0.0)) >= float(normal_cos)
+        c = ok.astype(np.float64)
+        n = np.where(ok[:, None], nf, 0.0) if plane else None
+        b = _data_term(c, n, share, np.where(ok[:, None], q64 - x64, 0.0))
+        if beta is not None:
+            use = ((beta != 0) & ~pinned)[:, None]
+            b = np.where(use, b + beta[:, None] * np.where(use, land, 0.0), b)
+        e = np.where(ok[:, None], p64 - q64, 0.0)
+    return c, n, b, float(_seq_sum(_dot3(e, e))), int(np.count_nonzero(ok))
+
+
+def _nonrigid_loop(pair, solve, extent, schedule, iterations, tol):
+    """The levels and pairings of ``nonrigid_align`` around ``pair() -> (rms, inliers, terms)`` and ``solve(terms, a, level)``."""
+    hist, levels = [], []
+    for a in schedule:
+        lvl = {'stiffness': a, 'pairings': 0, 'cg_steps': [], 'cg_residual': []}
+        levels.append(lvl)
+        for k in range(iterations):
+            rms, _, terms = pair()
+            hist.append(rms)
+            lvl['pairings'] += 1
+            if rms <= EPS32 * extent or (k > 0 and abs(hist[-2] - rms) <= tol * hist[-2]):
+                break
+            solve(terms, a, lvl)
+    rms, n, _ = pair()
+    hist.append(rms)
+    return hist, levels, n
+
+
+def _rms(sq, n):
+    return float(np.sqrt(max(sq, 0.0) / n)) if n > 0 else 0.0
+
+
+def _nonrigid_numpy(x, adj, verts, faces, pinned, metric, schedule, iterations, tol, cg_iterations, cg_tol, share, max_dist, trim, normal_cos,
+                    beta, land, search='grid', dtype=np.float64):
+    """The NumPy restatement of ``nonrigid_align`` (the definition); ``dtype``: the precision of the closest-point search."""
+    fin = _finite_rows(verts)
+    if not faces.shape[0] or not fin.shape[0]:
+        raise ValueError('nonrigid_align: the target mesh is empty')
+    extent = float(max(np.abs(fin.min(0).astype(np.float64)).max(), np.abs(fin.max(0).astype(np.float64)).max()))
+    normals = face_normals(verts, faces) if metric == 'plane' or normal_cos is not None else None
+    tree = WindingTree(verts, faces) if search == 'tree' else None
+    state = {'d': np.zeros((x.shape[0], 3))}
+
+    def pair():
+        p = _moved_numpy(x, state['d'], pinned)
+        dist, face, q = _closest_numpy(p, verts, faces, dtype) if tree is None else _closest_tree_numpy(p, tree, dtype)[:3]
+        ns = _mesh_normals_numpy(p, adj.faces, adj._state, 'area') if normal_cos is not None else None
+        thr = _trim_threshold_numpy(dist, face, max_dist, trim)
+        c, n, b, sq, cnt = _nonrigid_terms_numpy(x, p, q, dist, face, pinned, thr, metric, normals, ns, normal_cos, share, beta, land)
+        return _rms(sq, cnt), cnt, (c, n, b)
+
+    def solve(terms, a, lvl):
+        c, n, b = terms
+        xs, steps, res, _, _ = _nonrigid_cg_numpy(_nonrigid_operator(adj._state, c, n, share, beta, pinned, a), b, state['d'], pinned,
+                                                  cg_iterations, cg_tol)
+        state['d'] = xs
+        lvl['cg_steps'].append(steps)
+        lvl['cg_residual'].append(res)
+    hist, levels, n = _nonrigid_loop(pair, solve, extent, schedule, iterations, tol)
+    return state['d'], hist, levels, n
+
+
+def _nonrigid_device(x, adj, verts, faces, pinned, metric, schedule, iterations, tol, cg_iterations, cg_tol, share, max_dist, trim, normal_cos,
+                     beta, land, grid, search, tree):
+    from . import hipops
+    if not faces.shape[0] or not verts.shape[0]:
+        raise ValueError('nonrigid_align: the target mesh is empty')
+    if grid is None:
+        grid = TriangleGrid(verts, faces, build=search != 'tree')
+    finder = grid if search != 'tree' else (tree if tree is not None else WindingTree.from_grid(grid))
+    normals = face_normals(grid.verts, grid.faces).float().contiguous() if metric == 'plane' or normal_cos is not None else None
+    base = float('inf') if max_dist is None else float(F32(max_dist))
+    state = {'d': torch.zeros(x.shape[0], 3, dtype=torch.float64, device=x.device), 'pending': []}
+
+    def pair():
+        p = hipops.nonrigid_apply(x, state['d'], pinned)
+        r = finder.closest(p)
+        dist, face = r['dist'].contiguous(), r['face'].int().contiguous()
+        thr = base
+        if trim < 1.0:                                                    # one more host synchronisation, for tau
+            d = torch.where(torch.isfinite(dist) & (face >= 0), dist, torch.full_like(dist, float('inf'))).sort().values
+            n_fin = torch.isfinite(d).sum()
+            k = torch.ceil(trim * n_fin.double()).long().clamp(1, max(d.numel(), 1))
+            if d.numel():
+                thr = min(base, d[k - 1].item())
+        ns = hipops.mesh_normals(adj._state, p, adj.faces) if normal_cos is not None else None
+        c, n, b, stats = hipops.nonrigid_terms(x, p, r['point'].contiguous(), dist, face, pinned, thr, metric, normals, ns, normal_cos, share,
+                                               beta, land)
+        # the one host synchronisation of the pairing: its two sums, and the results of the solves since the last one
+        vals = torch.cat([stats] + [out for _, out in state['pending']]).cpu().tolist()
+        for i, (lvl, _) in enumerate(state['pending']):
+            lvl['cg_steps'].append(int(vals[2 + 5 * i + 2]))
+            lvl['cg_residual'].append(vals[2 + 5 * i + 3])
+        state['pending'] = []
+        return _rms(vals[0], int(vals[1])), int(vals[1]), (c, n if metric == 'plane' else None, b)
+
+    def solve(terms, a, lvl):
+        c, n, b = terms
+        state['d'], out = hipops.nonrigid_solve(adj._state, c, b, a, pinned, n, share, beta, state['d'], cg_iterations, cg_tol)
+        state['pending'].append((lvl, out))
+    hist, levels, n = _nonrigid_loop(pair, solve, float(grid.extent), schedule, iterations, tol)
+    return state['d'], hist, levels, n
+
+
+def nonrigid_align(source, verts, faces, metric='point', stiffness=(50.0, 10.0, 2.0, 0.5), iterations=5, tol=1e-4, cg_iterations=100,
+                   cg_tol=1e-6, point_share=0.1, max_dist=None, trim=1.0, normal_cos=None, fixed=None, landmarks=None, adjacency=None,
+                   grid=None, search='grid', tree=None):
+    """Fit a template mesh ``source = (src_verts float32 [V,3], src_faces [Fs,3])`` to the triangle mesh ``(verts, faces)`` without
+    changing its topology (non-rigid ICP): one displacement ``d_i`` per template vertex, kept in float64 and starting at 0, pulled to
+    the closest points of the target and held together by the uniform graph Laplacian of the template.  Align rigidly first
+    (``align_mesh``); this starts where that stops.  The definition: for each stiffness ``a`` of the schedule, in
+    order, at most ``iterations`` pairings.  One pairing:
+
+    1. ``p_i = fl32(x_i + d_i)``, always from the original ``x_i`` (the input bits where ``d_i`` is 0);
+    2. ``(dist_i, face_i, q_i)``: the closest point of the target (``closest_point``, ``search='grid'|'tree'``: the same bits);
+    3. pair i counts (``c_i = 1``, else 0) iff ``dist_i`` is finite and ``face_i >= 0``, ``dist_i <= max_dist`` if given,
+       ``dist_i <= tau`` if ``trim < 1`` (``align_mesh``'s tau), the vertex is not pinned, for ``metric='plane'`` the target face has a
+       normal, and with ``normal_cos`` the normal of ``p`` on the template's faces (``mesh_normals``, area weighting) and the unit
+       normal of the target face, both non-zero, have a dot product ``>= normal_cos``;
+    4. ``rms = sqrt(sum c_i |p_i - q_i|^2 / n)`` (0 for n = 0), a float64 sum in vertex order, appended to ``rms_history``;
+    5. the level ends when ``rms <= eps32 extent``, and from its second pairing on when ``|rms_prev - rms| <= tol rms_prev``;
+    6. otherwise ``(C + a L + B) d' = b`` is solved for the new d: ``(L d)_i = deg_i d_i - sum_j d_j`` over the template's
+       ``MeshAdjacency`` (j ascending), ``C_i = c_i I`` (``'point'``) or ``c_i (n_i n_i^T + point_share I)`` (``'plane'``, ``n_i`` the
+       unit normal of ``face_i``), ``B_i = w_k I`` at the vertices of ``landmarks = (index [K], position [K,3], weight)`` (a scalar or
+       [K]), ``b_i = C_i (q_i - x_i) + B_i (y_i - x_i)``.  Pinned vertices (a non-finite ``x_i``, or the bool mask ``fixed`` [V]) keep
+       ``d_i = 0`` and leave the system; a vertex without neighbours is only decoupled.  The solver is plain conjugate gradients in
+       float64 from the current d for exactly ``cg_iterations`` steps, every dot product a float64 sum in vertex order; once
+       ``|r|^2 <= cg_tol^2 |b|^2``, or ``p.Ap <= 0``, or a scalar is not finite, every later step is a no-op (the freeze rule).
+
+    After the last level one more pairing gives ``rms`` and ``inliers``.  Returns ``{'verts': fl32(x + d) in the caller's container,
+    'displacement' float64 [V,3], 'rms', 'rms_history', 'inliers', 'levels': per level {'stiffness', 'pairings', 'cg_steps' (the steps
+    taken before each solve froze), 'cg_residual' (|r| / |b| at the end of each solve)}, 'pinned' bool [V], 'adjacency'}``.  A source
+    without faces is legal: every vertex goes to its closest point.  Landmarks pull only while some pair counts.  An empty target, an
+    empty or non-positive schedule, ``cg_iterations < 1``, ``point_share <= 0`` with the plane metric, a ``fixed`` or landmark array of
+    the wrong shape, a landmark index given twice and an ``adjacency`` built for another mesh raise ValueError.
+
+    A device target runs on the kernels of csrc/nonrigid.hip: one ``TriangleGrid`` (``grid``) or ``WindingTree`` (``tree``) for all
+    pairings, no host synchronisation inside a solve, one per pairing for the rms (one more for tau when ``trim < 1``), the same bits
+    from run to run.  CPU tensors and NumPy arrays take the NumPy restatement, which is the definition."""
+    _closest_search(search)
+    if metric not in _ALIGN_MIN:
+        raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
+    if not (isinstance(source, (tuple, list)) and len(source) == 2):
+        raise ValueError('source must be a (verts, faces) pair')
+    sv, sf = source
+    _mesh_args(sv, sf)
+    _mesh_args(verts, faces)
+    nv = int(sv.shape[0])
+    schedule = [float(a) for a in (stiffness if np.ndim(stiffness) else [stiffness])]
+    if not schedule or not all(np.isfinite(a) and a > 0 for a in schedule):
+        raise ValueError(f'stiffness must be a non-empty schedule of positive numbers, got {stiffness!r}')
+    cg_iterations, cg_tol = _cg_args(cg_iterations, cg_tol)
+    if metric == 'plane' and not float(point_share) > 0:
+        raise ValueError(f'point_share must be > 0 with the plane metric, got {point_share}')
+    if not 0.0 < float(trim) <= 1.0:
+        raise ValueError(f'trim must be in (0, 1], got {trim}')
+    if max_dist is not None and not float(max_dist) >= 0:
+        raise ValueError(f'max_dist must be >= 0, got {max_dist}')
+    if int(iterations) < 0:
+        raise ValueError(f'iterations must be >= 0, got {iterations}')
+    _mask_checked(fixed, nv, 'fixed')
+    lm = None if landmarks is None else _landmark_rows(landmarks, nv)
+    if search != 'tree' and tree is not None:
+        raise ValueError("tree is used with search='tree' only")
+    on_dev = isinstance(verts, torch.Tensor) and verts.is_cuda
+    if on_dev:
+        sv = torch.as_tensor(sv).detach().to(verts.device).float().contiguous()
+        sf = torch.as_tensor(sf).to(verts.device)
+    elif isinstance(sv, torch.Tensor) and sv.is_cuda:
+        raise ValueError('the source is on a device and the target is not')
+    if not faces.shape[0] or not verts.shape[0]:
+        raise ValueError('nonrigid_align: the target mesh is empty')
+    adj = MeshAdjacency(sv, sf) if adjacency is None else adjacency
+    adj._check(sv, sf)
+    args = (metric, schedule, int(iterations), float(tol), cg_iterations, cg_tol, float(point_share), max_dist, float(trim),
+            None if normal_cos is None else float(normal_cos))
+    if on_dev:
+        from . import hipops
+        dev = verts.device
+        pinned = ~torch.isfinite(sv).all(1)
+        if fixed is not None:
+            pinned = pinned | torch.as_tensor(fixed).to(device=dev, dtype=torch.bool)
+        pinned = pinned.contiguous()
+        beta = land = None
+        if lm is not None:
+            at = torch.as_tensor(lm[0], device=dev)
+            beta, land = torch.zeros(nv, dtype=torch.float64, device=dev), torch.zeros(nv, 3, dtype=torch.float64, device=dev)
+            beta[at] = torch.as_tensor(lm[2], device=dev)
+            land[at] = torch.as_tensor(lm[1], device=dev) - sv[at].double()
+        d, hist, levels, n = _nonrigid_device(sv, adj, verts, faces, pinned, *args, beta, land, grid, search, tree)
+        out = hipops.nonrigid_apply(sv, d, pinned)
+        return {'verts': out, 'displacement': d, 'rms': hist[-1], 'rms_history': hist, 'inliers': n, 'levels': levels, 'pinned': pinned,
+                'adjacency': adj}
+    x = np.ascontiguousarray(_np(sv), dtype=F32)
+    tv, tf = np.asarray(_np(verts), dtype=F32), _np(faces).astype(np.int64)
+    _faces_in_range(tf, tv.shape[0])
+    pinned = ~np.isfinite(x).all(1)
+    if fixed is not None:
+        pinned = pinned | _np(fixed).astype(bool)
+    beta = land = None
+    if lm is not None:
+        beta, land = np.zeros(nv), np.zeros((nv, 3))
+        beta[lm[0]] = lm[2]
+        with np.errstate(all='ignore'):
+            land[lm[0]] = lm[1] - x[lm[0]].astype(np.float64)
+    d, hist, levels, n = _nonrigid_numpy(x, adj, tv, tf, pinned, *args, beta, land, search)
+    return {'verts': _as_out(_moved_numpy(x, d, pinned), sv), 'displacement': _as_out(d, sv, np.float64), 'rms': hist[-1], 'rms_history': hist,
+            'inliers': n, 'levels': levels, 'pinned': _as_out(pinned, sv, bool), 'adjacency': adj}
+
+
 def signed_volume(verts, faces):
     """Signed volume of an indexed mesh (positive for a closed outward-wound one), float64 on the host; faces with a non-finite vertex
     count 0."""

@@ -15,7 +15,11 @@ colours ``--error-ply`` with a diverging map (blue inside the ground truth, red 
 (with ``--winding-beta B``, default 2) makes the winding numbers behind both with ``geometry.WindingTree`` instead of the exact all-pairs
 sum: the route for meshes of hundreds of thousands of faces.  ``--search tree`` takes every closest-point query (the distances, the
 alignment, the IoU lattice, the colours) through ``geometry.closest_point(search='tree')``: the same numbers bit for bit, for meshes that
-lie far apart, where the uniform grid walks every cell; the JSON then records ``search: tree``.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
+lie far apart, where the uniform grid walks every cell; the JSON then records ``search: tree``.  ``--fit-nonrigid`` then (after the
+optional rigid alignment) wraps the prediction onto the ground truth with ``geometry.nonrigid_align`` (``--fit-metric``,
+``--fit-stiffness 50,10,2,0.5``, ``--fit-iterations``, ``--fit-normal-cos``), scores the FITTED mesh, adds a ``nonrigid`` block (rms before
+and after, the levels, inliers, the largest displacement) and, with ``--save-fitted OUT.ply``, writes the fitted mesh: the prediction's own
+faces on the ground truth's shape.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
 import argparse
 import json
 import math
@@ -71,8 +75,26 @@ def alignment_block(fit):
             'iterations': int(fit['iterations']), 'converged': bool(fit['converged']), 'inliers': int(fit['inliers'])}
 
 
+def fit_prediction(verts, faces, ref_verts, ref_faces, options=None):
+    """Wrap the mesh onto the reference with ``geometry.nonrigid_align`` (``options``: its other arguments): ``(fitted vertices, its
+    result)``."""
+    fit = geometry.nonrigid_align((verts, faces), ref_verts, ref_faces, **dict(options or {}))
+    return fit['verts'], fit
+
+
+def nonrigid_block(fit):
+    """The JSON form of a ``nonrigid_align`` result."""
+    d = geometry._np(fit['displacement']).astype(np.float64)
+    largest = float(np.sqrt((d * d).sum(1)).max()) if d.size else 0.0
+    return {'rms_before': float(fit['rms_history'][0]), 'rms_after': float(fit['rms']), 'inliers': int(fit['inliers']),
+            'pairings': len(fit['rms_history']), 'max_displacement': largest, 'pinned': int(geometry._np(fit['pinned']).sum()),
+            'levels': [{'stiffness': float(l['stiffness']), 'pairings': int(l['pairings']), 'cg_steps': [int(k) for k in l['cg_steps']],
+                        'cg_residual': [float(r) for r in l['cg_residual']]} for l in fit['levels']]}
+
+
 def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, error_ply=None, align=None, align_options=None,
-                   save_aligned=None, aligned=None, signed=False, iou=None, winding='exact', beta=2.0, search='grid'):
+                   save_aligned=None, aligned=None, signed=False, iou=None, winding='exact', beta=2.0, search='grid', fit=None,
+                   save_fitted=None, fitted=None):
     """``surface_distance(mesh, reference)`` plus the sizes of both meshes; ``error_ply``: also write the mesh coloured by distance.
     ``align``: 'rigid' or 'similarity' moves the mesh onto the reference first (``align_prediction`` with ``align_options``); the moved
     mesh is scored (and coloured), the result gains ``alignment`` (``alignment_block``), ``save_aligned`` is a PLY path for the moved mesh
@@ -80,9 +102,12 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
     diverging ``error_ply`` (``signed_error_colors``); ``iou``: a lattice resolution, adds ``volume_iou`` of the (moved) mesh and the
     reference.  ``winding='tree'``: the winding numbers behind ``signed`` and ``iou`` come from ``geometry.WindingTree`` with ``beta``
     (the approximation for large meshes) and the result gains ``winding: {'method', 'beta'}``.  ``search='tree'``: every closest-point
-    query goes through the cluster tree (``geometry.closest_point``; the same bits) and the result gains ``search: 'tree'``."""
+    query goes through the cluster tree (``geometry.closest_point``; the same bits) and the result gains ``search: 'tree'``.  ``fit``: a
+    dict of ``nonrigid_align`` arguments (may be empty) wraps the (moved) mesh onto the reference after that; the fitted mesh is scored,
+    the result gains ``nonrigid`` (``nonrigid_block``), ``save_fitted`` is a PLY path for it and ``fitted``, a dict, receives its ``verts``."""
     tree = {'winding': winding, 'beta': beta} if winding != 'exact' else {}
     how = {'search': geometry._closest_search(search)} if search != 'grid' else {}
+    fit_options = fit
     alignment = None
     if align is not None:
         verts, fit = align_prediction(verts, faces, ref_verts, ref_faces, align, samples, seed, {**dict(align_options or {}), **how})
@@ -91,6 +116,14 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
             geometry.write_ply(save_aligned, verts, faces)
         if aligned is not None:
             aligned.update(verts=verts, matrix=fit['matrix'])
+    nonrigid = None
+    if fit_options is not None:
+        verts, wrapped = fit_prediction(verts, faces, ref_verts, ref_faces, {**dict(fit_options), **how})
+        nonrigid = nonrigid_block(wrapped)
+        if save_fitted:
+            geometry.write_ply(save_fitted, verts, faces)
+        if fitted is not None:
+            fitted.update(verts=verts)
     res = geometry.surface_distance(verts, faces, ref_verts, ref_faces, samples=samples, seed=seed, thresholds=thresholds,
                                     **({'signed': True, **tree} if signed else {}), **how)
     if tree:
@@ -101,6 +134,8 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
                gt_faces=int(ref_faces.shape[0]))
     if alignment is not None:
         res['alignment'] = alignment
+    if nonrigid is not None:
+        res['nonrigid'] = nonrigid
     if iou is not None:
         res['volume_iou'] = geometry.volume_iou(verts, faces, ref_verts, ref_faces, resolution=int(iou), **tree, **how)
     if error_ply:
@@ -147,6 +182,31 @@ def align_options_of(args):
     return {'metric': args.align_metric, 'iterations': args.align_iterations, 'trim': args.align_trim, 'init': args.align_init}
 
 
+def add_fit_arguments(ap, flag=True):
+    """The ``--fit-*`` family of flags of the non-rigid fit, shared with extract_geometry (which has ``--fit-template`` for ``flag``)."""
+    if flag:
+        ap.add_argument('--fit-nonrigid', action='store_true', help='wrap the predicted mesh onto the reference (non-rigid ICP) and score the fitted mesh')
+    ap.add_argument('--fit-metric', default='point', choices=['point', 'plane'])
+    ap.add_argument('--fit-stiffness', default='50,10,2,0.5', metavar='A,B,...', help='the stiffness schedule, stiff to soft')
+    ap.add_argument('--fit-iterations', type=int, default=5, help='pairings per stiffness level')
+    ap.add_argument('--fit-normal-cos', type=float, default=None, metavar='C',
+                    help='reject pairs whose template and target normals have a dot product below C')
+
+
+def fit_options_of(args):
+    try:
+        schedule = tuple(float(x) for x in str(args.fit_stiffness).split(',') if x.strip())
+    except ValueError:
+        raise ValueError(f'--fit-stiffness must be numbers separated by commas, got {args.fit_stiffness!r}') from None
+    return {'metric': args.fit_metric, 'stiffness': schedule, 'iterations': args.fit_iterations,
+            **({'normal_cos': args.fit_normal_cos} if args.fit_normal_cos is not None else {})}
+
+
+def nonrigid_summary(n, what='fitted'):
+    return (f'{what}: rms {n["rms_before"]:.6g} -> {n["rms_after"]:.6g} in {n["pairings"]} pairings, {n["inliers"]} inliers, largest '
+            f'displacement {n["max_displacement"]:.6g}')
+
+
 def alignment_summary(a):
     return (f'aligned: scale {a["scale"]:.6g}, rotation {a["angle_deg"]:.4g} deg, |t| {a["shift"]:.6g}, rms {a["rms_before"]:.6g} -> '
             f'{a["rms_after"]:.6g} in {a["iterations"]} steps{"" if a["converged"] else " (not converged)"}')
@@ -175,6 +235,8 @@ def main(argv=None):
     add_align_arguments(ap)
     add_sign_arguments(ap)
     ap.add_argument('--save-aligned', default=None, metavar='OUT.ply', help='with --align: write the moved predicted mesh')
+    add_fit_arguments(ap)
+    ap.add_argument('--save-fitted', default=None, metavar='OUT.ply', help='with --fit-nonrigid: write the fitted predicted mesh')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
     meshes = []
@@ -185,11 +247,17 @@ def main(argv=None):
         ap.error('--save-aligned needs --align')
     extra = {'align': args.align, 'align_options': align_options_of(args), 'save_aligned': args.save_aligned} if args.align else {}
     extra.update(sign_options_of(args))
+    if args.save_fitted and not args.fit_nonrigid:
+        ap.error('--save-fitted needs --fit-nonrigid')
+    if args.fit_nonrigid:
+        extra.update(fit=fit_options_of(args), save_fitted=args.save_fitted)
     res = compare_meshes(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, error_ply=args.error_ply, **extra)
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
     if args.align:
         print(alignment_summary(res['alignment']))
+    if args.fit_nonrigid:
+        print(nonrigid_summary(res['nonrigid']))
     print(summary(res))
     return res
 

@@ -1787,6 +1787,132 @@ def align_sums(src, dst, dist, face, centre, max_dist=float('inf'), metric='poin
     return out
 
 
+# ------------------------------------------------------------------ non-rigid fitting (csrc/nonrigid.hip)
+
+def _f64c(t, what, shape):
+    if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise RuntimeError(f'{what} must be a contiguous float64 device tensor {tuple(shape)}')
+    return t
+
+
+def _pinned_checked(pinned, v):
+    if not (pinned.is_cuda and pinned.dtype == torch.bool and pinned.is_contiguous() and tuple(pinned.shape) == (v,)):
+        raise RuntimeError(f'pinned must be a contiguous bool device tensor [{v}]')
+    return pinned
+
+
+def nonrigid_terms(x, p, q, dist, face, pinned, max_dist=float('inf'), metric='point', face_normals=None, source_normals=None,
+                   normal_cos=None, point_share=0.1, beta=None, land=None):
+    """The terms of one pairing of the non-rigid fit (see ia_nonrigid_terms): x, p, q float32 [V,3], dist float32 [V], face int32 [V],
+    pinned bool [V], face_normals float32 [Fb,3] (plane metric, normal_cos), source_normals float32 [V,3] (normal_cos), beta float64
+    [V] and land float64 [V,3] (landmarks, or None) -> ``(c [V], n [V,3], b [V,3], stats [2])``, float64 device tensors; stats =
+    (sum c |p - q|^2, sum c).  No host synchronisation."""
+    if metric not in ALIGN_MODES:
+        raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
+    mode, use_cos = ALIGN_MODES[metric], normal_cos is not None
+    v, dev = dist.numel(), dist.device
+    for t, what in ((x, 'x'), (p, 'p'), (q, 'q')):
+        if tuple(_f32c(t, what).shape) != (v, 3) or t.device != dev:
+            raise RuntimeError(f'{what} must be [V,3] on the device of dist, got {tuple(t.shape)}')
+    _f32c(dist, 'dist')
+    if _i32c(face, 'face').numel() != v:
+        raise RuntimeError('face must be [V]')
+    _pinned_checked(pinned, v)
+    fb = 0
+    if mode or use_cos:
+        _f32c(face_normals, 'face_normals')
+        if face_normals.dim() != 2 or face_normals.shape[1] != 3 or face_normals.device != dev:
+            raise RuntimeError(f'face_normals must be [Fb,3] on the device of the points, got {tuple(face_normals.shape)}')
+        fb = face_normals.shape[0]
+    if use_cos and tuple(_f32c(source_normals, 'source_normals').shape) != (v, 3):
+        raise RuntimeError('source_normals must be [V,3]')
+    _f64c(beta, 'beta', (v,))
+    if beta is not None:
+        _f64c(land, 'land', (v, 3))
+    f64 = dict(dtype=torch.float64, device=dev)
+    c, n, b, out = torch.empty(v, **f64), torch.empty(v, 3, **f64), torch.empty(v, 3, **f64), torch.empty(2, **f64)
+    scratch, nbytes = _scratch('ia_nonrigid_terms_scratch_bytes', v, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _Timed('nonrigid_terms', 0.0, (61.0 + 56.0) * v, f'V={v} {metric}'):
+        st = _lib.load().ia_nonrigid_terms(_p(x), _p(p), _p(q), _p(dist), _p(face), v, _p(face_normals) if fb else None, fb,
+                                           _p(source_normals) if use_cos else None, float(max_dist), mode, int(use_cos),
+                                           float(normal_cos) if use_cos else 0.0, float(point_share), _p(pinned), _p(beta),
+                                           _p(land) if beta is not None else None, _p(c), _p(n), _p(b), _p(scratch), nbytes, _p(out),
+                                           _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_nonrigid_terms')
+    return c, n, b, out
+
+
+def nonrigid_rhs(weight, target_offset, pinned, normals=None, point_share=0.1, beta=None, land=None):
+    """float64 [V,3]: the right-hand side ``C t + B l`` of the non-rigid system from given weights and offsets (ia_nonrigid_rhs)."""
+    v, dev = weight.numel(), weight.device
+    _f64c(weight, 'weight', (v,))
+    _f64c(target_offset, 'target_offset', (v, 3))
+    _f64c(normals, 'normals', (v, 3))
+    _f64c(beta, 'beta', (v,))
+    if beta is not None:
+        _f64c(land, 'land', (v, 3))
+    _pinned_checked(pinned, v)
+    b = torch.empty(v, 3, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.load().ia_nonrigid_rhs(v, _p(weight), _p(target_offset), _p(normals), float(point_share), _p(beta),
+                                         _p(land) if beta is not None else None, _p(pinned), _p(b), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_nonrigid_rhs')
+    return b
+
+
+NONRIGID_LAUNCHES = 3        # launches per conjugate-gradient step (apply, update, direction); one more with heavy vertices
+
+
+def nonrigid_step_bytes(v, e):
+    """Algorithmic bytes one conjugate-gradient step moves: apply reads a 24-byte row and a 4-byte index per CSR entry, its own row,
+    offset, weight and pin (37) and writes 24; update reads four rows and writes two (144); direction reads two and writes one (72)."""
+    return 28.0 * e + (37.0 + 24.0 + 144.0 + 72.0) * v
+
+
+def nonrigid_solve(s, weight, b, stiffness, pinned, normals=None, point_share=0.1, beta=None, x0=None, cg_iterations=100, cg_tol=1e-6):
+    """Conjugate gradients on ``(C + a L + B) x = b`` over the ``mesh_adjacency`` state ``s`` (see ia_nonrigid_solve): weight float64
+    [V], b float64 [V,3], pinned bool [V], normals float64 [V,3] (plane metric) or None, beta float64 [V] or None, x0 float64 [V,3] or
+    None (zero) -> ``(x [V,3], out [5])``, float64 device tensors; out = (energy at the start, at the end, steps taken, |r| / |b|,
+    frozen).  ``x0`` is not written.  Every launch goes to the current stream; there is no host synchronisation."""
+    v, dev = s['V'], weight.device
+    _f64c(weight, 'weight', (v,))
+    _f64c(b, 'b', (v, 3))
+    _f64c(normals, 'normals', (v, 3))
+    _f64c(beta, 'beta', (v,))
+    _pinned_checked(pinned, v)
+    if int(cg_iterations) < 1:
+        raise ValueError(f'cg_iterations must be >= 1, got {cg_iterations}')
+    f64 = dict(dtype=torch.float64, device=dev)
+    if x0 is None:
+        x = torch.zeros(v, 3, **f64)
+    else:
+        x = torch.where(pinned[:, None], torch.zeros((), **f64), _f64c(x0, 'x0', (v, 3))).contiguous()
+    out = torch.empty(5, **f64)
+    scratch, nbytes = _scratch('ia_nonrigid_solve_scratch_bytes', v, dtype=torch.float64, device=dev)
+    e = s['E']
+    step_bytes = nonrigid_step_bytes(v, e)
+    with torch.cuda.device(dev), _Timed('nonrigid_solve', 0.0, step_bytes * int(cg_iterations), f'V={v} E={e} steps={int(cg_iterations)}'):
+        st = _lib.load().ia_nonrigid_solve(v, _p(s['offsets']), _p(s['neighbors']) if e else None, e, _p(s['heavy']) if s['n_heavy'] else None,
+                                           s['n_heavy'], _p(weight), _p(normals), _p(beta), _p(pinned), _p(b), float(stiffness),
+                                           float(point_share), _p(x), int(cg_iterations), float(cg_tol), _p(scratch), nbytes, _p(out),
+                                           _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_nonrigid_solve')
+    return x, out
+
+
+def nonrigid_apply(x, d, pinned):
+    """float32 [V,3]: ``fl32(x + d)``, the input bits where a vertex is pinned or a displacement is 0 (ia_nonrigid_apply)."""
+    v, dev = x.shape[0], x.device
+    _f32c(x, 'x')
+    _f64c(d, 'd', (v, 3))
+    _pinned_checked(pinned, v)
+    out = torch.empty_like(x)
+    with torch.cuda.device(dev), _Timed('nonrigid_apply', 0.0, 49.0 * v, f'V={v}'):
+        st = _lib.load().ia_nonrigid_apply(_p(x), _p(d), _p(pinned), v, _p(out), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_nonrigid_apply')
+    return out
+
+
 # ------------------------------------------------------------------ winding number (csrc/winding.hip)
 
 WINDING_TILE = 256           # triangles per LDS tile (csrc/winding.hip kTile)

@@ -535,7 +535,8 @@ class TriPlaneGenerator(torch.nn.Module):
 
     @torch.no_grad()
     def extract_geometry(self, ws, mesh_condition, resolution=256, level=10.0, cube_length=None, origin=(0, 0, 0), with_colors=False,
-                         with_normals=False, keep=None, min_voxels=0, simplify=None, smooth=None, texture=None, **synthesis_kwargs):
+                         with_normals=False, keep=None, min_voxels=0, simplify=None, smooth=None, texture=None, fit_template=None,
+                         **synthesis_kwargs):
         """Shape of the avatar: one dict per batch element with 'volume' [N,N,N] (density on the lattice of
         ``invertavatar_amd.geometry``: ``cube_length`` (default: box_warp) around ``origin``), 'verts' float32 [V,3] (same coordinates
         as the queries), 'faces' int64 [F,3] (outward-wound marching-cubes mesh of density > ``level``) and, with ``with_colors``,
@@ -554,8 +555,12 @@ class TriPlaneGenerator(torch.nn.Module):
         the smoothing's 'info' ('edges', 'boundary_edges', 'nonmanifold_edges', 'steps', ...).  ``texture`` (None: nothing changes; an
         int = the atlas size with the decoder as source; or a dict of ``bake_texture`` keyword arguments) bakes the colours of the
         FINAL mesh (after ``keep``, ``simplify`` and ``smooth``) into a texture atlas: 'texture' [size,size,3], 'uv' float32 [F,3,2],
-        'atlas' and 'texture_info' {'filled', 'mask' and, from views, 'views'}.  The planes are computed once per call; device tensors
-        stay on the device throughout."""
+        'atlas' and 'texture_info' {'filled', 'mask' and, from views, 'views'}.  ``fit_template`` (None: nothing changes; a ``(verts,
+        faces)`` pair; or a dict with 'verts', 'faces', optionally 'align' (``'rigid'`` or ``'similarity'``: ``geometry.align_mesh`` from
+        ``init='centroid'`` first) and ``geometry.nonrigid_align`` keyword arguments) wraps that template onto the FINAL mesh: 'template'
+        holds {'verts' (the template's vertices on the avatar's shape), 'faces' (the template's own), 'fit' (``nonrigid_align``'s result),
+        with ``with_colors`` 'colors' (queried at the fitted vertices) and with 'align' 'alignment' (``align_mesh``'s result)}: one fixed
+        topology for every seed.  The planes are computed once per call; device tensors stay on the device throughout."""
         from .. import geometry
         box_warp = self.rendering_kwargs['box_warp']
         length = box_warp if cube_length is None else cube_length
@@ -598,6 +603,22 @@ class TriPlaneGenerator(torch.nn.Module):
                 baked = self.bake_texture(ws[b:b + 1], cond_b, verts, faces, **kw, **synthesis_kwargs)
                 item['texture'], item['uv'], item['atlas'] = baked['texture'], baked['uv'], baked['atlas']
                 item['texture_info'] = {k: baked[k] for k in ('filled', 'mask', 'views') if k in baked}
+            if fit_template is not None:
+                kw = dict(fit_template) if isinstance(fit_template, dict) else {'verts': fit_template[0], 'faces': fit_template[1]}
+                tv = torch.as_tensor(kw.pop('verts')).to(verts.device).float().contiguous()
+                tf = torch.as_tensor(kw.pop('faces')).to(verts.device)
+                how, wrapped = kw.pop('align', None), {'faces': tf}
+                if how is not None:
+                    if how not in ('rigid', 'similarity'):
+                        raise ValueError(f"fit_template['align'] must be None, 'rigid' or 'similarity', got {how!r}")
+                    wrapped['alignment'] = geometry.align_mesh((tv, tf), verts, faces, scale=how == 'similarity', init='centroid',
+                                                               **({'search': kw['search']} if 'search' in kw else {}))
+                    tv = geometry.transform_points(tv, wrapped['alignment']['matrix'])
+                wrapped['fit'] = geometry.nonrigid_align((tv, tf), verts, faces, **kw)
+                wrapped['verts'] = wrapped['fit']['verts']
+                if with_colors:
+                    wrapped['colors'] = geometry.vertex_colors(planes[b:b + 1], self.decoder, wrapped['verts'], box_warp)
+                item['template'] = wrapped
             out.append(item)
         return out
 

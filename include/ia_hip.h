@@ -1129,6 +1129,26 @@ int ia_align_sums(const float* src, const float* dst, const float* dist, const i
                   void* stream);
 
 /*
+ * Pose search for global registration (csrc/pose_search.hip; no counterpart in the reference; definition: geometry.pose_scores and
+ * its NumPy restatement).  Additive entry point: the ABI version is unchanged.
+ *
+ * ia_pose_scores: out double [R, shifts^3] = the score of every candidate pose of the points float32 [n,3], n <= 4096, against the
+ * unsigned distance lattice dist float32 [nx,ny,nz] (x slowest; point (i,j,k) at h_origin + index * h_spacing, cubic cells):
+ *   score[r, k] = sum_i min(d(p_i), h_cap)^2 / n,   p_i = h_scale (R_r (x_i - fp32(h_c_src))) + (fp32(h_c_tgt) + o_k)
+ * with rotations float32 [R,9] row-major on the device, o_k = ((a_x, a_y, a_z) - (shifts - 1) / 2) h_shift_step for the offset index
+ * k = (a_x shifts + a_y) shifts + a_z (shifts odd, <= 15), and the lookup, per axis u = (p - origin) fp32(1 / h), c = clamp(u, 0,
+ * dim - 1), i = min(floor(c), dim - 2), t = c - i:  d = trilinear(dist, i, t) + h |u - c|_2 (lerp(a, b, t) = a + t (b - a) along z,
+ * then y, then x).  Float32 per point, every operation rounded on its own; min(d, cap) is squared and summed in double, per thread in
+ * index order, then wave, then workgroup in a fixed order: no floating-point atomics, and a candidate's score has the same bits from
+ * run to run, in any set or order of candidates and for any split of R.  A non-finite point gives a non-finite score to every
+ * candidate (drop such rows first).  h_origin: 3 floats, h_c_src and h_c_tgt: 3 doubles, all on the host; h_cap = +inf: no cap.
+ * n = 0 or R = 0: nothing is launched and out is not written.  No scratch.
+ */
+int ia_pose_scores(const float* points, int n, const float* dist, int nx, int ny, int nz, const float* h_origin, float h_spacing,
+                   const float* rotations, int64_t R, const double* h_c_src, const double* h_c_tgt, int shifts, float h_shift_step,
+                   float h_scale, float h_cap, double* out, void* stream);
+
+/*
  * Generalised winding number of points with respect to a triangle soup (csrc/winding.hip; no counterpart in the reference;
  * definition: geometry.winding_number and its NumPy restatement): 1 inside a closed outward-wound mesh, 0 outside,
  * in between for an open one.  Additive entry points: the ABI version is unchanged.

@@ -164,6 +164,8 @@ _SIGNATURES = {
     'ia_align_sums_scratch_bytes': [c_int64, c_int, ctypes.POINTER(ctypes.c_size_t)],
     'ia_align_sums': [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(ctypes.c_double), c_float, c_int,
                       c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
+    'ia_pose_scores': [c_void_p, c_int, c_void_p, c_int, c_int, c_int, _f32p, c_float, c_void_p, c_int64, ctypes.POINTER(ctypes.c_double),
+                       ctypes.POINTER(ctypes.c_double), c_int, c_float, c_float, c_float, c_void_p, c_void_p],
     'ia_winding_layout': [ctypes.POINTER(c_int)] * 3,
     'ia_winding_number_scratch_bytes': [c_int64, c_int64, ctypes.POINTER(ctypes.c_size_t)],
     'ia_winding_number': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],

@@ -33,7 +33,8 @@ the FINAL mesh into a SIZE^2 texture atlas (``geometry.TextureAtlas``) and write
 orbit onto the mesh (``--texture-mode blend|best``) with the decoder bake as the fallback; with ``--mesh-views`` the mesh is also rendered
 through the texture (``seed%04d_meshtex%02d.png``); a line per seed reports the block side, the share of filled texels and the views per
 texel.  ``--fit-template T.ply`` wraps the template mesh ``T.ply`` onto the FINAL mesh of every seed (``geometry.nonrigid_align``;
-``--fit-align rigid|similarity`` first moves it there with ``geometry.align_mesh`` from the centroids; ``--fit-metric``, ``--fit-stiffness``,
+``--fit-align rigid|similarity`` first moves it there with ``geometry.align_mesh`` from the centroids, or with ``--fit-init global`` from
+a pose search (``geometry.global_align``: a template in another coordinate frame); ``--fit-metric``, ``--fit-stiffness``,
 ``--fit-iterations`` and ``--fit-normal-cos`` as in ``geometry_metrics``) and writes ``seed%04d_template.ply``: the template's own faces on
 the avatar's shape, so every seed has the same topology, with colours queried at the fitted vertices unless ``--no-colors``; a line per
 seed reports the template's vertices, the rms before and after, the inliers and the largest displacement, and ``seed%04d_geometry.json``
@@ -129,6 +130,8 @@ def main(argv=None):
     ap.add_argument('--texture-mode', default='blend', choices=['blend', 'best'], help='with --texture-source views: blend the views or take the best')
     ap.add_argument('--fit-template', default=None, metavar='T.ply', help='wrap this template mesh onto the final mesh; writes _template.ply')
     ap.add_argument('--fit-align', default=None, choices=geometry_metrics.ALIGN_MODES, help='with --fit-template: align the template first (from the centroids)')
+    ap.add_argument('--fit-init', default='centroid', choices=['centroid', 'global'],
+                    help='with --fit-align: start from the centroids, or from a pose search (a template in another coordinate frame)')
     geometry_metrics.add_fit_arguments(ap, flag=False)
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
@@ -156,7 +159,8 @@ def main(argv=None):
     if args.fit_template:
         tv, tf, _ = geometry.read_ply(args.fit_template)
         texture['fit_template'] = {'verts': torch.from_numpy(tv).to(args.device), 'faces': torch.from_numpy(tf).to(args.device),
-                                   **({'align': args.fit_align} if args.fit_align else {}), **geometry_metrics.fit_options_of(args),
+                                   **({'align': args.fit_align} if args.fit_align else {}),
+                                   **({'align_init': args.fit_init} if args.fit_init != 'centroid' else {}), **geometry_metrics.fit_options_of(args),
                                    **({'search': args.search} if args.search != 'grid' else {})}
     for seed, w in zip(args.seeds, ws):
         out = G.extract_geometry(w.float(), mesh, resolution=args.res, level=args.level, with_colors=not args.no_colors,

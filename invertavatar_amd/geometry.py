@@ -1231,7 +1231,7 @@ def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dis
 
 
 def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30, tol=1e-6, max_dist=None, trim=1.0, init='identity',
-               grid=None, search='grid'):
+               grid=None, search='grid', global_options=None):
     """Align ``source`` (points [N,3], or a ``(verts, faces)`` pair whose vertices are used) to the triangle mesh ``(verts, faces)`` by
     iterated closest points: the rigid (``scale=False``) or similarity transform ``y = s R x + t`` that brings the points onto the
     surface, as a float64 4x4 ``M`` with ``M[:3,:3] = s R``, ``M[:3,3] = t``.  ICP finds the local optimum nearest to the start, so the
@@ -1256,7 +1256,11 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
     ``grid`` if given; one host synchronisation per iteration for the sums, one more for tau when ``trim < 1``); CPU tensors and NumPy
     arrays take the NumPy restatement, which is the definition.  ``search='tree'`` takes step 2 through ``closest_point(search='tree')``
     (one ``WindingTree`` for all iterations, no uniform grid): the same bits, and the choice for a source that starts outside the
-    target's box, where the grid walks every cell."""
+    target's box, where the grid walks every cell.
+
+    ``init='global'`` needs no start: ``M_0 = global_align(...)['matrix']`` with this call's ``metric / scale / trim / max_dist /
+    search`` and ``global_options`` (a dict of its other arguments: ``angle_step``, ``candidates``, ``shifts``, ``field``, ...), then the
+    loop above; the result gains ``'global': {'candidates', 'searched', 'rank'}``."""
     _closest_search(search)
     if metric not in _ALIGN_MIN:
         raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
@@ -1273,6 +1277,7 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
     if iterations < 0:
         raise ValueError(f'iterations must be >= 0, got {iterations}')
     on_dev = isinstance(verts, torch.Tensor) and verts.is_cuda
+    found = None
     if isinstance(init, str):
         if init == 'identity':
             M0 = np.eye(4)
@@ -1280,14 +1285,297 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
             if not faces.shape[0] or not verts.shape[0]:
                 raise ValueError('align_mesh: the target mesh is empty')
             M0 = _centroid_init(_np(source), _np(verts), scale)
+        elif init == 'global':
+            found = global_align(source, verts, faces, metric=metric, scale=scale, trim=trim, max_dist=max_dist, search=search, grid=grid,
+                                 **dict(global_options or {}))
+            M0 = found['matrix']
         else:
-            raise ValueError(f"init must be 'identity', 'centroid' or a 4x4 matrix, got {init!r}")
+            raise ValueError(f"init must be 'identity', 'centroid', 'global' or a 4x4 matrix, got {init!r}")
     else:
         M0 = _matrix44(init)
     args = (M0, metric, bool(scale), iterations, float(tol), max_dist, float(trim))
     if on_dev:
-        return _align_device(torch.as_tensor(source), verts, faces, *args, grid, search)
-    return _align_numpy(_np(source), _np(verts), _np(faces), *args, search=search)
+        res = _align_device(torch.as_tensor(source), verts, faces, *args, grid, search)
+    else:
+        res = _align_numpy(_np(source), _np(verts), _np(faces), *args, search=search)
+    if found is not None:
+        res['global'] = {k: found[k] for k in ('candidates', 'searched', 'rank')}
+    return res
+
+
+# ------------------------------------------------------------------ global registration: pose search over a distance field, then ICP
+
+POSE_MAX_POINTS = 4096       # csrc/pose_search.hip kMaxPoints = hipops.POSE_MAX_POINTS
+_POSE_HEAD = 4096            # entries of the score order that the selection walks (one host read on the device path)
+
+
+class PoseField:
+    """The unsigned distance of the target mesh ``(verts, faces)`` on a lattice with cubic cells, for ``pose_scores`` and
+    ``global_align``: build once per target, hand to many calls.  The lattice is that of ``mesh_to_volume`` (``_volume_lattice``): the
+    longest side of the box of the finite vertices gets ``resolution`` points, ``padding`` of them beyond the box on each side.
+    ``dist`` float32 [nx,ny,nz] (x slowest) is ``closest_point(search='tree')`` at the lattice points (most of them are off the mesh,
+    where the tree prunes best; the same bits as the other searches), a device tensor for a device mesh and a NumPy array otherwise.  Also ``dims``, ``origin`` (three floats),
+    ``spacing`` (one float, h), ``centroid`` and ``radius`` (mean and rms radius of the finite vertices, as ``init='centroid'`` takes
+    them), ``extent`` (largest absolute coordinate of the box) and ``n_verts`` / ``n_faces`` of the mesh it was made for."""
+
+    def __init__(self, verts, faces, resolution=32, padding=2):
+        _mesh_args(verts, faces)
+        if not faces.shape[0] or not verts.shape[0]:
+            raise ValueError('PoseField: the target mesh is empty')
+        box = _finite_box(verts)
+        if box is None:
+            raise ValueError('PoseField: the target mesh has no finite vertex')
+        self.dims, self.origin, spacing = _volume_lattice(box, int(resolution), None, None, padding)
+        self.spacing = float(spacing[0])
+        b = _finite_rows(np.asarray(_np(verts), dtype=np.float64))
+        self.centroid = b.mean(0)
+        self.radius = float(np.sqrt(((b - self.centroid) ** 2).sum(1).mean()))
+        self.extent = float(max(np.abs(box[0]).max(), np.abs(box[1]).max()))
+        self.n_verts, self.n_faces = int(verts.shape[0]), int(faces.shape[0])
+        pts = np.ascontiguousarray(np.stack(np.meshgrid(*_lattice_axes(self.dims, self.origin, spacing), indexing='ij'), -1).reshape(-1, 3))
+        if _is_device(verts):
+            self.device = verts.device
+            d = closest_point(torch.from_numpy(pts).to(verts.device), verts, faces, search='tree')['dist']
+            self.dist = d.reshape(self.dims).contiguous()
+        else:
+            self.device = None
+            d = closest_point(pts, np.asarray(_np(verts), dtype=F32), _np(faces), search='tree')['dist']
+            self.dist = np.ascontiguousarray(d.reshape(self.dims).astype(F32))
+
+    def lookup(self, points, dtype=np.float64):
+        """``d(p)`` of the NumPy restatement at points [..., 3] (the lattice is read back from the device if it lives there)."""
+        return _pose_lookup_numpy(_np(self.dist), self.origin, self.spacing, np.asarray(_np(points)), dtype)
+
+
+def _pose_lookup_numpy(dist, origin, h, p, dtype=np.float64):
+    """The lookup of ia_pose_scores in ``dtype`` at p [..., 3]: per axis ``u = (p - origin) (1 / h)``, ``c = clamp(u, 0, dim - 1)``,
+    ``i = min(floor(c), dim - 2)``, ``t = c - i``; ``d = trilinear(dist, i, t) + h |u - c|_2`` with ``lerp(a, b, t) = a + t (b - a)``
+    along z, then y, then x; every operation rounded on its own.  A NaN coordinate gives NaN."""
+    v = np.asarray(dist, dtype=F32).astype(dtype)
+    p = np.asarray(p).astype(dtype)
+    hh, inv = dtype(F32(h)), dtype(1.0 / float(F32(h)))
+    idx, t, e = [], [], []
+    with np.errstate(invalid='ignore', over='ignore'):
+        for a in range(3):
+            u = (p[..., a] - dtype(F32(origin[a]))) * inv
+            c = np.minimum(np.maximum(u, dtype(0)), dtype(v.shape[a] - 1))
+            i = np.clip(np.floor(np.where(np.isfinite(c), c, 0)).astype(np.int64), 0, v.shape[a] - 2)
+            idx.append(i)
+            t.append(c - i.astype(dtype))
+            e.append(u - c)
+        (i, j, k), (tx, ty, tz) = idx, t
+        lerp = lambda a, b, w: a + w * (b - a)                                               # noqa: E731
+        c00, c01 = lerp(v[i, j, k], v[i, j, k + 1], tz), lerp(v[i, j + 1, k], v[i, j + 1, k + 1], tz)
+        c10, c11 = lerp(v[i + 1, j, k], v[i + 1, j, k + 1], tz), lerp(v[i + 1, j + 1, k], v[i + 1, j + 1, k + 1], tz)
+        inside = lerp(lerp(c00, c01, ty), lerp(c10, c11, ty), tx)
+        return (inside + hh * np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])).astype(dtype)
+
+
+def _pose_offsets(shifts):
+    shifts = int(shifts)
+    if shifts < 1 or shifts % 2 == 0:
+        raise ValueError(f'shifts must be odd and >= 1, got {shifts}')
+    return shifts
+
+
+def _pose_scores_numpy(points, dist, origin, h, rotations, c_src, c_tgt, shifts=1, shift_step=None, scale=1.0, cap=np.inf,
+                       dtype=np.float64, chunk=1 << 19):
+    """NumPy restatement of ia_pose_scores, float64 [R, shifts^3]; ``dtype``: the precision of the per-point term
+    ``min(d(p), cap)`` (np.float32 repeats the kernel's operations one by one); its square and the sum are float64 in both."""
+    shifts = _pose_offsets(shifts)
+    x = np.asarray(points, dtype=F32).reshape(-1, 3).astype(dtype)
+    rot = np.asarray(rotations, dtype=np.float64).reshape(-1, 3, 3).astype(F32).astype(dtype)
+    n, R, S3 = x.shape[0], rot.shape[0], shifts ** 3
+    out = np.full((R, S3), np.nan)
+    if n == 0 or R == 0:
+        return out
+    f = lambda a: np.asarray(a, dtype=np.float64).astype(F32).astype(dtype)                  # noqa: E731
+    step = dtype(F32(h if shift_step is None else shift_step))
+    s, capv = dtype(F32(scale)), dtype(F32(np.inf if cap is None else cap))
+    with np.errstate(invalid='ignore', over='ignore'):
+        y = x - f(c_src)
+        a = (np.arange(shifts) - (shifts - 1) // 2).astype(dtype) * step
+        off = f(c_tgt) + np.stack(np.meshgrid(a, a, a, indexing='ij'), -1).reshape(-1, 3)   # [S3,3], x slowest
+        per = max(1, chunk // (n * S3))
+        for r0 in range(0, R, per):
+            m = rot[r0:r0 + per, None]                                                       # [r,1,3,3]
+            q = s * ((m[..., 0] * y[None, :, None, 0] + m[..., 1] * y[None, :, None, 1]) + m[..., 2] * y[None, :, None, 2])   # [r,n,3]
+            d = _pose_lookup_numpy(dist, origin, h, q[:, None] + off[None, :, None], dtype)  # [r,S3,n]
+            term = np.where(d > capv, capv, d).astype(np.float64)
+            out[r0:r0 + per] = (term * term).sum(-1) / n
+    return out
+
+
+def pose_candidates(angle_step=15.0):
+    """Candidate rotations that cover SO(3) at about ``angle_step`` degrees: float64 [R,3,3].  With theta in radians,
+    ``m = ceil(4 pi / theta^2)`` Fibonacci-sphere directions ``d_j = (r cos phi, r sin phi, z)``, ``z = 1 - 2 (j + 1/2) / m``,
+    ``r = sqrt(1 - z^2)``, ``phi = (j + 1/2) pi (3 - sqrt 5)``, times ``k = ceil(2 pi / theta)`` spins:
+    ``R[j k + l] = A_j Rz(2 pi l / k)`` with ``A_j`` the rotation about ``z x d_j`` that takes z to ``d_j``.  4 416 rotations at 15
+    degrees, 1 872 at 20; the largest angle from 300 random rotations to the nearest candidate was 11.09 and 14.88 degrees."""
+    theta = np.deg2rad(float(angle_step))
+    if not 0.0 < theta <= np.pi / 2:
+        raise ValueError(f'angle_step must be in (0, 90] degrees, got {angle_step}')
+    m, k = int(np.ceil(4 * np.pi / theta ** 2)), int(np.ceil(2 * np.pi / theta))
+    j = np.arange(m) + 0.5
+    z = 1.0 - 2.0 * j / m
+    r, phi = np.sqrt(1.0 - z * z), j * (np.pi * (3.0 - np.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], -1)
+    spins = np.stack([_rodrigues(np.array([0.0, 0.0, 2 * np.pi * l / k])) for l in range(k)])
+    out = np.empty((m, k, 3, 3))
+    for a in range(m):
+        axis = np.array([-d[a, 1], d[a, 0], 0.0])                                             # z x d
+        norm = float(np.linalg.norm(axis))
+        A = _rodrigues(axis / norm * np.arctan2(norm, d[a, 2])) if norm > 0 else np.eye(3)
+        out[a] = A @ spins
+    return out.reshape(m * k, 3, 3)
+
+
+def _pose_points(points):
+    """The finite rows as float32 and their mean (float64)."""
+    x = np.asarray(_np(points), dtype=F32).reshape(-1, 3)
+    x = np.ascontiguousarray(x[np.isfinite(x).all(1)])
+    if x.shape[0] > POSE_MAX_POINTS:
+        raise ValueError(f'pose_scores takes at most {POSE_MAX_POINTS} points, got {x.shape[0]}: score a subset (global_align: samples=)')
+    if not x.shape[0]:
+        raise ValueError('pose_scores: no finite point')
+    return x, x.astype(np.float64).mean(0)
+
+
+def pose_scores(points, field, rotations, shifts=1, shift_step=None, scale=1.0, cap=None):
+    """The score of candidate poses of ``points`` [n,3] (float32; non-finite rows are dropped; n <= 4096) against a ``PoseField``:
+    float64 ``[R, shifts^3]`` for ``rotations`` [R,3,3].  For rotation r and offset ``o_k`` on the grid
+    ``(a - (shifts - 1) / 2) shift_step`` per axis (x slowest, ``shifts`` odd, ``shift_step`` defaults to the field's h):
+
+        ``p_i = s R_r (x_i - c_src) + c_tgt + o_k``,   ``score = sum_i min(d(p_i), cap)^2 / n``
+
+    with ``c_src`` the mean of the points, ``c_tgt`` the field's centroid and ``d`` the lookup of the field: trilinear inside the
+    lattice, plus ``h |u - clamp(u)|`` outside it (an upper bound of the true distance up to the interpolation error).  A truncated
+    mean square, not a trimmed one.  A field on the device runs ia_pose_scores (a device tensor comes back), a field on the host the
+    NumPy restatement, which is the definition."""
+    if not isinstance(field, PoseField):
+        raise ValueError(f'field must be a PoseField, got {type(field).__name__}')
+    shifts = _pose_offsets(shifts)
+    x, c_src = _pose_points(points)
+    rot = np.asarray(_np(rotations), dtype=np.float64).reshape(-1, 3, 3)
+    cap = np.inf if cap is None else float(cap)
+    if field.device is not None:
+        from . import hipops
+        dev = field.device
+        return hipops.pose_scores(torch.from_numpy(x).to(dev), field.dist, field.origin, field.spacing,
+                                  torch.from_numpy(rot.reshape(-1, 9).astype(F32)).to(dev), c_src, field.centroid, shifts, shift_step, scale, cap)
+    return _pose_scores_numpy(x, field.dist, field.origin, field.spacing, rot, c_src, field.centroid, shifts, shift_step, scale, cap)
+
+
+def _rotation_angle(A, B):
+    """The angle of ``A^T B`` in degrees."""
+    return float(np.degrees(np.arccos(np.clip((np.trace(A.T @ B) - 1.0) / 2.0, -1.0, 1.0))))
+
+
+def _pose_select(order, scores, rotations, shifts, angle_step, candidates):
+    """Greedy choice among the candidates in rank order (``order``: flat indices ``r shifts^3 + k``, ``scores``: theirs): one is skipped
+    when an already chosen one has a relative rotation angle <= 1.5 ``angle_step`` AND grid offsets that differ by at most one step on
+    every axis; a NaN score ends the walk.  ``[(rank, flat index, r, (ax, ay, az), score)]``, at most ``candidates``."""
+    S3, chosen = shifts ** 3, []
+    for rank, (flat, sc) in enumerate(zip(order, scores)):
+        if len(chosen) == candidates or np.isnan(sc):
+            break
+        r, k = divmod(int(flat), S3)
+        a = np.array([k // (shifts * shifts), (k // shifts) % shifts, k % shifts])
+        if any(np.abs(a - c[3]).max() <= 1 and _rotation_angle(rotations[c[2]], rotations[r]) <= 1.5 * angle_step for c in chosen):
+            continue
+        chosen.append((rank, int(flat), r, a, float(sc)))
+    return chosen
+
+
+def global_align(source, verts, faces, angle_step=15.0, candidates=8, refine_iterations=20, samples=1024, shifts=1, shift_step=None,
+                 field=None, resolution=32, metric='plane', scale=False, trim=1.0, max_dist=None, search='tree', cap=None, grid=None):
+    """Pose-free alignment of ``source`` (points [N,3], or a ``(verts, faces)`` pair) to the mesh ``(verts, faces)``: a search over
+    candidate poses scored against the target's distance field, then ``align_mesh`` from the best few.
+
+    1. points: the finite rows of the source, and if there are more than ``samples`` of them, ``x[floor(i N / samples)]``;
+    2. ``s`` = 1, or with ``scale`` the rms radius of the target's vertices over that of these points (``init='centroid'``);
+    3. ``pose_scores`` of these points for ``pose_candidates(angle_step)`` and the ``shifts^3`` offsets (``field``: a ``PoseField`` of
+       the target, built here with ``resolution`` if None), ordered by (score, flat index), NaN last;
+    4. the first 4 096 of that order are walked greedily (``_pose_select``) until ``candidates`` are chosen;
+    5. each is refined by ``align_mesh`` on the points of step 1 from ``M = [s R | c_tgt + o - s R c_src]`` with ``refine_iterations``
+       and the call's ``metric / scale / trim / max_dist / search``; a start from which ICP fails counts as rms +inf;
+    6. the winner has the lowest final rms, the earlier rank among equals.
+
+    Returns the winner's ``align_mesh`` dict plus ``'candidates'`` (per refined candidate ``{'matrix'`` (its start), ``'score', 'index',
+    'rms', 'converged'}``), ``'searched'`` (R shifts^3), ``'rank'`` (the winner's place among the refined) and ``'field'``.  A
+    symmetric target has many equal optima; ``shifts > 1`` is an expert option (it did not help a partial source in the trial of
+    DESIGN.md 4.30).  Device tensors score on ia_pose_scores, order with ``torch.sort`` and read the head of the order once; CPU tensors
+    and NumPy arrays take the NumPy restatement.  Selection and refinement are the same host code for both."""
+    _closest_search(search)
+    if isinstance(source, (tuple, list)) and len(source) == 2 and getattr(source[0], 'ndim', 0) == 2:
+        source = source[0]
+    _mesh_args(verts, faces)
+    if source.ndim != 2 or source.shape[1] != 3:
+        raise ValueError(f'source must be points [N,3] or a (verts, faces) pair, got {tuple(source.shape)}')
+    if not faces.shape[0] or not verts.shape[0]:
+        raise ValueError('global_align: the target mesh is empty')
+    candidates, samples, shifts = int(candidates), int(samples), _pose_offsets(shifts)
+    if candidates < 1:
+        raise ValueError(f'candidates must be >= 1, got {candidates}')
+    if not 1 <= samples <= POSE_MAX_POINTS:
+        raise ValueError(f'samples must be in [1, {POSE_MAX_POINTS}], got {samples}')
+    on_dev = _is_device(verts)
+    if field is None:
+        field = PoseField(verts, faces, resolution)
+    elif not isinstance(field, PoseField):
+        raise ValueError(f'field must be a PoseField, got {type(field).__name__}')
+    if (field.n_verts, field.n_faces) != (int(verts.shape[0]), int(faces.shape[0])) or (field.device is not None) != on_dev:
+        raise ValueError(f'field was made for a mesh of {field.n_verts} vertices and {field.n_faces} faces '
+                         f'{"on the device" if field.device is not None else "on the host"}: not this target')
+    x = np.asarray(_np(source), dtype=F32).reshape(-1, 3)
+    x = x[np.isfinite(x).all(1)]
+    if not x.shape[0]:
+        raise ValueError('global_align: the source has no finite point')
+    if x.shape[0] > samples:
+        x = x[(np.arange(samples, dtype=np.int64) * x.shape[0]) // samples]
+    x = np.ascontiguousarray(x)
+    c_src = x.astype(np.float64).mean(0)
+    s = 1.0
+    if scale:
+        ra = float(np.sqrt(((x.astype(np.float64) - c_src) ** 2).sum(1).mean()))
+        if not (ra > 0 and field.radius > 0):
+            raise ValueError('global_align with scale needs point sets with an extent')
+        s = field.radius / ra
+    rotations = pose_candidates(angle_step)
+    step = field.spacing if shift_step is None else float(shift_step)
+    scores = pose_scores(x, field, rotations, shifts, step, s, cap)
+    if on_dev:
+        flat = scores.reshape(-1)
+        ordered = torch.sort(flat, stable=True)                                              # NaN last, equal scores by flat index
+        head = torch.stack([ordered.values[:_POSE_HEAD], ordered.indices[:_POSE_HEAD].double()]).cpu().numpy()      # the one host read
+        order, ranked = head[1].astype(np.int64), head[0]
+    else:
+        flat = scores.reshape(-1)
+        order = np.argsort(flat, kind='stable')[:_POSE_HEAD]                                  # NaN last, equal scores by flat index
+        ranked = flat[order]
+    chosen = _pose_select(order, ranked, rotations, shifts, float(angle_step), candidates)
+    if not chosen:
+        raise ValueError('global_align: no candidate pose has a score (is the source finite?)')
+    if on_dev and grid is None:
+        grid = TriangleGrid(verts, faces, build=search != 'tree')
+    src = torch.from_numpy(x).to(verts.device) if on_dev else x
+    half, best, tried = (shifts - 1) // 2, None, []
+    for _, flat_index, r, a, sc in chosen:
+        M = np.eye(4)
+        M[:3, :3] = s * rotations[r]
+        M[:3, 3] = field.centroid + (a - half) * step - M[:3, :3] @ c_src
+        try:
+            fit = align_mesh(src, verts, faces, metric=metric, scale=scale, iterations=refine_iterations, max_dist=max_dist, trim=trim, init=M,
+                             grid=grid, search=search)
+        except ValueError:
+            fit = None
+        tried.append({'matrix': M, 'score': sc, 'index': flat_index, 'rms': fit['rms'] if fit else float('inf'),
+                      'converged': bool(fit and fit['converged'])})
+        if fit is not None and (best is None or fit['rms'] < best[1]['rms']):
+            best = (len(tried) - 1, fit)
+    if best is None:
+        raise ValueError('global_align: ICP failed from every chosen candidate (too few pairs count: see max_dist and trim)')
+    return {**best[1], 'candidates': tried, 'searched': int(rotations.shape[0]) * shifts ** 3, 'rank': best[0], 'field': field}
 
 
 # ------------------------------------------------------------------ winding number, signed distance, mesh -> volume

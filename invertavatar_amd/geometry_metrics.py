@@ -8,7 +8,9 @@ the distance of its vertices to the ground truth (black = 0, red = the largest t
 ``--align-trim``, ``--align-init centroid`` set its arguments; the source points are the ``--samples`` area-weighted samples of the
 prediction when given, else its vertices), scores the moved mesh, adds an ``alignment`` block to the JSON and, with ``--save-aligned
 OUT.ply``, writes the moved mesh.  ICP finds the nearest local optimum: a prediction far from the ground truth needs ``--align-init
-centroid`` or a pose from landmarks (``geometry.fit_transform``).  ``--signed`` adds the signed numbers of
+centroid``, a pose from landmarks (``geometry.fit_transform``) or, for a prediction in another coordinate frame altogether,
+``--align-init global`` (``geometry.global_align``: ``--align-angle-step``, ``--align-candidates``, ``--align-shifts``; the ``alignment``
+block then also carries ``searched``, ``rank`` and ``candidate_scores``).  ``--signed`` adds the signed numbers of
 ``surface_distance(signed=True)`` (mean signed distance and inside share per direction: is the prediction inflated or deflated?) and
 colours ``--error-ply`` with a diverging map (blue inside the ground truth, red outside, white on it).  ``--iou RES`` adds a
 ``volume_iou`` block: the volumetric IoU of the two meshes on a lattice of ``RES`` points along the longest axis.  ``--winding tree``
@@ -70,9 +72,13 @@ def align_prediction(verts, faces, ref_verts, ref_faces, align, samples=None, se
 def alignment_block(fit):
     """The JSON form of an ``align_mesh`` result."""
     cos = min(1.0, max(-1.0, (float(np.trace(fit['rotation'])) - 1.0) / 2.0))
-    return {'matrix': [[float(x) for x in row] for row in fit['matrix']], 'scale': float(fit['scale']), 'angle_deg': math.degrees(math.acos(cos)),
-            'shift': float(np.linalg.norm(fit['translation'])), 'rms_before': float(fit['rms_history'][0]), 'rms_after': float(fit['rms']),
-            'iterations': int(fit['iterations']), 'converged': bool(fit['converged']), 'inliers': int(fit['inliers'])}
+    block = {'matrix': [[float(x) for x in row] for row in fit['matrix']], 'scale': float(fit['scale']), 'angle_deg': math.degrees(math.acos(cos)),
+             'shift': float(np.linalg.norm(fit['translation'])), 'rms_before': float(fit['rms_history'][0]), 'rms_after': float(fit['rms']),
+             'iterations': int(fit['iterations']), 'converged': bool(fit['converged']), 'inliers': int(fit['inliers'])}
+    if 'global' in fit:                                                    # init='global': what the pose search did
+        g = fit['global']
+        block.update(searched=int(g['searched']), rank=int(g['rank']), candidate_scores=[float(c['score']) for c in g['candidates']])
+    return block
 
 
 def fit_prediction(verts, faces, ref_verts, ref_faces, options=None):
@@ -175,11 +181,18 @@ def add_align_arguments(ap):
     ap.add_argument('--align-metric', default='plane', choices=['point', 'plane'])
     ap.add_argument('--align-iterations', type=int, default=30)
     ap.add_argument('--align-trim', type=float, default=1.0, help='share of the closest pairs that count (1: all)')
-    ap.add_argument('--align-init', default='identity', choices=['identity', 'centroid'])
+    ap.add_argument('--align-init', default='identity', choices=['identity', 'centroid', 'global'],
+                    help='the start of ICP; global: a pose search over the reference\'s distance field (geometry.global_align)')
+    ap.add_argument('--align-angle-step', type=float, default=15.0, metavar='DEG', help='with --align-init global: spacing of the candidate rotations')
+    ap.add_argument('--align-candidates', type=int, default=8, help='with --align-init global: candidates refined by ICP')
+    ap.add_argument('--align-shifts', type=int, default=1, help='with --align-init global: offsets per axis around the centroid (odd; expert option)')
 
 
 def align_options_of(args):
-    return {'metric': args.align_metric, 'iterations': args.align_iterations, 'trim': args.align_trim, 'init': args.align_init}
+    opts = {'metric': args.align_metric, 'iterations': args.align_iterations, 'trim': args.align_trim, 'init': args.align_init}
+    if args.align_init == 'global':
+        opts['global_options'] = {'angle_step': args.align_angle_step, 'candidates': args.align_candidates, 'shifts': args.align_shifts}
+    return opts
 
 
 def add_fit_arguments(ap, flag=True):

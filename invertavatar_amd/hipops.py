@@ -1787,6 +1787,47 @@ def align_sums(src, dst, dist, face, centre, max_dist=float('inf'), metric='poin
     return out
 
 
+# ------------------------------------------------------------------ pose search (csrc/pose_search.hip)
+
+POSE_MAX_POINTS = 4096       # csrc/pose_search.hip kMaxPoints
+POSE_SLAB = 1 << 16          # candidate rotations per launch; a score does not depend on the cut
+
+
+def pose_scores(points, dist, origin, spacing, rotations, c_src, c_tgt, shifts=1, shift_step=None, scale=1.0, cap=float('inf')):
+    """The score of every candidate pose (see ia_pose_scores): points float32 [n,3] (n <= 4096), dist float32 [nx,ny,nz] the distance
+    lattice with ``origin`` (three floats) and ``spacing`` (one float), rotations float32 [R,9], ``c_src`` / ``c_tgt`` three floats on
+    the host -> float64 device tensor [R, shifts^3].  R is cut into slabs of POSE_SLAB; n = 0 gives NaN (a mean over nothing) and
+    R = 0 an empty tensor, both without a launch."""
+    _f32c(points, 'points')
+    _f32c(rotations, 'rotations')
+    nx, ny, nz = _volume_checked(dist)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'points must be [n,3], got {tuple(points.shape)}')
+    if rotations.dim() != 2 or rotations.shape[1] != 9 or not (rotations.device == dist.device == points.device):
+        raise RuntimeError(f'rotations must be [R,9] on the device of the points and the lattice, got {tuple(rotations.shape)}')
+    shifts = int(shifts)
+    n, r, dev = points.shape[0], rotations.shape[0], points.device
+    if n > POSE_MAX_POINTS:
+        raise ValueError(f'pose_scores takes at most {POSE_MAX_POINTS} points, got {n}: score a subset (samples=)')
+    if shifts < 1 or shifts % 2 == 0:
+        raise ValueError(f'shifts must be odd and >= 1, got {shifts}')
+    s3 = shifts ** 3
+    step = float(spacing) if shift_step is None else float(shift_step)
+    if n == 0 or r == 0:
+        return torch.full((r, s3), float('nan'), dtype=torch.float64, device=dev)
+    out = torch.empty(r, s3, dtype=torch.float64, device=dev)
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    lib = _lib.load()
+    for r0 in range(0, r, POSE_SLAB):
+        rows = min(POSE_SLAB, r - r0)
+        lookups = float(rows) * s3 * n
+        with torch.cuda.device(dev), _Timed('pose_scores', 40.0 * lookups, 32.0 * lookups, f'R={rows} n={n} shifts={shifts}'):
+            st = lib.ia_pose_scores(_p(points), n, _p(dist), nx, ny, nz, org, float(spacing), _p(rotations[r0:r0 + rows]), rows, _d3(c_src),
+                                    _d3(c_tgt), shifts, step, float(scale), float(cap), _p(out[r0:r0 + rows]), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_pose_scores')
+    return out
+
+
 # ------------------------------------------------------------------ non-rigid fitting (csrc/nonrigid.hip)
 
 def _f64c(t, what, shape):

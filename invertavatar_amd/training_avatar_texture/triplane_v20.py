@@ -557,7 +557,7 @@ class TriPlaneGenerator(torch.nn.Module):
         FINAL mesh (after ``keep``, ``simplify`` and ``smooth``) into a texture atlas: 'texture' [size,size,3], 'uv' float32 [F,3,2],
         'atlas' and 'texture_info' {'filled', 'mask' and, from views, 'views'}.  ``fit_template`` (None: nothing changes; a ``(verts,
         faces)`` pair; or a dict with 'verts', 'faces', optionally 'align' (``'rigid'`` or ``'similarity'``: ``geometry.align_mesh`` from
-        ``init='centroid'`` first) and ``geometry.nonrigid_align`` keyword arguments) wraps that template onto the FINAL mesh: 'template'
+        ``init='centroid'`` first, or with 'align_init': 'global' from a pose search) and ``geometry.nonrigid_align`` keyword arguments) wraps that template onto the FINAL mesh: 'template'
         holds {'verts' (the template's vertices on the avatar's shape), 'faces' (the template's own), 'fit' (``nonrigid_align``'s result),
         with ``with_colors`` 'colors' (queried at the fitted vertices) and with 'align' 'alignment' (``align_mesh``'s result)}: one fixed
         topology for every seed.  The planes are computed once per call; device tensors stay on the device throughout."""
@@ -607,11 +607,13 @@ class TriPlaneGenerator(torch.nn.Module):
                 kw = dict(fit_template) if isinstance(fit_template, dict) else {'verts': fit_template[0], 'faces': fit_template[1]}
                 tv = torch.as_tensor(kw.pop('verts')).to(verts.device).float().contiguous()
                 tf = torch.as_tensor(kw.pop('faces')).to(verts.device)
-                how, wrapped = kw.pop('align', None), {'faces': tf}
+                how, start, wrapped = kw.pop('align', None), kw.pop('align_init', 'centroid'), {'faces': tf}
                 if how is not None:
                     if how not in ('rigid', 'similarity'):
                         raise ValueError(f"fit_template['align'] must be None, 'rigid' or 'similarity', got {how!r}")
-                    wrapped['alignment'] = geometry.align_mesh((tv, tf), verts, faces, scale=how == 'similarity', init='centroid',
+                    if start not in ('centroid', 'global'):
+                        raise ValueError(f"fit_template['align_init'] must be 'centroid' or 'global', got {start!r}")
+                    wrapped['alignment'] = geometry.align_mesh((tv, tf), verts, faces, scale=how == 'similarity', init=start,
                                                                **({'search': kw['search']} if 'search' in kw else {}))
                     tv = geometry.transform_points(tv, wrapped['alignment']['matrix'])
                 wrapped['fit'] = geometry.nonrigid_align((tv, tf), verts, faces, **kw)

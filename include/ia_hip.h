@@ -1453,6 +1453,30 @@ int ia_nonrigid_solve(int64_t V, const int* offsets, const int* neighbors, int64
                       double* out, void* stream);
 int ia_nonrigid_apply(const float* x, const double* d, const unsigned char* pinned, int64_t V, float* verts, void* stream);
 
+/* ---- a set of frames as a distribution (csrc/distribution.hip; the definitions are in distribution_metrics.py) ----
+ * All four work on feature sets, float32 [rows, D] row-major and contiguous.  No floating-point atomics: the same call gives the same bits.
+ * ia_feature_moments: sum [D] += sum_r x[r,:] and cov [D,D] += sum_r x[r,:] x[r,:]^T for the n rows of one chunk, in double (the
+ * products of float32 values are exact in double).  One wave owns a 32 x 32 block of the lower triangle, adds the rows in order, four per
+ * v_mfma_f64_16x16x4_f64, and writes the block and its mirror: cov stays symmetric bit for bit.  1 <= D <= 4096; n = 0 does nothing.
+ * sum and cov are read and written: the caller zeroes them before the first chunk.
+ * ia_kid_subsets: for subset s with rows x_i = gen[idx_gen[s,i]], y_i = real[idx_real[s,i]] (i < m; the indices must be in range, the
+ * kernel does not know the sets' sizes) and k(u, v) = (u . v / D + 1)^3:
+ *     out[s,0] = sum_{i != j} k(x_i, x_j),  out[s,1] = sum_{i != j} k(y_i, y_j),  out[s,2] = sum_{i,j} k(x_i, y_j).
+ * i != j is by position in the subset.  The dot products are fp32 (v_mfma_f32_32x32x2_f32, channels in ascending order); the division,
+ * the cube (t t) t and the sums are double: a lane adds its elements in order, a wave its 128 x 128 tiles in order (an off-diagonal
+ * tile of a symmetric block counts twice), then the butterfly and the four waves in order.  A subset's three numbers depend on its rows
+ * alone: the same bits for any S and any position in the call.
+ * ia_knn_radius: r2[j] = the (k + 1)-th smallest of d2(j, i) over all i < N, i = j included and duplicates counted; 0 <= k <= 15, N > k.
+ * ia_manifold_covered: covered[p] = 1 iff d2(probe p, manifold j) <= r2[j] for some j < N, else 0.
+ * In both d2(a, b) = sum_c (a_c - b_c)^2 in the difference form: the difference rounded to fp32, then fmaf into the sum, c ascending.
+ */
+int ia_feature_moments(const float* x, int64_t n, int D, double* sum, double* cov, void* stream);
+int ia_kid_subsets(const float* gen, const float* real, int D, const int* idx_gen, const int* idx_real, int S, int m, double* out,
+                   void* stream);
+int ia_knn_radius(const float* feat, int64_t N, int D, int k, float* r2, void* stream);
+int ia_manifold_covered(const float* probes, int64_t P, const float* manifold, const float* r2, int64_t N, int D, unsigned char* covered,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

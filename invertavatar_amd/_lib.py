@@ -213,6 +213,10 @@ _SIGNATURES = {
     'ia_nonrigid_solve': [c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int] + [c_void_p] * 5 + [ctypes.c_double, ctypes.c_double, c_void_p,
                          c_int, ctypes.c_double, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     'ia_nonrigid_apply': [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_feature_moments': [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
+    'ia_kid_subsets': [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    'ia_knn_radius': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
+    'ia_manifold_covered': [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p],
 }
 
 

@@ -2872,3 +2872,93 @@ def cx_head(fx, fy, band_width=0.5, mu='frame', debug=False):
         return cx, loss, {'mu': table, 'xh': xh, 'yh': yh, 'm': m.reshape(n, p).clone(), 's': s.reshape(n, p).clone(),
                           'colmax': colmax.reshape(n, p).clone()}
     return cx, loss
+
+
+# ------------------------------------------------------------------ distribution scores (csrc/distribution.hip)
+
+MOMENTS_MAX_D = 4096         # csrc/distribution.hip kMomMaxD
+KNN_MAX_K = 15               # csrc/distribution.hip kPrMaxK
+
+
+def _features_checked(x, what):
+    _f32c(x, what)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f'{what} must be [rows, D] with D >= 1, got {tuple(x.shape)}')
+    return x
+
+
+def feature_moments(x, raw_sum, raw_cov):
+    """ia_feature_moments: adds the column sums and the second moments x^T x of the chunk x (float32 [n,D], D <= 4096) into the running
+    float64 device tensors raw_sum [D] and raw_cov [D,D], in place."""
+    _features_checked(x, 'x')
+    n, d = x.shape
+    if d > MOMENTS_MAX_D:
+        raise ValueError(f'feature_moments takes at most {MOMENTS_MAX_D} features, got {d}')
+    _f64c(raw_sum, 'raw_sum', (d,)), _f64c(raw_cov, 'raw_cov', (d, d))
+    if not (raw_sum.device == raw_cov.device == x.device):
+        raise RuntimeError('feature_moments: x, raw_sum and raw_cov must be on one device')
+    if n == 0:
+        return
+    with torch.cuda.device(x.device), _Timed('feature_moments', float(n) * d * (d + 1), 4.0 * n * d + 16.0 * d * d, f'n={n} D={d}'):
+        st = _lib.load().ia_feature_moments(_p(x), n, d, _p(raw_sum), _p(raw_cov), _lib.stream_ptr(x.device))
+    _lib.check(st, 'ia_feature_moments')
+
+
+def kid_subsets(gen, real, idx_gen, idx_real):
+    """ia_kid_subsets: gen [Ng,D], real [Nr,D] float32 on the device; idx_gen, idx_real integer [S,m] arrays ON THE HOST (NumPy or CPU
+    tensors: they are checked against Ng / Nr here, where that costs no synchronisation) -> float64 device tensor [S,3]."""
+    _features_checked(gen, 'gen'), _features_checked(real, 'real')
+    if gen.shape[1] != real.shape[1] or gen.device != real.device:
+        raise RuntimeError(f'kid_subsets: gen and real must share D and the device, got {tuple(gen.shape)} and {tuple(real.shape)}')
+    ig, ir = torch.as_tensor(idx_gen), torch.as_tensor(idx_real)
+    if ig.is_cuda or ir.is_cuda or ig.dim() != 2 or ig.shape != ir.shape or ig.is_floating_point() or ir.is_floating_point():
+        raise RuntimeError('kid_subsets: idx_gen and idx_real must be host integer arrays of one shape [S,m]')
+    s, m = ig.shape
+    if m < 1:
+        raise ValueError('kid_subsets: a subset needs at least one row')
+    out = torch.empty(s, 3, dtype=torch.float64, device=gen.device)
+    if s == 0:
+        return out
+    if int(ig.min()) < 0 or int(ig.max()) >= gen.shape[0] or int(ir.min()) < 0 or int(ir.max()) >= real.shape[0]:
+        raise ValueError(f'kid_subsets: an index is outside its set ({gen.shape[0]} generated, {real.shape[0]} real rows)')
+    ig = ig.to(torch.int32).contiguous().to(gen.device, non_blocking=True)
+    ir = ir.to(torch.int32).contiguous().to(gen.device, non_blocking=True)
+    d = gen.shape[1]
+    with torch.cuda.device(gen.device), _Timed('kid_subsets', 6.0 * s * m * m * d, 8.0 * s * m * d, f'S={s} m={m} D={d}'):
+        st = _lib.load().ia_kid_subsets(_p(gen), _p(real), d, _p(ig), _p(ir), s, m, _p(out), _lib.stream_ptr(gen.device))
+    _lib.check(st, 'ia_kid_subsets')
+    return out
+
+
+def knn_radius(feat, k):
+    """ia_knn_radius: feat float32 [N,D] -> float32 [N], the squared distance from each row to its (k + 1)-th nearest row, itself included."""
+    _features_checked(feat, 'feat')
+    n, d = feat.shape
+    k = int(k)
+    if not 0 <= k <= KNN_MAX_K:
+        raise ValueError(f'knn_radius: k must be in [0, {KNN_MAX_K}], got {k}')
+    if n <= k:
+        raise ValueError(f'knn_radius: {n} rows have no neighbour number {k}')
+    r2 = torch.empty(n, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device), _Timed('knn_radius', 3.0 * n * n * d, 4.0 * n * d, f'N={n} D={d} k={k}'):
+        st = _lib.load().ia_knn_radius(_p(feat), n, d, k, _p(r2), _lib.stream_ptr(feat.device))
+    _lib.check(st, 'ia_knn_radius')
+    return r2
+
+
+def manifold_covered(probes, manifold, r2):
+    """ia_manifold_covered: probes [P,D], manifold [N,D], r2 [N] float32 -> bool [P]: the probe lies within some manifold row's radius."""
+    _features_checked(probes, 'probes'), _features_checked(manifold, 'manifold'), _f32c(r2, 'r2')
+    if probes.shape[1] != manifold.shape[1] or tuple(r2.shape) != (manifold.shape[0],) or manifold.shape[0] < 1 \
+            or not (probes.device == manifold.device == r2.device):
+        raise RuntimeError(f'manifold_covered: probes [P,D], manifold [N,D] (N >= 1) and r2 [N] on one device, got {tuple(probes.shape)}, '
+                           f'{tuple(manifold.shape)}, {tuple(r2.shape)}')
+    p, d = probes.shape
+    n = manifold.shape[0]
+    covered = torch.zeros(p, dtype=torch.uint8, device=probes.device)
+    if p == 0:
+        return covered.bool()
+    with torch.cuda.device(probes.device), _Timed('manifold_covered', 3.0 * p * n * d, 4.0 * (p + n) * d, f'P={p} N={n} D={d}'):
+        st = _lib.load().ia_manifold_covered(_p(probes), p, _p(manifold), _p(r2), n, d, _p(covered), _lib.stream_ptr(probes.device))
+    _lib.check(st, 'ia_manifold_covered')
+    return covered.bool()

@@ -1477,6 +1477,40 @@ int ia_knn_radius(const float* feat, int64_t N, int D, int k, float* r2, void* s
 int ia_manifold_covered(const float* probes, int64_t P, const float* manifold, const float* r2, int64_t N, int D, unsigned char* covered,
                         void* stream);
 
+/*
+ * Point clouds on the cluster tree: k nearest points and normals (csrc/point_tree.hip; no counterpart in the reference; definitions:
+ * geometry._nearest_numpy, _nearest_tree_numpy, _point_tree_numpy and _point_normals_numpy).  Additive entry points:
+ * the ABI version is unchanged.
+ *
+ * The tree is the level layout of ia_winding_tree_plan over points: the usable (finite) points in the stable ascending order of
+ * ia_winding_tree_point_keys (cube: the box of the usable points), L points per leaf, B nodes per parent.
+ * ia_point_tree_gather: sorted float4 [n_usable] with sorted[s] = (points[order[s]].xyz, the bits of the int32 order[s]).
+ * ia_point_tree_boxes: the rows of ia_tree_boxes over the sorted points: exact min / max, bit-equal run to run.
+ * ia_nearest_points_brute: for queries float32 [N,3], dist float32 [N,k] and index int32 [N,k] (input indices).  In fp32 with every
+ * operation rounded on its own, d2 = (dx dx + dy dy) + dz dz with dx = x.x - p.x, ...; the result is the k smallest pairs (d2, index)
+ * over all usable points other than exclude[i] (int32 [N], or NULL), ascending; dist = sqrt(d2), correctly rounded.  A place is
+ * +inf / -1 where the cloud has no further point or dist > max_dist (+inf: no limit), and throughout for a non-finite query.
+ * ia_nearest_points_tree: the same bits by the walk of ia_closest_point_tree.  A node is skipped iff lb > the lane's k-th d2 (strictly;
+ * +inf while the list is not full), lb = the expression of d2 on g = max(lo - p, 0, p - hi) per axis: rounding is monotone, so
+ * lb <= d2 of every point of the box and no margin is needed.  counts (int32 [N,2], or NULL): boxes tested and leaves taken, the first
+ * descent included.  1 <= k <= 32 (lists of 1, 4, 8, 16 or 32 places in registers; k is rounded up, which changes no bit),
+ * N >= 0 with 3 N < 2^31 and N k < 2^31, 0 <= n_usable <= 2^25, n_nodes that of ia_winding_tree_plan.
+ * ia_point_normals: for points float32 [n,3] and index int32 [n,k] (ia_nearest_points_*; entries outside [0, n) are left out), per
+ * point in double: the mean of the neighbours added in order, the covariance (xx xy xz yy yz zz) of the differences added in order and
+ * divided by their number m, and its eigen-decomposition by 8 cyclic Jacobi sweeps over (0,1) (0,2) (1,2).  eigenvalues double [n,3]
+ * ascending, covariance double [n,6], normal float32 [n,3] = the unit eigenvector of the smallest, its largest-magnitude component
+ * positive, variation float32 [n] = l0 / ((l0 + l1) + l2); normal and variation are 0 where m < 3 or the trace is not positive.
+ * One thread per point, no atomics: bit-equal run to run.
+ */
+int ia_point_tree_gather(const float* points, int64_t n, const int* order, int64_t n_usable, void* sorted, void* stream);
+int ia_point_tree_boxes(const void* sorted, int64_t n_usable, void* boxes, int64_t n_nodes, void* stream);
+int ia_nearest_points_brute(const float* queries, int64_t N, const void* sorted, int64_t n_usable, int k, float max_dist,
+                            const int* exclude, float* dist, int* index, void* stream);
+int ia_nearest_points_tree(const float* queries, int64_t N, const void* sorted, int64_t n_usable, const void* boxes, int64_t n_nodes,
+                           int k, float max_dist, const int* exclude, float* dist, int* index, int* counts, void* stream);
+int ia_point_normals(const float* points, int64_t n, const int* index, int k, float* normal, float* variation, double* eigenvalues,
+                     double* covariance, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,11 @@ _SIGNATURES = {
     'ia_kid_subsets': [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     'ia_knn_radius': [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p],
     'ia_manifold_covered': [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p],
+    'ia_point_tree_gather': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    'ia_point_tree_boxes': [c_void_p, c_int64, c_void_p, c_int64, c_void_p],
+    'ia_nearest_points_brute': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    'ia_nearest_points_tree': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float] + [c_void_p] * 5,
+    'ia_point_normals': [c_void_p, c_int64, c_void_p, c_int] + [c_void_p] * 5,
 }
 
 

@@ -103,6 +103,15 @@ template <class T> __device__ __forceinline__ Vec3<T> cross(Vec3<T> a, Vec3<T> b
 }
 template <class T> __device__ __forceinline__ bool finite3(Vec3<T> a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
 
+// Squared distance of the pair (query p, point x) of the nearest-point queries (point_tree.hip; geometry._pair_d2 in NumPy): three
+// differences, three squares and two sums, every operation rounded on its own.  box_d2: the same expression on the gaps between p and
+// the box [lo, hi]; it never exceeds pair_d2(p, x) for a point x of the box.
+__device__ __forceinline__ float gaps_d2(float dx, float dy, float dz) { return (dx * dx + dy * dy) + dz * dz; }
+__device__ __forceinline__ float pair_d2(Vec3<float> p, Vec3<float> x) { return gaps_d2(x.x - p.x, x.y - p.y, x.z - p.z); }
+__device__ __forceinline__ float box_d2(Vec3<float> p, float4 lo, float4 hi) {
+    return gaps_d2(fmaxf(fmaxf(lo.x - p.x, 0.f), p.x - hi.x), fmaxf(fmaxf(lo.y - p.y, 0.f), p.y - hi.y), fmaxf(fmaxf(lo.z - p.z, 0.f), p.z - hi.z));
+}
+
 // Signed solid angle of triangle A B C seen from p (the per-pair function of the winding number, winding.hip): relative to the query,
 // the numerator from the edges; every operation rounded on its own.  A triangle without area gives atan2f(0, den >= 0) = 0.
 __device__ __forceinline__ float solid_angle(Vec3<float> p, Vec3<float> A, Vec3<float> B, Vec3<float> C) {

@@ -865,7 +865,51 @@ def _sample_set(verts, faces, samples, seed, points):
     return pts, nrm[idx]
 
 
-def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, thresholds=None, points_a=None, points_b=None,
+def _distance_report(s_ab, s_ba, thresholds, with_normals=False):
+    """The result of ``surface_distance`` from the two rows of ia_distance_stats."""
+    def direction(s):
+        cnt = s[0]
+        if cnt == 0:
+            return float('nan'), float('nan'), float('nan'), float('nan'), [0.0] * len(thresholds)
+        return s[1] / cnt, s[2] / cnt, float(np.sqrt(s[2] / cnt)), s[3], [float(s[6 + k] / cnt) for k in range(len(thresholds))]
+    mean_ab, sq_ab, rms_ab, max_ab, prec = direction(s_ab)
+    mean_ba, sq_ba, rms_ba, max_ba, rec = direction(s_ba)
+    res = {'mean_ab': float(mean_ab), 'rms_ab': rms_ab, 'max_ab': float(max_ab), 'mean_ba': float(mean_ba), 'rms_ba': rms_ba,
+           'max_ba': float(max_ba), 'chamfer': float((mean_ab + mean_ba) / 2), 'chamfer_sq': float(sq_ab + sq_ba),
+           'hausdorff': float(max(max_ab, max_ba)), 'thresholds': thresholds, 'precision': prec, 'recall': rec,
+           'fscore': [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(prec, rec)],
+           'normal_consistency': None, 'n_a': int(s_ab[0] + s_ab[5]), 'n_b': int(s_ba[0] + s_ba[5]),
+           'skipped_ab': int(s_ab[5]), 'skipped_ba': int(s_ba[5])}
+    if with_normals and s_ab[0] + s_ba[0] > 0:
+        res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
+    return res
+
+
+def _surface_cloud_distance(verts_a, faces_a, verts_b, faces_b, samples, seed, thresholds, points_a, points_b, search):
+    """``surface_distance`` with a cloud on either side: the distance to a cloud is ``nearest_points`` (k = 1), the distance to a mesh
+    ``closest_point``; the sample set of a cloud is its points (or the points given)."""
+    thresholds = _cloud_thresholds(thresholds, verts_a, verts_b)
+    on_dev = _is_device(verts_a)
+    if on_dev != _is_device(verts_b):
+        raise ValueError('both sides must be device tensors or both be on the host')
+    sides = ((verts_a, faces_a, points_a, seed), (verts_b, faces_b, points_b, seed + 1))
+    pts = [(p if p is not None else v) if f is None else _sample_set(v, f, samples, s, p)[0] for v, f, p, s in sides]
+    stats = []
+    for own, (v, f, _, _) in ((pts[0], sides[1]), (pts[1], sides[0])):
+        if f is None:
+            stats.append(_cloud_stats(own, v, thresholds))
+            continue
+        _mesh_args(v, f)
+        dist = closest_point(own, v, f, search=search)['dist']
+        if on_dev:
+            from . import hipops
+            stats.append(hipops.distance_stats(dist.contiguous(), thresholds).cpu().numpy())
+        else:
+            stats.append(_stats_numpy(_np(dist), thresholds))
+    return _distance_report(stats[0], stats[1], thresholds)
+
+
+def surface_distance(verts_a, faces_a, verts_b, faces_b=None, samples=None, seed=0, thresholds=None, points_a=None, points_b=None,
                      signed=False, winding='exact', beta=2.0, search='grid'):
     """How far surface a is from surface b.  The sample set of each mesh is its vertices (``samples=None``), ``samples`` area-weighted
     points (``sample_surface`` with ``seed`` for a and ``seed + 1`` for b) or the points given (``points_a`` / ``points_b``).  With
@@ -890,7 +934,16 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
     ``winding='tree'`` the one ``WindingTree`` per mesh serves both): the choice for meshes that do not overlap.
 
     Device meshes run on the kernels (one ``TriangleGrid`` per mesh, ia_distance_stats for the sums); CPU tensors and NumPy arrays take
-    the NumPy restatements."""
+    the NumPy restatements.
+
+    ``faces_b=None`` (or ``faces_a=None``) makes that side a point cloud: its sample set is its points (or ``points_b``), the distance
+    to it is that to its nearest point (``nearest_points``), the distance to a mesh stays ``closest_point``; ``normal_consistency`` is
+    None, and ``signed`` needs two surfaces."""
+    if faces_a is None or faces_b is None:
+        if signed:
+            raise ValueError('signed=True needs a surface on both sides: a point cloud has no inside')
+        _closest_search(search)
+        return _surface_cloud_distance(verts_a, faces_a, verts_b, faces_b, samples, seed, thresholds, points_a, points_b, search)
     _mesh_args(verts_a, faces_a)
     _mesh_args(verts_b, faces_b)
     _winding_method(winding, 'winding')
@@ -939,22 +992,7 @@ def surface_distance(verts_a, faces_a, verts_b, faces_b, samples=None, seed=0, t
                 sides.append((r['dist'], tree.query(_np(pts), beta) if use_tree else _winding_numpy(_np(pts), _np(v), _np(f))[0]))
             out.append(_stats_numpy(r['dist'], thresholds, *((r['face'], _np(nrm), _np(fn)) if nrm is not None else ())))
         s_ab, s_ba = out
-
-    def direction(s):
-        cnt = s[0]
-        if cnt == 0:
-            return float('nan'), float('nan'), float('nan'), float('nan'), [0.0] * len(thresholds)
-        return s[1] / cnt, s[2] / cnt, float(np.sqrt(s[2] / cnt)), s[3], [float(s[6 + k] / cnt) for k in range(len(thresholds))]
-    mean_ab, sq_ab, rms_ab, max_ab, prec = direction(s_ab)
-    mean_ba, sq_ba, rms_ba, max_ba, rec = direction(s_ba)
-    res = {'mean_ab': float(mean_ab), 'rms_ab': rms_ab, 'max_ab': float(max_ab), 'mean_ba': float(mean_ba), 'rms_ba': rms_ba,
-           'max_ba': float(max_ba), 'chamfer': float((mean_ab + mean_ba) / 2), 'chamfer_sq': float(sq_ab + sq_ba),
-           'hausdorff': float(max(max_ab, max_ba)), 'thresholds': thresholds, 'precision': prec, 'recall': rec,
-           'fscore': [2 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(prec, rec)],
-           'normal_consistency': None, 'n_a': int(s_ab[0] + s_ab[5]), 'n_b': int(s_ba[0] + s_ba[5]),
-           'skipped_ab': int(s_ab[5]), 'skipped_ba': int(s_ba[5])}
-    if na is not None and nb is not None and s_ab[0] + s_ba[0] > 0:
-        res['normal_consistency'] = float((s_ab[4] / max(s_ab[0], 1) + s_ba[4] / max(s_ba[0], 1)) / 2)
+    res = _distance_report(s_ab, s_ba, thresholds, na is not None and nb is not None)
     if signed:
         for tag, (dist, w) in zip(('ab', 'ba'), sides):
             d, w = _np(dist).astype(np.float64).reshape(-1), _np(w).reshape(-1)
@@ -1202,6 +1240,65 @@ def _align_numpy(src, verts, faces, M0, metric, scale, iterations, tol, max_dist
     return _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol)
 
 
+def _cloud_normals(points, normals, normals_k, metric):
+    """The per-point normals of the plane metric against a cloud: those given, or ``estimate_normals(k=normals_k)``."""
+    if metric != 'plane':
+        return None
+    if normals is None:
+        return estimate_normals(points, normals_k)['normal']
+    if tuple(normals.shape) != tuple(points.shape):
+        raise ValueError(f'normals must be one row per target point, got {tuple(normals.shape)} for {tuple(points.shape)}')
+    return normals
+
+
+def _align_cloud_numpy(src, points, normals, M0, metric, scale, iterations, tol, max_dist, trim, dtype=np.float64):
+    """``_align_numpy`` against a point cloud: the pairing is ``nearest_points(k=1)``, q the nearest point, face its index, and the
+    plane metric reads the per-point ``normals``; everything else is the same."""
+    src, points = np.asarray(src, dtype=F32).reshape(-1, 3), np.asarray(points, dtype=F32).reshape(-1, 3)
+    fin = _finite_rows(points)
+    if not fin.shape[0]:
+        raise ValueError('align_mesh: the target cloud is empty')
+    lo, hi = fin.min(0).astype(np.float64), fin.max(0).astype(np.float64)
+    centre, extent = (lo + hi) / 2, float(max(np.abs(lo).max(), np.abs(hi).max()))
+    normals = None if normals is None else np.asarray(normals, dtype=F32).reshape(-1, 3)
+    tree = PointTree(points)
+
+    def pair(M):
+        p = _transform_numpy(src, M)
+        dist, index = _nearest_tree_numpy(p, tree, 1, dtype=dtype)
+        dist, face = dist[:, 0], index[:, 0]
+        q = np.where(face[:, None] >= 0, points[np.maximum(face, 0)], F32(np.nan)).astype(dtype)
+        return _align_sums_numpy(p, q, dist, face, normals, centre, _trim_threshold_numpy(dist, face, max_dist, trim), metric)
+    return _align_loop(pair, centre, extent, M0, metric, scale, iterations, tol)
+
+
+def _align_cloud_device(src, points, normals, M0, metric, scale, iterations, tol, max_dist, trim):
+    from . import hipops
+    tree = PointTree(points)
+    if not tree.usable:
+        raise ValueError('align_mesh: the target cloud is empty')
+    dev = tree.device
+    src = src.detach().to(dev).float().reshape(-1, 3).contiguous()
+    centre = [(float(a) + float(b)) / 2 for a, b in zip(tree.box_lo, tree.box_hi)]
+    normals = None if normals is None else normals.detach().to(dev).float().contiguous()
+    base = float('inf') if max_dist is None else float(F32(max_dist))
+
+    def pair(M):
+        p = hipops.transform_points(src, M)
+        r = tree.nearest(p, 1)
+        dist, face = r['dist'][:, 0].contiguous(), r['index'][:, 0].contiguous()
+        q = torch.where((face >= 0)[:, None], tree.points[face.clamp(min=0).long()], torch.full_like(p, float('nan'))).contiguous()
+        thr = base
+        if trim < 1.0:
+            d = torch.where(torch.isfinite(dist) & (face >= 0), dist, torch.full_like(dist, float('inf'))).sort().values
+            n_fin = torch.isfinite(d).sum()
+            k = torch.ceil(trim * n_fin.double()).long().clamp(1, max(d.numel(), 1))
+            if d.numel():
+                thr = min(base, float(d[k - 1]))
+        return hipops.align_sums(p, q, dist, face, centre, thr, metric, normals).cpu().numpy()
+    return _align_loop(pair, np.asarray(centre), float(tree.extent), M0, metric, scale, iterations, tol)
+
+
 def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dist, trim, grid, search='grid'):
     from . import hipops
     if not faces.shape[0] or not verts.shape[0]:
@@ -1230,8 +1327,8 @@ def _align_device(src, verts, faces, M0, metric, scale, iterations, tol, max_dis
     return _align_loop(pair, np.asarray(centre), float(grid.extent), M0, metric, scale, iterations, tol)
 
 
-def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30, tol=1e-6, max_dist=None, trim=1.0, init='identity',
-               grid=None, search='grid', global_options=None):
+def align_mesh(source, verts, faces=None, metric='plane', scale=False, iterations=30, tol=1e-6, max_dist=None, trim=1.0, init='identity',
+               grid=None, search='grid', global_options=None, normals=None, normals_k=16):
     """Align ``source`` (points [N,3], or a ``(verts, faces)`` pair whose vertices are used) to the triangle mesh ``(verts, faces)`` by
     iterated closest points: the rigid (``scale=False``) or similarity transform ``y = s R x + t`` that brings the points onto the
     surface, as a float64 4x4 ``M`` with ``M[:3,:3] = s R``, ``M[:3,3] = t``.  ICP finds the local optimum nearest to the start, so the
@@ -1260,13 +1357,26 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
 
     ``init='global'`` needs no start: ``M_0 = global_align(...)['matrix']`` with this call's ``metric / scale / trim / max_dist /
     search`` and ``global_options`` (a dict of its other arguments: ``angle_step``, ``candidates``, ``shifts``, ``field``, ...), then the
-    loop above; the result gains ``'global': {'candidates', 'searched', 'rank'}``."""
+    loop above; the result gains ``'global': {'candidates', 'searched', 'rank'}``.
+
+    ``faces=None``: the target is the point cloud ``verts``.  Step 2 becomes ``nearest_points(k=1)`` on one ``PointTree``: ``q_i`` is
+    the nearest point and ``f_i`` its index; the plane metric reads the per-point ``normals`` ([n,3]; ``estimate_normals(k=normals_k)``
+    if None), and a pair counts iff that normal is not 0.  The sums, the threshold, the solve and the loop are the same.  ``grid``,
+    ``search`` and ``init='global'`` belong to a mesh target."""
     _closest_search(search)
     if metric not in _ALIGN_MIN:
         raise ValueError(f"metric must be 'point' or 'plane', got {metric!r}")
     if isinstance(source, (tuple, list)) and len(source) == 2 and getattr(source[0], 'ndim', 0) == 2:
         source = source[0]
-    _mesh_args(verts, faces)
+    cloud = faces is None
+    if cloud:
+        _cloud_args(verts, 'the target cloud')
+        if grid is not None or (isinstance(init, str) and init == 'global'):
+            raise ValueError("grid and init='global' need a mesh target (faces)")
+    else:
+        if normals is not None:
+            raise ValueError('normals are those of a cloud target (faces=None); a mesh has its face normals')
+        _mesh_args(verts, faces)
     if source.ndim != 2 or source.shape[1] != 3:
         raise ValueError(f'source must be points [N,3] or a (verts, faces) pair, got {tuple(source.shape)}')
     if not 0.0 < float(trim) <= 1.0:
@@ -1282,7 +1392,7 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
         if init == 'identity':
             M0 = np.eye(4)
         elif init == 'centroid':
-            if not faces.shape[0] or not verts.shape[0]:
+            if (not cloud and not faces.shape[0]) or not verts.shape[0]:
                 raise ValueError('align_mesh: the target mesh is empty')
             M0 = _centroid_init(_np(source), _np(verts), scale)
         elif init == 'global':
@@ -1294,6 +1404,11 @@ def align_mesh(source, verts, faces, metric='plane', scale=False, iterations=30,
     else:
         M0 = _matrix44(init)
     args = (M0, metric, bool(scale), iterations, float(tol), max_dist, float(trim))
+    if cloud:
+        nrm = _cloud_normals(verts, normals, _nearest_k(normals_k), metric)
+        if on_dev:
+            return _align_cloud_device(torch.as_tensor(source), verts, nrm, *args)
+        return _align_cloud_numpy(_np(source), _np(verts), None if nrm is None else _np(nrm), *args)
     if on_dev:
         res = _align_device(torch.as_tensor(source), verts, faces, *args, grid, search)
     else:
@@ -1944,6 +2059,491 @@ def _closest_tree_numpy(points, tree, dtype=np.float64, slack=None):
             point = np.where(hit[:, None], p + q, np.nan).astype(dtype)
     best_d[~ok] = np.nan
     return best_d, best_f.astype(np.int32), point, np.stack([n_box, n_pair], -1)
+
+
+# ---- point clouds on the same tree: k nearest points, normals (csrc/point_tree.hip)
+
+NEAREST_MAX_K = 32
+_NEAREST_LISTS = (1, 4, 8, 16, 32)     # the lists the kernels are instantiated for; k is rounded up, which changes no result
+_NO_INDEX = np.iinfo(np.int32).max     # the index of an empty place of a list
+_JACOBI_SWEEPS = 8
+
+
+def _cloud_args(points, what='points'):
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f'{what} must be [n,3], got {tuple(points.shape)}')
+
+
+def _nearest_k(k):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= NEAREST_MAX_K:
+        raise ValueError(f'k must be an integer in 1 .. {NEAREST_MAX_K}, got {k!r}')
+    return int(k)
+
+
+def _pair_d2(p, x):
+    """Squared distance of pairs (query p [..., 3], point x [..., 3]) in the arrays' dtype: pair_d2 of csrc/geom_common.h, three
+    differences, three squares and two sums, each rounded on its own."""
+    dx, dy, dz = x[..., 0] - p[..., 0], x[..., 1] - p[..., 1], x[..., 2] - p[..., 2]
+    return (dx * dx + dy * dy) + dz * dz
+
+
+def _box_d2(p, row):
+    """box_d2 of csrc/geom_common.h: the expression of ``_pair_d2`` on the gaps ``max(lo - p, 0, p - hi)`` between points [n,3] and
+    the box of one row [8] (or one row per point).  Rounding is monotone, so it never exceeds ``_pair_d2(p, x)`` for x in the box."""
+    g = np.maximum(np.maximum(row[..., 0:3] - p, p.dtype.type(0)), p - row[..., 4:7])
+    return (g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2]
+
+
+def _point_boxes_numpy(pts, counts):
+    """NumPy restatement of ia_point_tree_boxes: float32 [n,8] = (lo.xyz, 0, hi.xyz, 0) per node over the sorted points [n_usable,3]."""
+    out = np.zeros((sum(counts), 8), dtype=F32)
+    start = child0 = 0
+    for lvl, cnt in enumerate(counts):
+        if lvl == 0:
+            at = np.arange(0, pts.shape[0], WINDING_LEAF)
+            lo, hi = np.minimum.reduceat(pts, at, axis=0), np.maximum.reduceat(pts, at, axis=0)
+        else:
+            ch = out[child0:child0 + counts[lvl - 1]]
+            at = np.arange(0, counts[lvl - 1], WINDING_BRANCH)
+            lo, hi = np.minimum.reduceat(ch[:, 0:3], at, axis=0), np.maximum.reduceat(ch[:, 4:7], at, axis=0)
+        out[start:start + cnt, 0:3], out[start:start + cnt, 4:7] = lo, hi
+        child0, start = start, start + cnt
+    return out
+
+
+def _point_tree_numpy(points):
+    """NumPy restatement of the tree of a cloud, the definition of ``PointTree``: ``{'order' int64 [n] (sorted position -> input
+    index: the usable = finite points by the 30-bit Morton key of their position in the cube of the usable points, ties by input
+    index, then the others), 'points' float32 [n_usable,3] in that order, 'boxes' float32 [nodes,8], 'counts', 'usable', 'lo',
+    'scale'}``.  ``WINDING_LEAF`` points per leaf, ``WINDING_BRANCH`` nodes per parent, leaves first."""
+    p32 = np.asarray(points, dtype=F32).reshape(-1, 3)
+    usable = np.isfinite(p32).all(1)
+    fin = p32[usable]
+    lo, scale = _morton_cube(fin.min(0), fin.max(0)) if fin.shape[0] else (np.zeros(3, dtype=F32), F32(0))
+    keys = np.where(usable, _morton_keys_numpy(p32, lo, scale), _WINDING_NO_KEY)
+    order = np.argsort(keys, kind='stable')
+    nu = int(usable.sum())
+    pts = p32[order[:nu]]
+    counts = _winding_levels(nu)
+    return {'order': order, 'points': pts, 'boxes': _point_boxes_numpy(pts, counts), 'counts': counts, 'usable': nu, 'lo': lo, 'scale': scale}
+
+
+def _smallest_pairs(d2, kk):
+    """Per row of d2 [r,n] the ``kk`` smallest pairs (value, column), ascending: (values [r,kk], columns int64 [r,kk]), +inf / -1
+    where the row has fewer columns."""
+    r, n = d2.shape
+    vals, cols = np.full((r, kk), np.inf, dtype=d2.dtype), np.full((r, kk), -1, dtype=np.int64)
+    if r == 0 or n == 0:
+        return vals, cols
+    m = min(kk, n)
+    kth = np.partition(d2, m - 1, axis=1)[:, m - 1]
+    rows, at = np.nonzero(d2 <= kth[:, None])                                              # (every tie of the m-th value is in)
+    v = d2[rows, at]
+    o = np.lexsort((at, v, rows))
+    rows, at, v = rows[o], at[o], v[o]
+    rank = np.arange(rows.size) - np.searchsorted(rows, np.arange(r))[rows]
+    keep = rank < kk
+    vals[rows[keep], rank[keep]], cols[rows[keep], rank[keep]] = v[keep], at[keep]
+    return vals, cols
+
+
+def _nearest_finish(d2, ids, ok, max_dist, dtype):
+    """(dist, index int32) of the lists (d2, input index or -1): ``sqrt``, the ``max_dist`` rule and the non-finite queries."""
+    with np.errstate(invalid='ignore'):
+        dist = np.sqrt(d2).astype(dtype)
+    admitted = (ids >= 0) & ok[:, None]
+    if max_dist is not None:
+        admitted &= dist <= dtype(max_dist)
+    return np.where(admitted, dist, dtype(np.inf)), np.where(admitted, ids, -1).astype(np.int32)
+
+
+def _exclude_rows(exclude, exclude_self, n):
+    if exclude is not None:
+        return np.asarray(exclude, dtype=np.int64).reshape(n)
+    return np.arange(n, dtype=np.int64) if exclude_self else None
+
+
+def _nearest_numpy(queries, points, k=1, max_dist=None, exclude_self=False, dtype=np.float64, exclude=None, pairs=1 << 22):
+    """The definition of ``nearest_points``, over all pairs: ``(dist [N,k] in dtype, index int32 [N,k])``.  For query p and usable
+    (finite) point x, ``d2 = (dx dx + dy dy) + dz dz`` in ``dtype`` with every operation rounded on its own; the result is the k
+    smallest pairs ``(d2, input index)``, ascending, ``dist = sqrt(d2)``; a place is ``inf`` / ``-1`` where the cloud has no further
+    point or ``dist > max_dist``, and throughout for a non-finite query.  ``exclude_self`` leaves out the point whose input index is
+    the query's row (``exclude``: one input index per query instead)."""
+    k = _nearest_k(k)
+    q32, p32 = np.asarray(queries, dtype=F32).reshape(-1, 3), np.asarray(points, dtype=F32).reshape(-1, 3)
+    idx = np.flatnonzero(np.isfinite(p32).all(1))
+    x, q = p32[idx].astype(dtype), q32.astype(dtype)
+    n = q.shape[0]
+    ok = np.isfinite(q32).all(1)
+    excl = _exclude_rows(exclude, exclude_self, n)
+    kk = k if excl is None else k + 1
+    d2, ids = np.full((n, k), np.inf, dtype=dtype), np.full((n, k), -1, dtype=np.int64)
+    step = max(int(pairs) // max(idx.size, 1), 1)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        for c0 in range(0, n, step):
+            sl = slice(c0, min(c0 + step, n))
+            v, at = _smallest_pairs(np.where(ok[sl, None], _pair_d2(q[sl, None, :], x[None, :, :]), dtype(np.inf)), kk)
+            i = np.where(at >= 0, idx[np.maximum(at, 0)] if idx.size else -1, -1)
+            if excl is not None:                                                           # the pair left out goes last, the others keep their order
+                o = np.argsort(i == excl[sl, None], axis=1, kind='stable')
+                v, i = np.take_along_axis(v, o, 1), np.take_along_axis(i, o, 1)
+            d2[sl], ids[sl] = v[:, :k], i[:, :k]
+    if excl is not None:
+        ids = np.where(ids == excl[:, None], -1, ids)
+    return _nearest_finish(d2, ids, ok, max_dist, dtype)
+
+
+def _nearest_tree_numpy(queries, tree, k=1, max_dist=None, exclude_self=False, dtype=np.float64, exclude=None, return_counts=False):
+    """NumPy restatement of ia_nearest_points_tree in ``dtype`` on a host ``PointTree``: what ``_nearest_numpy`` gives, exactly, by
+    the walk of ``_closest_tree_numpy``.  Each query keeps a sorted list of K pairs ``(d2, input index)`` (K: k rounded up to one of
+    1, 4, 8, 16, 32) that starts at ``(inf, none)``; a leaf merges its points into it.  A node is skipped iff ``lb > (the K-th d2)``,
+    strictly, ``lb = _box_d2``; the query first descends to the child with the smallest ``lb`` (the lowest index among equals), takes
+    that leaf and passes over it in the walk.  With ``return_counts`` also int64 [N,2] (boxes tested, leaves taken)."""
+    if tree.device is not None:
+        raise ValueError('_nearest_tree_numpy restates the query on a host PointTree')
+    k = _nearest_k(k)
+    K = next(c for c in _NEAREST_LISTS if c >= k)
+    q32 = np.asarray(queries, dtype=F32).reshape(-1, 3)
+    q, x = q32.astype(dtype), np.asarray(tree.sorted, dtype=F32).astype(dtype)
+    order = np.asarray(tree.order, dtype=np.int64)
+    counts, boxes = list(tree.counts), np.asarray(tree.boxes, dtype=F32).astype(dtype)
+    n, nu = q.shape[0], x.shape[0]
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    ok = np.isfinite(q32).all(1)
+    excl = _exclude_rows(exclude, exclude_self, n)
+    best_d, best_i = np.full((n, K), np.inf, dtype=dtype), np.full((n, K), _NO_INDEX, dtype=np.int64)
+    n_box, n_leaf = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    with np.errstate(invalid='ignore', over='ignore', under='ignore'):
+        def leaf(j, r):
+            sl = slice(j * WINDING_LEAF, min((j + 1) * WINDING_LEAF, nu))
+            d2 = _pair_d2(q[r, None, :], x[None, sl, :])
+            ids = np.broadcast_to(order[sl], d2.shape)
+            if excl is not None:
+                drop = ids == excl[r, None]
+                d2, ids = np.where(drop, dtype(np.inf), d2), np.where(drop, _NO_INDEX, ids)
+            cd, ci = np.concatenate([best_d[r], d2], 1), np.concatenate([best_i[r], ids], 1)
+            o = np.lexsort((ci, cd), axis=1)[:, :K]
+            best_d[r], best_i[r] = np.take_along_axis(cd, o, 1), np.take_along_axis(ci, o, 1)
+            n_leaf[r] += 1
+
+        rows = np.flatnonzero(ok) if counts else np.zeros(0, dtype=np.int64)
+        seed = np.full(n, -1, dtype=np.int64)
+        if rows.size:
+            j = np.zeros(rows.size, dtype=np.int64)
+            for lvl in range(len(counts) - 1, 0, -1):
+                least, pick = np.full(rows.size, np.inf, dtype=dtype), j * WINDING_BRANCH
+                for c in range(WINDING_BRANCH):
+                    at = j * WINDING_BRANCH + c
+                    valid = at < counts[lvl - 1]
+                    lb = _box_d2(q[rows], boxes[starts[lvl - 1] + np.minimum(at, counts[lvl - 1] - 1)])
+                    less = valid & (lb < least)
+                    least, pick = np.where(less, lb, least), np.where(less, at, pick)
+                    n_box[rows] += valid
+                j = pick
+            seed[rows] = j
+            for leaf_j in np.unique(j):
+                leaf(int(leaf_j), rows[j == leaf_j])
+
+        def visit(lvl, j, at, idx):
+            if lvl == 0:
+                idx = idx[seed[idx] != j]
+            lb = _box_d2(q[idx], boxes[at])
+            n_box[idx] += 1
+            r = idx[~(lb > best_d[idx, K - 1])]
+            if lvl == 0 and r.size:
+                leaf(j, r)
+            return r
+
+        _tree_walk(counts, rows, visit)
+    out = _nearest_finish(best_d[:, :k], np.where(best_i[:, :k] == _NO_INDEX, -1, best_i[:, :k]), ok, max_dist, dtype)
+    return out + (np.stack([n_box, n_leaf], -1),) if return_counts else out
+
+
+class PointTree:
+    """The cluster tree of one point cloud for ``nearest_points``, built once: the usable (finite) points sorted by the 30-bit Morton
+    key of their position in the cloud's cube (the arithmetic of the face keys of ``WindingTree``; ties by input index),
+    ``WINDING_LEAF`` points per leaf, ``WINDING_BRANCH`` nodes per parent, one exact bounding box per node; no pointers.  ``order``
+    (sorted position -> input index), ``sorted`` (the usable points in that order: float32 [n_usable,4] = xyz and the bits of the
+    input index on the device, [n_usable,3] on the host), ``boxes``, ``counts``, ``info``.  Device tensors build on the kernels; CPU
+    tensors and NumPy arrays take ``_point_tree_numpy``, which is the definition."""
+
+    def __init__(self, points):
+        _cloud_args(points)
+        self.device = points.device if _is_device(points) else None
+        self._like = points
+        n = int(points.shape[0])
+        if n > (1 << 25):
+            raise ValueError(f'a cloud holds at most 2^25 points, got {n}')
+        if self.device is not None:
+            from . import hipops
+            self.points = points.detach().float().contiguous()
+            fin = self.points[torch.isfinite(self.points).all(1)]
+            box = torch.stack([fin.amin(0), fin.amax(0)]).cpu().tolist() if fin.shape[0] else [[0.0] * 3, [0.0] * 3]   # one host synchronisation
+            lo, scale = _morton_cube(box[0], box[1]) if fin.shape[0] else (np.zeros(3, dtype=F32), F32(0))
+            self.order, self.sorted, self.boxes, self.counts, self.usable = hipops.point_tree_build(self.points, lo.tolist(), float(scale))
+        else:
+            self.points = np.asarray(_np(points), dtype=F32).reshape(-1, 3)
+            t = _point_tree_numpy(self.points)
+            fin = _finite_rows(self.points)
+            box = [fin.min(0).tolist(), fin.max(0).tolist()] if fin.shape[0] else [[0.0] * 3, [0.0] * 3]
+            lo, scale = t['lo'], t['scale']
+            self.order, self.sorted, self.boxes, self.counts, self.usable = t['order'], t['points'], t['boxes'], t['counts'], t['usable']
+        self.box_lo, self.box_hi = box
+        self.extent = max(max(abs(v) for v in box[0]), max(abs(v) for v in box[1]))
+        self.lo, self.scale = [float(v) for v in lo], float(scale)
+        self.info = {'points': n, 'usable': int(self.usable), 'levels': len(self.counts), 'nodes': int(sum(self.counts)),
+                     'leaf': WINDING_LEAF, 'branch': WINDING_BRANCH}
+
+    def nearest(self, queries, k=1, max_dist=None, exclude_self=False, brute=False, return_counts=False, sort=True):
+        """``{'dist' float32 [N,k], 'index' int32 [N,k]}`` of queries [N,3] (see ``nearest_points``); with ``return_counts`` also
+        ``'counts'`` int [N,2] (boxes tested, leaves taken).  ``sort`` (device): query in Morton order of the queries and return in
+        the caller's order; it changes no result.  A host tree answers in float64."""
+        k = _nearest_k(k)
+        _cloud_args(queries, 'queries')
+        if max_dist is not None and not float(max_dist) >= 0:
+            raise ValueError(f'max_dist must be >= 0, got {max_dist}')
+        if brute and return_counts:
+            raise ValueError('return_counts counts the walk: it excludes brute=True')
+        if self.device is None:
+            if brute:
+                out = _nearest_numpy(_np(queries), self.points, k, max_dist, exclude_self)
+            else:
+                out = _nearest_tree_numpy(_np(queries), self, k, max_dist, exclude_self, return_counts=return_counts)
+            res = {'dist': _as_out(out[0], queries), 'index': _as_out(out[1], queries, np.int32)}
+            if return_counts:
+                res['counts'] = _as_out(out[2], queries, np.int64)
+            return res
+        from . import hipops
+        pts = torch.as_tensor(queries).detach().to(self.device).float().reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        excl = torch.arange(n, dtype=torch.int32, device=self.device) if exclude_self else None
+        limit = float('inf') if max_dist is None else float(F32(max_dist))
+        boxes = None if brute else self.boxes
+        if sort and not brute and n > 64:
+            perm = torch.argsort(hipops.winding_tree_point_keys(pts, self.lo, self.scale), stable=True)
+            back = torch.empty_like(perm)
+            back[perm] = torch.arange(n, device=perm.device)
+            out = hipops.nearest_points(pts[perm].contiguous(), self.sorted, boxes, k, limit, None if excl is None else excl[perm].contiguous(),
+                                        counts=return_counts)
+            dist, index, cnt = [None if t is None else t[back] for t in out]
+        else:
+            dist, index, cnt = hipops.nearest_points(pts, self.sorted, boxes, k, limit, excl, counts=return_counts)
+        res = {'dist': dist, 'index': index}
+        if return_counts:
+            res['counts'] = cnt
+        return res
+
+
+def _point_tree_for(points, tree):
+    if tree is None:
+        return PointTree(points)
+    if not isinstance(tree, PointTree) or tree.info['points'] != points.shape[0] or (tree.device is not None) != _is_device(points):
+        raise ValueError('tree must be the PointTree of these points, on their device')
+    return tree
+
+
+def nearest_points(queries, points, k=1, tree=None, max_dist=None, exclude_self=False, brute=False, return_counts=False):
+    """The k nearest points of the cloud ``points`` [n,3] for every query [N,3]: ``{'dist' float32 [N,k], 'index' int32 [N,k]}``
+    with input indices.  The usable points are the finite rows.  For query p and usable point x, in float32 with every operation
+    rounded on its own, ``d2 = (dx dx + dy dy) + dz dz``; the result is the k smallest pairs ``(d2, input index)``, ascending (equal
+    distances come out in index order), ``dist = sqrt(d2)`` correctly rounded.  A place is ``inf`` / ``-1`` where fewer than k points
+    are admissible, and throughout for a non-finite query; ``max_dist`` admits ``dist <= max_dist``; ``exclude_self`` (for
+    ``queries is points``) leaves out the point whose index is the query's row.  k is in 1 .. 32.
+
+    Device tensors walk the ``PointTree`` of the cloud (``tree``; built here if None) with ia_nearest_points_tree, or, with
+    ``brute=True``, take all pairs (ia_nearest_points_brute): the tree only prunes, so both give the same bits, which are those of the
+    NumPy float32 restatement (``_nearest_numpy(dtype=np.float32)``), for any k, any slabbing of the queries and any run.  CPU tensors
+    and NumPy arrays take ``_nearest_tree_numpy`` (``_nearest_numpy`` with ``brute``) in float64.  ``return_counts`` adds ``'counts'``
+    int [N,2]: boxes tested and leaves taken per query."""
+    _cloud_args(points)
+    _cloud_args(queries, 'queries')
+    _nearest_k(k)
+    if _is_device(points) != _is_device(queries):
+        raise ValueError('queries and points must both be device tensors or both be on the host')
+    return _point_tree_for(points, tree).nearest(queries, k, max_dist, exclude_self, brute, return_counts)
+
+
+def _jacobi_rotate(A, V, p, q, r):
+    """One Jacobi rotation in the (p, q) plane of the symmetric matrices A [n,3,3] (r: the third axis), accumulated into the columns of
+    V: the operations of jacobi_rotate in csrc/point_tree.hip, in place."""
+    apq = A[:, p, q].copy()
+    live = apq != 0.0
+    theta = (A[:, q, q] - A[:, p, p]) / (2.0 * np.where(live, apq, 1.0))
+    t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+    c = 1.0 / np.sqrt(t * t + 1.0)
+    s = t * c
+    t, c, s = np.where(live, t, 0.0), np.where(live, c, 1.0), np.where(live, s, 0.0)      # (apq = 0: the rotation is skipped)
+    app, aqq = A[:, p, p] - t * apq, A[:, q, q] + t * apq
+    arp, arq = c * A[:, r, p] - s * A[:, r, q], s * A[:, r, p] + c * A[:, r, q]
+    A[:, p, p], A[:, q, q] = app, aqq
+    A[:, p, q] = A[:, q, p] = 0.0
+    A[:, r, p] = A[:, p, r] = arp
+    A[:, r, q] = A[:, q, r] = arq
+    vp, vq = c[:, None] * V[:, :, p] - s[:, None] * V[:, :, q], s[:, None] * V[:, :, p] + c[:, None] * V[:, :, q]
+    V[:, :, p], V[:, :, q] = vp, vq
+
+
+def _jacobi3_numpy(cov6):
+    """Eigen-decomposition of symmetric 3x3 matrices float64 [n,6] (xx xy xz yy yz zz) by ``_JACOBI_SWEEPS`` cyclic Jacobi sweeps over
+    (0,1) (0,2) (1,2): ``(eigenvalues [n,3] ascending, the lowest axis first among equals, eigenvectors [n,3,3] as columns)``."""
+    c = np.asarray(cov6, dtype=np.float64).reshape(-1, 6)
+    A = np.stack([c[:, [0, 1, 2]], c[:, [1, 3, 4]], c[:, [2, 4, 5]]], 1)
+    V = np.broadcast_to(np.eye(3), A.shape).copy()
+    with np.errstate(over='ignore', invalid='ignore'):
+        for _ in range(_JACOBI_SWEEPS):
+            _jacobi_rotate(A, V, 0, 1, 2)
+            _jacobi_rotate(A, V, 0, 2, 1)
+            _jacobi_rotate(A, V, 1, 2, 0)
+    w = np.stack([A[:, 0, 0], A[:, 1, 1], A[:, 2, 2]], -1)
+    for a, b in ((0, 1), (1, 2), (0, 1)):                                                  # the kernel's network on three values
+        swap = w[:, b] < w[:, a]
+        w[swap, a], w[swap, b] = w[swap, b], w[swap, a]
+        V[swap, :, a], V[swap, :, b] = V[swap, :, b], V[swap, :, a]
+    return w, V
+
+
+def _point_normals_numpy(points, index):
+    """NumPy restatement of ia_point_normals: ``(normal float32 [n,3], variation float32 [n], eigenvalues float64 [n,3], covariance
+    float64 [n,6])`` for points [n,3] and their neighbour table int [n,k] (entries outside [0, n) are left out).  In double: the mean
+    of the neighbours added in order, the covariance (xx xy xz yy yz zz) of the differences added in order and divided by their
+    number m, ``_jacobi3_numpy``.  The normal is the unit eigenvector of the smallest eigenvalue with its largest-magnitude component
+    positive, ``variation = l0 / ((l0 + l1) + l2)``; both are 0 where m < 3 or the trace is not positive."""
+    p = np.asarray(points, dtype=F32).reshape(-1, 3).astype(np.float64)
+    idx = np.asarray(index, dtype=np.int64).reshape(p.shape[0], -1)
+    n, k = idx.shape
+    valid = (idx >= 0) & (idx < n)
+    nb = p[np.where(valid, idx, 0)]                                                        # [n,k,3]
+    m = valid.sum(1)
+    total = np.zeros((n, 3))
+    for s in range(k):
+        total = np.where(valid[:, s, None], total + nb[:, s], total)
+    cov = np.zeros((n, 6))
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        mean = total / m[:, None]
+        for s in range(k):
+            e = nb[:, s] - mean
+            term = np.stack([e[:, 0] * e[:, 0], e[:, 0] * e[:, 1], e[:, 0] * e[:, 2], e[:, 1] * e[:, 1], e[:, 1] * e[:, 2], e[:, 2] * e[:, 2]], -1)
+            cov = np.where(valid[:, s, None], cov + term, cov)
+        cov = np.where(m[:, None] > 0, cov / m[:, None], 0.0)
+        w, V = _jacobi3_numpy(cov)
+        trace = (w[:, 0] + w[:, 1]) + w[:, 2]
+        good = (m >= 3) & (trace > 0.0)
+        v0 = V[:, :, 0]
+        nrm = v0 / np.sqrt((v0[:, 0] * v0[:, 0] + v0[:, 1] * v0[:, 1]) + v0[:, 2] * v0[:, 2])[:, None]
+        a = np.abs(nrm)
+        lead = np.where((a[:, 0] >= a[:, 1]) & (a[:, 0] >= a[:, 2]), nrm[:, 0], np.where(a[:, 1] >= a[:, 2], nrm[:, 1], nrm[:, 2]))
+        nrm = np.where(lead[:, None] < 0.0, -nrm, nrm)
+        normal = np.where(good[:, None], nrm, 0.0).astype(F32)
+        variation = np.where(good, w[:, 0] / np.where(good, trace, 1.0), 0.0).astype(F32)
+    return normal, variation, w, cov
+
+
+_ORIENTS = (None, 'viewpoint', 'centroid')
+
+
+def estimate_normals(points, k=16, tree=None, orient=None, viewpoint=None):
+    """Normals of a point cloud [n,3] from its k nearest usable points (the point itself included): ``{'normal' float32 [n,3],
+    'variation' float32 [n], 'eigenvalues' float64 [n,3], 'covariance' float64 [n,6]}``, see ``_point_normals_numpy`` (the
+    definition).  ``normal`` is the eigenvector of the smallest eigenvalue of the neighbours' covariance, its largest-magnitude
+    component positive; ``variation = l0 / (l0 + l1 + l2)`` (0 on a plane, 1/3 for an isotropic blob).  A point with fewer than 3
+    neighbours or without spread gets a zero normal.  ``orient='viewpoint'`` turns every normal towards ``viewpoint`` (three floats),
+    ``orient='centroid'`` away from the centroid of the usable points; a consistent orientation by propagation is not done.  Device
+    tensors take ``nearest_points`` on the ``PointTree`` (``tree``; built here if None) and ia_point_normals."""
+    _cloud_args(points)
+    k = _nearest_k(k)
+    if orient not in _ORIENTS:
+        raise ValueError(f'orient must be one of {_ORIENTS}, got {orient!r}')
+    if (orient == 'viewpoint') != (viewpoint is not None):
+        raise ValueError("viewpoint goes with orient='viewpoint'")
+    tree = _point_tree_for(points, tree)
+    index = tree.nearest(points, k)['index']
+    if tree.device is not None:
+        from . import hipops
+        normal, variation, eig, cov = hipops.point_normals(tree.points, index.contiguous())
+        if orient is not None:
+            fin = tree.points[torch.isfinite(tree.points).all(1)].double()
+            ref = torch.tensor([float(v) for v in viewpoint], dtype=torch.float64, device=tree.device) if orient == 'viewpoint' else fin.mean(0)
+            to = (ref - tree.points.double()) if orient == 'viewpoint' else (tree.points.double() - ref)
+            normal = torch.where(((normal.double() * to).sum(1) < 0)[:, None], -normal, normal)
+        return {'normal': normal, 'variation': variation, 'eigenvalues': eig, 'covariance': cov}
+    normal, variation, eig, cov = _point_normals_numpy(tree.points, _np(index))
+    if orient is not None:
+        p = tree.points.astype(np.float64)
+        ref = np.asarray([float(v) for v in viewpoint]) if orient == 'viewpoint' else _finite_rows(p).mean(0)
+        to = (ref - p) if orient == 'viewpoint' else (p - ref)
+        with np.errstate(invalid='ignore'):
+            normal = np.where(((normal.astype(np.float64) * to).sum(1) < 0)[:, None], -normal, normal)
+    return {'normal': _as_out(normal, points), 'variation': _as_out(variation, points), 'eigenvalues': _as_out(eig, points, np.float64),
+            'covariance': _as_out(cov, points, np.float64)}
+
+
+def remove_outliers(points, k=16, std_ratio=2.0, tree=None):
+    """Statistical outlier removal: ``{'keep' bool [n], 'mean_dist' float64 [n]}``.  ``mean_dist`` is the mean distance, in double, to
+    the k nearest usable points other than the point itself (NaN for a point that is not finite or has no neighbour); a point is kept
+    iff it is ``<= mean + std_ratio * std`` over the points that have one (the population standard deviation)."""
+    _cloud_args(points)
+    tree = _point_tree_for(points, tree)
+    r = tree.nearest(points, k, exclude_self=True)
+    if tree.device is not None:
+        d, has = r['dist'].double(), r['index'] >= 0
+        cnt = has.sum(1)
+        md = torch.where(cnt > 0, torch.where(has, d, torch.zeros_like(d)).sum(1) / cnt.clamp(min=1), torch.full_like(d[:, 0], float('nan')))
+        ok = torch.isfinite(md)
+        if not bool(ok.any()):
+            return {'keep': torch.zeros_like(ok), 'mean_dist': md}
+        mu = md[ok].mean()
+        sd = ((md[ok] - mu) ** 2).mean().sqrt()
+        return {'keep': ok & (md <= mu + float(std_ratio) * sd), 'mean_dist': md}
+    d, has = _np(r['dist']).astype(np.float64), _np(r['index']) >= 0
+    cnt = has.sum(1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        md = np.where(cnt > 0, np.where(has, d, 0.0).sum(1) / np.maximum(cnt, 1), np.nan)
+        ok = np.isfinite(md)
+        if ok.any():
+            mu = md[ok].mean()
+            sd = np.sqrt(((md[ok] - mu) ** 2).mean())
+            keep = ok & (md <= mu + float(std_ratio) * sd)
+        else:
+            keep = np.zeros_like(ok)
+    return {'keep': _as_out(keep, points, bool), 'mean_dist': _as_out(md, points, np.float64)}
+
+
+def _cloud_stats(a, b, thresholds, tree_b=None):
+    """ia_distance_stats (or its restatement) of the distances from the points a to the cloud b: float64 [14]."""
+    dist = nearest_points(a, b, 1, tree=tree_b)['dist'][:, 0]
+    if _is_device(b):
+        from . import hipops
+        return hipops.distance_stats(dist.contiguous(), thresholds).cpu().numpy()
+    return _stats_numpy(_np(dist), thresholds)
+
+
+def _cloud_thresholds(thresholds, *clouds):
+    if thresholds is None:
+        diag = 0.0
+        for v in clouds:
+            x = torch.as_tensor(_np(v) if not _is_device(v) else v).float()
+            x = x[torch.isfinite(x).all(1)]
+            if x.shape[0]:
+                diag = max(diag, float((x.amax(0) - x.amin(0)).double().norm()))
+        thresholds = [0.005 * diag, 0.01 * diag, 0.02 * diag]
+    thresholds = [float(F32(t)) for t in thresholds]
+    if len(thresholds) > 8:
+        raise ValueError(f'at most 8 thresholds, got {len(thresholds)}')
+    return thresholds
+
+
+def cloud_distance(points_a, points_b, thresholds=None):
+    """How far cloud a is from cloud b: the keys of ``surface_distance`` (``mean_ab``, ``rms_ab``, ``max_ab`` and the ``_ba`` ones,
+    ``chamfer``, ``chamfer_sq``, ``hausdorff``, ``thresholds``, ``precision``, ``recall``, ``fscore``, ``n_a``, ``n_b``, ``skipped_ab``,
+    ``skipped_ba``; ``normal_consistency`` is None) with ``d_ab`` the distance of every point of a to its nearest point of b
+    (``nearest_points`` with k = 1) and ``d_ba`` the reverse: the Chamfer distance between point sets.  ``thresholds`` default to 0.5 %,
+    1 % and 2 % of the larger bounding-box diagonal.  Device tensors run on the kernels (ia_distance_stats for the sums)."""
+    _cloud_args(points_a, 'points_a')
+    _cloud_args(points_b, 'points_b')
+    if _is_device(points_a) != _is_device(points_b):
+        raise ValueError('points_a and points_b must both be device tensors or both be on the host')
+    thresholds = _cloud_thresholds(thresholds, points_a, points_b)
+    return _distance_report(_cloud_stats(points_a, points_b, thresholds), _cloud_stats(points_b, points_a, thresholds), thresholds)
 
 
 # ---- rays against the mesh on the same tree (csrc/ray_tree.hip; DESIGN.md 4.28)
@@ -3887,6 +4487,31 @@ def rasterize_mesh(verts, faces, cameras, resolution, normals=None, attributes=N
     return {k: None if x is None else _as_out(x, verts, kinds.get(k, dtype)) for k, x in out.items()}
 
 
+def depth_to_points(depth, cameras, mask=None):
+    """World points ``o + t d`` of a ray-parameter depth image [N,1,H,W] or [N,H,W] with H = W (the ``image_depth`` of ``synthesis``,
+    the depth of ``render_geometry``, ``render_mesh`` and ``rasterize_mesh``) seen from ``cameras`` [N,25]: float32 [M,3], the pixels
+    in (view, row, column) order for which ``mask`` (same shape as depth; default: depth finite and > 0) is set.  The rays are those of
+    ``RaySampler_zxc`` (unit directions, pixel centres at integer coordinates).  A point cloud for ``PointTree`` and its callers."""
+    from .training_avatar_texture.volumetric_rendering.ray_sampler import RaySampler_zxc
+    like = depth
+    d = torch.as_tensor(depth).detach().float()
+    if d.ndim == 4 and d.shape[1] == 1:
+        d = d[:, 0]
+    if d.ndim != 3 or d.shape[1] != d.shape[2]:
+        raise ValueError(f'depth must be [N,1,H,W] or [N,H,W] with H = W, got {tuple(torch.as_tensor(depth).shape)}')
+    cams = torch.as_tensor(cameras).detach().to(d.device).float()
+    if cams.ndim != 2 or cams.shape[1] != 25 or cams.shape[0] != d.shape[0]:
+        raise ValueError(f'cameras must be [{d.shape[0]},25], got {tuple(cams.shape)}')
+    if mask is None:
+        m = torch.isfinite(d) & (d > 0)
+    else:
+        m = torch.as_tensor(mask).to(d.device).bool().reshape(d.shape)
+    with torch.no_grad():
+        o, dirs = RaySampler_zxc()(cams[:, :16].reshape(-1, 4, 4), cams[:, 16:25].reshape(-1, 3, 3), int(d.shape[1]))
+    pts = (o + d.reshape(d.shape[0], -1, 1) * dirs)[m.reshape(d.shape[0], -1)]
+    return pts if isinstance(like, torch.Tensor) else pts.cpu().numpy()
+
+
 # ------------------------------------------------------------------ texture atlas
 
 TEXTURE_MIN_BLOCK = 4
@@ -4311,7 +4936,7 @@ def read_ply(path, with_normals=False):
     end = data.index(b'end_header\n') + len(b'end_header\n')
     head = data[:end].decode('ascii').split('\n')
     nv = int(next(h for h in head if h.startswith('element vertex')).split()[-1])
-    nf = int(next(h for h in head if h.startswith('element face')).split()[-1])
+    nf = int(next((h for h in head if h.startswith('element face')), 'element face 0').split()[-1])     # (a cloud has no face element)
     has_col, has_nrm = 'property uchar red' in head, 'property float nx' in head
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')] + ([('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')] if has_nrm else [])
     fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')] if has_col else []

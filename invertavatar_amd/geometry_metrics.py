@@ -155,6 +155,31 @@ def compare_meshes(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
     return res
 
 
+def compare_clouds(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thresholds=None, align=None, align_options=None,
+                   normals_k=16, save_aligned=None, search='grid'):
+    """``compare_meshes`` when the prediction, the reference or both are point clouds (no faces): ``geometry.surface_distance`` with
+    ``faces=None`` on that side (the distance to a cloud is the distance to its nearest point), after ``geometry.align_mesh`` onto the
+    reference if asked (against a cloud reference: its ``faces=None`` route, the plane metric with normals from ``normals_k``
+    neighbours).  The result gains ``"target": "cloud"``."""
+    pf = faces if faces.shape[0] else None
+    rf = ref_faces if ref_faces.shape[0] else None
+    res = {}
+    if align is not None:
+        if align not in ALIGN_MODES:
+            raise ValueError(f"align must be None, 'rigid' or 'similarity', got {align!r}")
+        source = verts if samples is None or pf is None else geometry.sample_surface(verts, pf, samples, seed)[0]
+        more = {'normals_k': int(normals_k)} if rf is None else {'search': search}
+        fit = geometry.align_mesh(source, ref_verts, rf, scale=align == 'similarity', **dict(align_options or {}), **more)
+        verts = geometry.transform_points(verts, fit['matrix'])
+        res['alignment'] = alignment_block(fit)
+        if save_aligned:
+            geometry.write_ply(save_aligned, verts, faces)
+    res.update(geometry.surface_distance(verts, pf, ref_verts, rf, samples=samples, seed=seed, thresholds=thresholds, search=search))
+    res.update(pred_vertices=int(verts.shape[0]), pred_faces=int(faces.shape[0]), gt_vertices=int(ref_verts.shape[0]),
+               gt_faces=int(ref_faces.shape[0]), target='cloud')
+    return res
+
+
 def add_sign_arguments(ap):
     """``--signed``, ``--iou``, how their winding numbers are made (``--winding``, ``--winding-beta``) and how closest points are searched
     (``--search``), shared with extract_geometry."""
@@ -186,6 +211,8 @@ def add_align_arguments(ap):
     ap.add_argument('--align-angle-step', type=float, default=15.0, metavar='DEG', help='with --align-init global: spacing of the candidate rotations')
     ap.add_argument('--align-candidates', type=int, default=8, help='with --align-init global: candidates refined by ICP')
     ap.add_argument('--align-shifts', type=int, default=1, help='with --align-init global: offsets per axis around the centroid (odd; expert option)')
+    ap.add_argument('--normals-k', type=int, default=16, metavar='K',
+                    help='with --align-metric plane against a reference without faces (a point cloud): neighbours per estimated normal')
 
 
 def align_options_of(args):
@@ -258,7 +285,21 @@ def main(argv=None):
         meshes += [torch.from_numpy(v).to(args.device), torch.from_numpy(f).to(args.device)]
     if args.save_aligned and not args.align:
         ap.error('--save-aligned needs --align')
-    extra = {'align': args.align, 'align_options': align_options_of(args), 'save_aligned': args.save_aligned} if args.align else {}
+    if not meshes[1].shape[0] or not meshes[3].shape[0]:                   # a file without faces: the cloud routes
+        for on, flag in ((args.signed, '--signed'), (args.iou is not None, '--iou'), (args.fit_nonrigid, '--fit-nonrigid'),
+                         (args.align and args.align_init == 'global', '--align-init global'), (args.error_ply, '--error-ply')):
+            if on:
+                ap.error(f'{flag} needs a surface on both sides; {args.pred if not meshes[1].shape[0] else args.gt} is a point cloud (no faces)')
+        res = compare_clouds(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, align=args.align,
+                             align_options=align_options_of(args) if args.align else None, normals_k=args.normals_k,
+                             save_aligned=args.save_aligned, search=args.search)
+        with open(args.out, 'w') as fh:
+            json.dump(res, fh, indent=1)
+        if args.align:
+            print(alignment_summary(res['alignment']))
+        print(summary(res))
+        return res
+    extra ={'align': args.align, 'align_options': align_options_of(args), 'save_aligned': args.save_aligned} if args.align else {}
     extra.update(sign_options_of(args))
     if args.save_fitted and not args.fit_nonrigid:
         ap.error('--save-fitted needs --fit-nonrigid')

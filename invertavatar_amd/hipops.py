@@ -2205,6 +2205,94 @@ def ao_rays(verts, normals, table, bias):
     return origins, dirs
 
 
+# ------------------------------------------------------------------ point clouds on the tree (csrc/point_tree.hip)
+
+NEAREST_MAX_K = 32           # csrc/point_tree.hip kMaxK
+
+
+def _cloud_checked(points, what='points'):
+    _f32c(points, what)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f'{what} must be [N,3], got {tuple(points.shape)}')
+
+
+def point_tree_build(points, lo, scale):
+    """The cluster tree of a cloud (see ia_point_tree_gather): points float32 [n,3], (lo, scale) the Morton cube -> (order int64 [n]:
+    sorted position -> input index, usable points first, sorted float32 [n_usable,4], boxes float32 [nodes,8], nodes per level,
+    n_usable).  The keys are sorted by ``torch.sort`` (stable); one host synchronisation (the number of usable points)."""
+    _cloud_checked(points)
+    n, dev = points.shape[0], points.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        keys = winding_tree_point_keys(points, lo, scale)
+        skeys, order = torch.sort(keys, stable=True)
+        usable = int((skeys < WINDING_NO_KEY).sum()) if n else 0
+        order32 = order.int().contiguous()
+        rows = torch.empty(usable, 4, device=dev)
+        with _Timed('point_tree_gather', 0.0, 32.0 * usable, f'n={usable}'):
+            st = lib.ia_point_tree_gather(_p(points), n, _p(order32), usable, _p(rows), _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_point_tree_gather')
+        counts, total, _ = winding_tree_plan(usable)
+        boxes = torch.empty(total, TREE_BOX_ROW, device=dev)
+        with _Timed('point_tree_boxes', 0.0, 16.0 * usable + 64.0 * total, f'n={usable} nodes={total}'):
+            st = lib.ia_point_tree_boxes(_p(rows), usable, _p(boxes), total, _lib.stream_ptr(dev))
+        _lib.check(st, 'ia_point_tree_boxes')
+    return order, rows, boxes, counts, usable
+
+
+def nearest_points(queries, sorted_points, boxes=None, k=1, max_dist=float('inf'), exclude=None, counts=False):
+    """The k nearest points of a cloud per query (see ia_nearest_points_tree; ``boxes=None``: ia_nearest_points_brute): queries float32
+    [N,3], ``sorted_points`` / ``boxes`` from ``point_tree_build``, ``exclude`` int32 [N] or None -> (dist float32 [N,k], index int32
+    [N,k], counts int32 [N,2] or None)."""
+    _cloud_checked(queries, 'queries')
+    _f32c(sorted_points, 'sorted_points')
+    dev, n = queries.device, queries.shape[0]
+    if sorted_points.dim() != 2 or sorted_points.shape[1] != 4 or sorted_points.device != dev:
+        raise RuntimeError(f'sorted_points must be [n,4] on the device of the queries, got {tuple(sorted_points.shape)}')
+    if boxes is not None:
+        _f32c(boxes, 'boxes')
+        if boxes.dim() != 2 or boxes.shape[1] != TREE_BOX_ROW or boxes.device != dev:
+            raise RuntimeError(f'boxes must be [n,{TREE_BOX_ROW}] on the device of the queries, got {tuple(boxes.shape)}')
+    elif counts:
+        raise RuntimeError('counts are those of the walk: they need boxes')
+    if exclude is not None:
+        _i32c(exclude, 'exclude')
+        if tuple(exclude.shape) != (n,) or exclude.device != dev:
+            raise RuntimeError(f'exclude must be [N] on the device of the queries, got {tuple(exclude.shape)}')
+    k = int(k)
+    rows = max(min(k, NEAREST_MAX_K), 1)                 # (a k out of range is refused by the library; the buffers stay small)
+    dist = torch.empty(n, rows, device=dev)
+    index = torch.empty(n, rows, dtype=torch.int32, device=dev)
+    cnt = torch.empty(n, 2, dtype=torch.int32, device=dev) if counts else None
+    lib, m = _lib.load(), sorted_points.shape[0]
+    with torch.cuda.device(dev), _Timed('nearest_points', 0.0, 12.0 * n + 8.0 * n * rows, f'N={n} n={m} k={k} {"brute" if boxes is None else "tree"}'):
+        if boxes is None:
+            st = lib.ia_nearest_points_brute(_p(queries), n, _p(sorted_points), m, k, float(max_dist), _p(exclude), _p(dist), _p(index),
+                                             _lib.stream_ptr(dev))
+        else:
+            st = lib.ia_nearest_points_tree(_p(queries), n, _p(sorted_points), m, _p(boxes), boxes.shape[0], k, float(max_dist), _p(exclude),
+                                            _p(dist), _p(index), _p(cnt), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_nearest_points_brute' if boxes is None else 'ia_nearest_points_tree')
+    return dist, index, cnt
+
+
+def point_normals(points, index):
+    """Normals of a cloud from its neighbour table (see ia_point_normals): points float32 [n,3], index int32 [n,k] -> (normal float32
+    [n,3], variation float32 [n], eigenvalues float64 [n,3], covariance float64 [n,6])."""
+    _cloud_checked(points)
+    _i32c(index, 'index')
+    n, dev = points.shape[0], points.device
+    if index.dim() != 2 or index.shape[0] != n or index.device != dev:
+        raise RuntimeError(f'index must be [n,k] on the device of the points, got {tuple(index.shape)}')
+    normal, variation = torch.empty(n, 3, device=dev), torch.empty(n, device=dev)
+    eig, cov = torch.empty(n, 3, dtype=torch.float64, device=dev), torch.empty(n, 6, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), _Timed('point_normals', 0.0, (88.0 + 16.0 * index.shape[1]) * n, f'n={n} k={index.shape[1]}'):
+        st = _lib.load().ia_point_normals(_p(points), n, _p(index), index.shape[1], _p(normal), _p(variation), _p(eig), _p(cov),
+                                          _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_point_normals')
+    return normal, variation, eig, cov
+
+
 # ------------------------------------------------------------------ mesh simplification (csrc/simplify.hip)
 
 def simplify_plan(lo, hi, cells=None, cells_long=0, cell_size=0.0):

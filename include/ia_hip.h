@@ -1511,6 +1511,28 @@ int ia_nearest_points_tree(const float* queries, int64_t N, const void* sorted, 
 int ia_point_normals(const float* points, int64_t n, const int* index, int k, float* normal, float* variation, double* eigenvalues,
                      double* covariance, void* stream);
 
+/*
+ * TSDF integration: depth maps fused into a truncated signed distance lattice (csrc/tsdf.hip; no counterpart in the reference;
+ * definition: geometry._fuse_numpy).  An additive entry point: the ABI version is unchanged.
+ *
+ * depth float32 [N,H,W] (the ray parameter of the pixel's unit ray), mask uint8 [N,H,W] or NULL, weights float32 [N,H,W] or NULL,
+ * colors float32 [N,C,H,W] (NULL exactly when C = 0), views float32 [N,18]: per view the rotation row-major (9), the origin (3) and
+ * rows 0 and 1 of K_res (row 0 of K times W, row 1 times H; pixel centres at integer coordinates).  The lattice is that of ia_mc_*:
+ * point (i, j, k) at h_lo + index * h_step in fp32, z fastest.  Per lattice point X, over the views in order, fp32 with every
+ * operation rounded on its own: d = X - o, xc_a = (R_0a d_x + R_1a d_y) + R_2a d_z; u = ((k0 xc_x + k1 xc_y) + k2 xc_z) / xc_z,
+ * v likewise with k3 .. k5; i = rint(u), j = rint(v) (ties to even); t = depth[n,j,i], w = weights[n,j,i] or 1;
+ * s = t - sqrt((d_x d_x + d_y d_y) + d_z d_z).  The view is skipped unless xc_z is finite and > near, u and v are finite,
+ * 0 <= i <= W - 1 and 0 <= j <= H - 1 (compared as floats), t is finite and > 0, the mask is set, w is finite and > 0 and
+ * s >= -truncation.  Otherwise sum += min(s / truncation, 1) w and weight += w, and where s <= truncation color_sum[c] +=
+ * colors[n,c,j,i] w per channel and color_weight += w.  Outputs float32: sum, weight, tsdf = sum / weight (1 where weight is not > 0)
+ * [nx,ny,nz], color_sum [nx,ny,nz,C] and color_weight [nx,ny,nz] (C > 0).  accumulate != 0: the sums start from the contents of the
+ * output arrays instead of 0, so views [0, N) in one call give the bits of [0, k) followed by [k, N).  One thread per lattice point,
+ * no atomics: bit-equal run to run.  N >= 1, 0 <= C <= 8, 1 <= H, W <= 16384, truncation > 0, near >= 0.
+ */
+int ia_tsdf_integrate(const float* depth, const unsigned char* mask, const float* weights, const float* colors, const float* views, int N,
+                      int C, int H, int W, int nx, int ny, int nz, const float* h_lo, const float* h_step, float truncation, float near,
+                      int accumulate, float* sum, float* weight, float* tsdf, float* color_sum, float* color_weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

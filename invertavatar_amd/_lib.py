@@ -222,6 +222,7 @@ _SIGNATURES = {
     'ia_nearest_points_brute': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     'ia_nearest_points_tree': [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float] + [c_void_p] * 5,
     'ia_point_normals': [c_void_p, c_int64, c_void_p, c_int] + [c_void_p] * 5,
+    'ia_tsdf_integrate': [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_float, c_float, c_int] + [c_void_p] * 6,
 }
 
 

@@ -38,7 +38,10 @@ a pose search (``geometry.global_align``: a template in another coordinate frame
 ``--fit-iterations`` and ``--fit-normal-cos`` as in ``geometry_metrics``) and writes ``seed%04d_template.ply``: the template's own faces on
 the avatar's shape, so every seed has the same topology, with colours queried at the fitted vertices unless ``--no-colors``; a line per
 seed reports the template's vertices, the rms before and after, the inliers and the largest displacement, and ``seed%04d_geometry.json``
-gains a ``template`` block.  Runs on the device when there is one."""
+gains a ``template`` block.  ``--fuse-depth`` (with ``--views``) fuses the ray-cast depth maps of the orbit into one surface
+(``geometry.fuse_depth`` on the lattice of the density volume, ``geometry.fused_mesh``), writes it as ``seed%04d_fused.ply`` and prints the
+two-sided ``surface_distance`` between it and the marching-cubes mesh: whether the depth maps of the views describe the shape that was
+meshed.  Runs on the device when there is one."""
 import argparse
 import json
 import os
@@ -108,6 +111,7 @@ def main(argv=None):
     ap.add_argument('--mesh-views', type=int, default=0, help='also render N views of the final mesh (rasterised; same orbit) as PNGs')
     ap.add_argument('--render-res', type=int, default=512, help='pixels per side of the rendered views')
     ap.add_argument('--save-depth', action='store_true', help='with --views: also write the depth maps as .npy')
+    ap.add_argument('--fuse-depth', action='store_true', help='with --views: fuse the depth maps into one surface; writes _fused.ply')
     ap.add_argument('--keep', type=parse_keep, default=None, help="'largest' or N: keep only the N largest connected components of the shape")
     ap.add_argument('--min-voxels', type=int, default=0, help='with --keep: also drop kept components of fewer lattice points')
     ap.add_argument('--compare', default=None, metavar='REF.ply', help='score the extracted mesh against this mesh (Chamfer, Hausdorff, F-score)')
@@ -147,6 +151,8 @@ def main(argv=None):
         ap.error('--smooth-check needs --smooth')
     if args.align and not args.compare:
         ap.error('--align needs --compare')
+    if args.fuse_depth and args.views < 1:
+        ap.error('--fuse-depth needs --views')
     if (args.signed or args.iou is not None) and not args.compare:
         ap.error('--signed and --iou need --compare')
     smooth = None if args.smooth is None else {'iterations': args.smooth, 'lam': args.smooth_lambda, 'mu': args.smooth_mu,
@@ -284,6 +290,20 @@ def main(argv=None):
                 np.save(os.path.join(args.outdir, f'seed{seed:04d}_depth.npy'), views['depth'][0, :, 0].cpu().numpy())
             out['views'] = views
             print(f'seed {seed}: {args.views} views at {args.render_res}^2, {int(views["mask"].sum())} surface pixels')
+            if args.fuse_depth:
+                _, lo, step = geometry.lattice_axis(args.res, G.rendering_kwargs['box_warp'], 0.0)
+                fusion = geometry.fuse_depth(views['depth'][0], cams[0], args.res, origin=(float(lo),) * 3, spacing=(float(step),) * 3,
+                                             mask=views['mask'][0])
+                fv, ff = geometry.fused_mesh(fusion)
+                fpath = os.path.join(args.outdir, f'seed{seed:04d}_fused.ply')
+                geometry.write_ply(fpath, fv, ff)
+                line = f'seed {seed}: fused {args.views} depth maps: {fusion["info"]["observed"]} lattice points seen, {ff.shape[0]} triangles -> {fpath}'
+                if ff.shape[0] and out['faces'].shape[0]:
+                    d = geometry.surface_distance(fv, ff, out['verts'], out['faces'], samples=200000 if fv.is_cuda else 2000)
+                    out['fused'] = {'verts': fv, 'faces': ff, 'distance': d}
+                    line += (f'; fused -> mesh mean {d["mean_ab"]:.6g} max {d["max_ab"]:.6g}, mesh -> fused mean {d["mean_ba"]:.6g} max '
+                             f'{d["max_ba"]:.6g}, lattice step {float(step):.6g}')
+                print(line)
         if args.mesh_views > 0:
             from PIL import Image
             cams = orbit_cameras(G, args.mesh_views, device=args.device)

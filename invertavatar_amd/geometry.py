@@ -618,9 +618,8 @@ def keep_mesh_components(verts, faces, keep='largest', extras=()):
     flag[kept] = True
     flag = flag.to(tv.device)
     vmask, fmask = flag[vl.long()], flag[fl.long()]
-    new_index = torch.cumsum(vmask, 0) - 1
-    out_f = new_index[tf[fmask].long()].reshape(-1, 3)
-    out = [tv[vmask], out_f] + [torch.as_tensor(e).to(tv.device)[vmask] for e in extras]
+    out_v, out_f, out_e = _compact_mesh(tv, tf, vmask, fmask, [torch.as_tensor(e).to(tv.device) for e in extras])
+    out = [out_v, out_f] + out_e
     if as_np:
         out = [o.numpy() for o in out]
         stats = _np(stats)
@@ -4510,6 +4509,316 @@ def depth_to_points(depth, cameras, mask=None):
         o, dirs = RaySampler_zxc()(cams[:, :16].reshape(-1, 4, 4), cams[:, 16:25].reshape(-1, 3, 3), int(d.shape[1]))
     pts = (o + d.reshape(d.shape[0], -1, 1) * dirs)[m.reshape(d.shape[0], -1)]
     return pts if isinstance(like, torch.Tensor) else pts.cpu().numpy()
+
+
+# ------------------------------------------------------------------ depth fusion (TSDF)
+
+FUSE_MAX_CHANNELS = 8           # csrc/tsdf.hip kMaxChannels
+_FUSE_POINTS = 1 << 19          # lattice points per NumPy chunk
+_FUSE_SUMS = ('sum', 'weight', 'color_sum', 'color_weight')
+
+
+def _depth_box_numpy(depth, cam32, valid):
+    """(lo, hi) float64 [3] of the back-projected pixels ``o + t d`` of ``valid`` [N,H,W] (the points of ``depth_to_points``, for any
+    H and W: d the unit ray of pixel (i, j), K_res^-1 [i, j, 1] rotated into the world), or None when there is none."""
+    N, H, W = depth.shape
+    R, o, k = _camera_numpy(cam32, H, W, np.float64)
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for n in range(N):
+        jj, ii = np.nonzero(valid[n])
+        if not jj.size:
+            continue
+        xs, ys = ii - k[n, 2], jj - k[n, 5]
+        det = k[n, 0] * k[n, 4] - k[n, 1] * k[n, 3]
+        d = np.stack([(k[n, 4] * xs - k[n, 1] * ys) / det, (k[n, 0] * ys - k[n, 3] * xs) / det, np.ones(xs.shape)], 1)
+        d *= (depth[n, jj, ii].astype(np.float64) / np.sqrt(_dot3(d, d)))[:, None]
+        pts = o[n] + d @ R[n].T
+        pts = pts[np.isfinite(pts).all(1)]
+        if pts.shape[0]:
+            lo, hi = np.minimum(lo, pts.min(0)), np.maximum(hi, pts.max(0))
+    return (lo, hi) if np.isfinite(lo).all() else None
+
+
+def _fuse_numpy(axes, depth, cam32, tau, near, mask=None, weights=None, colors=None, sums=None, dtype=F32, decisions=None):
+    """The definition of ``fuse_depth`` on the lattice of the fp32 ``axes``: (sum [P], weight [P], color_sum [P,C] or None, color_weight
+    [P] or None) in ``dtype``, P = nx ny nz with z fastest; every operation is rounded on its own, the views are added in their order.
+    ``sums``: such a tuple to go on from.  ``decisions`` (a list): receives (code, pixel), int64 [N,P]: per view the number of the step
+    of the definition at which the view was skipped, negated (-1 .. -4; -3 also for an unusable weight), or 0 where it was added, and
+    the pixel ``j W + i`` looked up (-1 where step 1 or 2 skipped)."""
+    T = dtype
+    N, H, W = depth.shape
+    R, o, k = _camera_numpy(cam32, H, W, T)
+    dims = tuple(a.shape[0] for a in axes)
+    P, C = dims[0] * dims[1] * dims[2], 0 if colors is None else colors.shape[1]
+    tau, near = T(F32(tau)), T(F32(near))
+    dep = depth.astype(T)
+    wts = None if weights is None else weights.astype(T)
+    cols = None if colors is None else colors.astype(T)
+    F, Wt = (np.zeros(P, T), np.zeros(P, T)) if sums is None else (sums[0].astype(T).reshape(P), sums[1].astype(T).reshape(P))
+    Cs = CW = None
+    if C:
+        Cs, CW = (np.zeros((P, C), T), np.zeros(P, T)) if sums is None else (sums[2].astype(T).reshape(P, C), sums[3].astype(T).reshape(P))
+    taken = None if decisions is None else (np.zeros((N, P), dtype=np.int64), np.full((N, P), -1, dtype=np.int64))
+    with np.errstate(all='ignore'):
+        for c0 in range(0, P, _FUSE_POINTS):
+            idx = np.arange(c0, min(c0 + _FUSE_POINTS, P))
+            X = [axes[0][idx // (dims[1] * dims[2])].astype(T), axes[1][(idx // dims[2]) % dims[1]].astype(T), axes[2][idx % dims[2]].astype(T)]
+            f_, w_ = F[idx], Wt[idx]
+            if C:
+                c_, cw_ = Cs[idx], CW[idx]
+            for n in range(N):
+                d = [X[a] - o[n, a] for a in range(3)]
+                xc = [(R[n, 0, a] * d[0] + R[n, 1, a] * d[1]) + R[n, 2, a] * d[2] for a in range(3)]
+                ok1 = np.isfinite(xc[2]) & (xc[2] > near)
+                px = (k[n, 0] * xc[0] + k[n, 1] * xc[1]) + k[n, 2] * xc[2]
+                py = (k[n, 3] * xc[0] + k[n, 4] * xc[1]) + k[n, 5] * xc[2]
+                u, v = px / xc[2], py / xc[2]
+                fi, fj = np.rint(u), np.rint(v)
+                ok2 = ok1 & np.isfinite(u) & np.isfinite(v) & (fi >= 0) & (fi <= T(W - 1)) & (fj >= 0) & (fj <= T(H - 1))
+                ii, jj = np.where(ok2, fi, T(0)).astype(np.int64), np.where(ok2, fj, T(0)).astype(np.int64)
+                t = dep[n, jj, ii]
+                w = np.ones(idx.shape[0], T) if wts is None else wts[n, jj, ii]
+                ok3 = ok2 & np.isfinite(t) & (t > 0) & np.isfinite(w) & (w > 0)
+                if mask is not None:
+                    ok3 &= mask[n, jj, ii]
+                s = t - np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+                ok = ok3 & ~(s < -tau)
+                f_ = np.where(ok, f_ + np.minimum(s / tau, T(1)) * w, f_)
+                w_ = np.where(ok, w_ + w, w_)
+                if C:
+                    okc = ok & (s <= tau)
+                    c_ = np.where(okc[:, None], c_ + cols[n][:, jj, ii].T * w[:, None], c_)
+                    cw_ = np.where(okc, cw_ + w, cw_)
+                if taken is not None:
+                    taken[0][n, idx] = np.where(ok, 0, np.where(ok3, -4, np.where(ok2, -3, np.where(ok1, -2, -1))))
+                    taken[1][n, idx] = np.where(ok2, jj * W + ii, -1)
+            F[idx], Wt[idx] = f_, w_
+            if C:
+                Cs[idx], CW[idx] = c_, cw_
+    if decisions is not None:
+        decisions.append(taken)
+    return F, Wt, Cs, CW
+
+
+def _same_lattice(state, dims, org, spc, tau, channels):
+    """Raises unless ``state`` (a result of ``fuse_depth``) lies on this lattice with this truncation and channel count."""
+    try:
+        same = (tuple(state['sum'].shape) == dims and tuple(state['weight'].shape) == dims
+                and tuple(float(F32(x)) for x in state['origin']) == tuple(float(F32(x)) for x in org)
+                and tuple(float(F32(x)) for x in state['spacing']) == tuple(float(F32(x)) for x in spc)
+                and float(F32(state['truncation'])) == float(F32(tau))
+                and (tuple(state['color_sum'].shape) == dims + (channels,) if channels else 'color_sum' not in state))
+    except (KeyError, TypeError, AttributeError):
+        same = False
+    if not same:
+        raise ValueError('state must be the result of fuse_depth on the same lattice, with the same truncation and colour channels')
+
+
+def fuse_depth(depth, cameras, resolution, origin=None, spacing=None, truncation=None, mask=None, weights=None, colors=None, near=1e-6,
+               padding=2, state=None, dtype=np.float32):
+    """Depth maps with cameras fused into one truncated signed distance (TSDF) lattice.  ``depth`` [N,H,W] or [N,1,H,W] is the ray
+    parameter of the pixel's unit ray (the ``image_depth`` of ``synthesis``, the depth of ``raycast``, ``render_geometry``,
+    ``render_mesh`` and ``rasterize_mesh``; H and W may differ), ``cameras`` [N,25] the generator's labels (the last row of K must be
+    [0, 0, 1]).  Optional, shaped like ``depth``: ``mask`` (bool) and ``weights`` (float32, e.g. the cosine from a normal image);
+    ``colors`` [N,C,H,W] float32 with 1 <= C <= 8.
+
+    The lattice is that of ``marching_cubes`` / ``mesh_to_volume``: point (i, j, k) at ``origin + index * spacing`` in fp32
+    (``_lattice_axes``), volumes indexed [i, j, k] with z fastest.  With ``origin`` and ``spacing`` None it is fitted
+    (``_volume_lattice``, ``padding`` cells on every side) to the box of the back-projected valid pixels, or taken from ``state``.
+    ``truncation`` tau > 0 defaults to 3 times the largest spacing.  The definition, per lattice point X and for the
+    views n = 0 .. N - 1 in this order, float32 with every operation rounded on its own, ``R, o, k = _camera_numpy(...)``:
+
+    1. d = X - o, xc_a = (R_0a d_x + R_1a d_y) + R_2a d_z; the view is skipped unless xc_z is finite and > ``near``.
+    2. u = ((k0 xc_x + k1 xc_y) + k2 xc_z) / xc_z, v likewise with k3 .. k5; i = rint(u), j = rint(v) (ties to even; pixel centres
+       at integer coordinates; nearest pixel by design: interpolating depth across a silhouette invents surface).  Skipped unless u and v
+       are finite, 0 <= i <= W - 1 and 0 <= j <= H - 1, compared as floats.
+    3. t = depth[n,j,i]; skipped unless t is finite and > 0 and the mask is set.  w = weights[n,j,i] or 1; skipped unless w is finite
+       and > 0.
+    4. s = t - sqrt((d_x d_x + d_y d_y) + d_z d_z); skipped if s < -tau (the point is hidden behind the surface in this view).
+    5. sum += min(s / tau, 1) w, weight += w; with colours, and only if s <= tau, color_sum_c += colors[n,c,j,i] w, color_weight += w.
+
+    Returns, in the container of ``depth``: ``{'sum', 'weight', 'tsdf' float32 [nx,ny,nz]`` (tsdf = sum / weight where weight > 0, else
+    1: positive in front of the surface, negative behind it, so ``marching_cubes(-tsdf, 0, origin, spacing)`` meshes it; see
+    ``fused_mesh``), ``'observed'`` bool (weight > 0), with colours ``'color_sum'`` [nx,ny,nz,C], ``'color_weight'`` and ``'color'`` (the
+    quotient, 0 where unweighted), ``'origin'``, ``'spacing'``, ``'truncation'``, ``'info': {'views', 'observed', 'band'}`` (the points
+    seen and those with |tsdf| < 1)``}``.  ``state``: the dictionary an earlier call returned on the same lattice; the call goes on from
+    its sums, and since the sums run over the views in one order per point, views [0, N) in one call give the bits of [0, k) followed
+    by [k, N).  Device tensors run on ia_tsdf_integrate (csrc/tsdf.hip: one thread per lattice point, no atomics) and give the bits of
+    the float32 restatement; CPU tensors and NumPy arrays take the restatement, where ``dtype=np.float64`` evaluates everything after
+    the float32 camera labels in double and returns float64 sums."""
+    on_dev = _is_device(depth)
+    dshape = tuple(depth.shape)
+    if len(dshape) == 4 and dshape[1] == 1:
+        dshape = (dshape[0],) + dshape[2:]
+    if len(dshape) != 3 or min(dshape) < 1:
+        raise ValueError(f'depth must be [N,H,W] or [N,1,H,W] with N, H, W >= 1, got {tuple(depth.shape)}')
+    N, H, W = dshape
+    if cameras.ndim != 2 or tuple(cameras.shape) != (N, 25):
+        raise ValueError(f'cameras must be [{N},25], got {tuple(cameras.shape)}')
+    for name, a in (('mask', mask), ('weights', weights)):
+        if a is not None and tuple(a.shape) not in (dshape, (N, 1, H, W)):
+            raise ValueError(f'{name} must have the shape of depth, got {tuple(a.shape)}')
+    C = 0
+    if colors is not None:
+        if colors.ndim != 4 or colors.shape[0] != N or tuple(colors.shape[2:]) != (H, W):
+            raise ValueError(f'colors must be [{N},C,{H},{W}], got {tuple(colors.shape)}')
+        C = int(colors.shape[1])
+        if not 1 <= C <= FUSE_MAX_CHANNELS:
+            raise ValueError(f'colors must have 1 .. {FUSE_MAX_CHANNELS} channels, got {C}')
+    near = float(near)
+    if not near >= 0:
+        raise ValueError(f'near must be >= 0, got {near!r}')
+    dtype = np.dtype(dtype).type if not isinstance(dtype, torch.dtype) else {torch.float32: F32, torch.float64: np.float64}.get(dtype)
+    if dtype not in (np.float32, np.float64) or (on_dev and dtype is not np.float32):
+        raise ValueError('dtype must be float32 or float64, and float32 on the device')
+    cam32 = np.ascontiguousarray(_np(cameras), dtype=F32)
+    if not (cam32[:, 22:25] == np.array([0, 0, 1], dtype=F32)).all():
+        raise ValueError('the last row of K must be [0, 0, 1]')
+    if origin is None and spacing is None and state is not None:
+        origin, spacing = state.get('origin'), state.get('spacing')
+        truncation = state.get('truncation') if truncation is None else truncation
+    box = None
+    if origin is None and spacing is None:
+        d_np = np.asarray(_np(depth), dtype=F32).reshape(dshape)
+        valid = np.isfinite(d_np) & (d_np > 0)
+        if mask is not None:
+            valid &= _np(mask).astype(bool).reshape(dshape)
+        if weights is not None:
+            w_np = np.asarray(_np(weights), dtype=F32).reshape(dshape)
+            valid &= np.isfinite(w_np) & (w_np > 0)
+        box = _depth_box_numpy(d_np, cam32, valid)
+        if box is None:
+            raise ValueError('fuse_depth: no valid pixel to fit the lattice to; give origin and spacing')
+    dims, org, spc = _volume_lattice(box, resolution, origin, spacing, padding)
+    if dims[0] * dims[1] * dims[2] >= 1 << 31:
+        raise ValueError(f'a lattice of {dims} has 2^31 points or more')
+    tau = 3.0 * max(spc) if truncation is None else float(truncation)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError(f'truncation must be finite and > 0, got {truncation!r}')
+    tau = float(F32(tau))
+    if state is not None:
+        _same_lattice(state, dims, org, spc, tau, C)
+    names = _FUSE_SUMS[:4 if C else 2]
+    if on_dev:
+        from . import hipops
+        dev = depth.device
+        prep = lambda t, dt, shape: None if t is None else torch.as_tensor(t).detach().to(device=dev, dtype=dt).reshape(shape).contiguous()
+        R, o, k = _camera_numpy(cam32, H, W, F32)
+        views = torch.from_numpy(np.ascontiguousarray(np.concatenate([R.reshape(N, 9), o, k], 1), dtype=F32)).to(dev)
+        prior = None if state is None else {n_: prep(state[n_], torch.float32, tuple(state[n_].shape)) for n_ in names}
+        out = hipops.tsdf_integrate(prep(depth, torch.float32, dshape), views, dims, [F32(x) for x in org], [F32(x) for x in spc], tau, near,
+                                    prep(mask, torch.bool, dshape), prep(weights, torch.float32, dshape),
+                                    prep(colors, torch.float32, (N, C, H, W)), prior)
+        out['observed'] = out['weight'] > 0
+        if C:
+            cw = out['color_weight'][..., None]
+            out['color'] = torch.where(cw > 0, out['color_sum'] / torch.where(cw > 0, cw, torch.ones_like(cw)), torch.zeros_like(cw))
+        seen, band = int(out['observed'].sum()), int((out['tsdf'].abs() < 1).sum())
+    else:
+        as_np = lambda a, dt, shape: None if a is None else np.ascontiguousarray(_np(a), dtype=dt).reshape(shape)
+        prior = None if state is None else tuple(_np(state[n_]) for n_ in names) + (None,) * (4 - len(names))
+        F, Wt, Cs, CW = _fuse_numpy(_lattice_axes(dims, org, spc), as_np(depth, F32, dshape), cam32, tau, near, as_np(mask, bool, dshape),
+                                    as_np(weights, F32, dshape), as_np(colors, F32, (N, C, H, W)), prior, dtype)
+        with np.errstate(all='ignore'):
+            tsdf = np.where(Wt > 0, F / np.where(Wt > 0, Wt, dtype(1)), dtype(1))
+            res = {'sum': F.reshape(dims), 'weight': Wt.reshape(dims), 'tsdf': tsdf.reshape(dims)}
+            if C:
+                res.update(color_sum=Cs.reshape(dims + (C,)), color_weight=CW.reshape(dims),
+                           color=np.where(CW[:, None] > 0, Cs / np.where(CW > 0, CW, dtype(1))[:, None], dtype(0)).reshape(dims + (C,)))
+        seen, band = int((Wt > 0).sum()), int((np.abs(tsdf) < 1).sum())
+        out = {k_: _as_out(x, depth, dtype) for k_, x in res.items()}
+        out['observed'] = _as_out(Wt.reshape(dims) > 0, depth, bool)
+    out.update(origin=org, spacing=spc, truncation=tau, info={'views': N, 'observed': seen, 'band': band})
+    return out
+
+
+def _compact_mesh(verts, faces, vmask, fmask, extras=()):
+    """The faces of ``fmask`` over the vertices of ``vmask`` (tensors on one device): (verts, faces int64 re-indexed, extras), the
+    vertices compacted in their old order."""
+    new_index = torch.cumsum(vmask, 0) - 1
+    return verts[vmask], new_index[faces[fmask].long()].reshape(-1, 3), [e[vmask] for e in extras]
+
+
+def _fused_filter(verts, faces, fusion, min_weight, with_colors, xp):
+    """``fused_mesh`` steps 2 and 4 in float32, every operation rounded on its own, on NumPy arrays (``xp`` numpy: the restatement) or on
+    tensors of one device (``xp`` torch): (keep bool [F], vertex colours [V,C] or None)."""
+    dims = tuple(int(n) for n in fusion['weight'].shape)
+    if xp is torch:                                                      # (constants as tensors: a host scalar divisor becomes a reciprocal)
+        const = lambda v: torch.tensor(v, dtype=torch.float32, device=verts.device)
+        as_index = lambda c: c.long()
+    else:
+        const = lambda v: np.array(v, dtype=F32)
+        as_index = lambda c: c.astype(np.int64)
+    org, spc = const([float(F32(x)) for x in fusion['origin']]), const([float(F32(x)) for x in fusion['spacing']])
+    zero, one, three, top = const([0.0]), const([1.0]), const([3.0]), const([float(n - 2) for n in dims])
+
+    def cells(points):
+        """Position in cells ``(c - origin) / spacing`` and the cell ``clamp(floor(.), 0, n - 2)`` per axis, both float32 [M,3]."""
+        g = (points - org) / spc
+        return g, xp.minimum(xp.maximum(xp.floor(g), zero), top)
+
+    def corners(vol, cell):
+        """The eight corner values [M,8,...] of the cells int64 [M,3] of a lattice array, x slowest and z fastest."""
+        i, j, k = cell[:, 0], cell[:, 1], cell[:, 2]
+        return xp.stack([vol[i + a, j + b, k + c] for a in (0, 1) for b in (0, 1) for c in (0, 1)], 1)
+
+    tri = verts[faces.reshape(-1)].reshape(-1, 3, 3)
+    centre = ((tri[:, 0] + tri[:, 1]) + tri[:, 2]) / three
+    keep = corners(fusion['weight'] > min_weight, as_index(cells(centre)[1])).all(1)
+    if not with_colors:
+        return keep, None
+    g, cell = cells(verts)
+    t = xp.minimum(xp.maximum(g - cell, zero), one)
+    s = one - t
+    idx = as_index(cell)
+    w8 = xp.stack([((t if a else s)[:, 0] * (t if b else s)[:, 1]) * (t if c else s)[:, 2] for a in (0, 1) for b in (0, 1) for c in (0, 1)], 1)
+    w8 = xp.where(corners(fusion['color_weight'], idx) > 0, w8, zero)
+    col = corners(fusion['color'], idx)                                   # [V,8,C]
+    num, den = w8[:, 0, None] * col[:, 0], w8[:, 0]
+    for c in range(1, 8):
+        num, den = num + w8[:, c, None] * col[:, c], den + w8[:, c]
+    seen = den > 0
+    return keep, xp.where(seen[:, None], num / xp.where(seen, den, one)[:, None], zero)
+
+
+def fused_mesh(fusion, min_weight=0.0, with_colors=False):
+    """The surface of a ``fuse_depth`` result: ``(verts float32 [V,3], faces int64 [F,3])``, with ``with_colors`` also vertex colours
+    [V,C].
+
+    1. ``marching_cubes(-tsdf, 0, origin, spacing)``.
+    2. A face is kept only if all eight corners of the cell that holds its centroid have ``weight > min_weight``; the centroid is
+       ``((A + B) + C) / 3`` per axis and the cell ``clamp(floor((c - origin) / spacing), 0, n - 2)``, all in float32.  This removes the
+       false sheets between seen and never-seen space (unseen points hold tsdf = 1) that a TSDF has behind every surface and at the
+       edges of the frustums.
+    3. Unused vertices are dropped; the others keep their order and their bits (they are ``marching_cubes``' own).
+    4. Vertex colours: the trilinear interpolation of ``'color'`` over the corners with ``color_weight > 0`` of the vertex's cell,
+       renormalised (0 where no corner has colour).
+
+    Steps 2 to 4 are PyTorch on the device of a device result and NumPy (the restatement) otherwise; the face filter agrees exactly."""
+    tsdf = fusion['tsdf']
+    if with_colors and 'color' not in fusion:
+        raise ValueError('with_colors needs a fusion with colours')
+    min_weight = float(min_weight)
+    if _is_device(tsdf):
+        verts, faces = marching_cubes(-tsdf.float(), 0.0, fusion['origin'], fusion['spacing'])
+        fus = {k: fusion[k].float() for k in ('tsdf', 'weight', 'color', 'color_weight') if k in fusion}
+        fus.update(origin=fusion['origin'], spacing=fusion['spacing'])
+        keep, cols = _fused_filter(verts, faces, fus, min_weight, with_colors, torch)
+        tv, tf = verts, faces
+    else:
+        fus = {k: np.asarray(_np(fusion[k]), dtype=F32) for k in ('tsdf', 'weight', 'color', 'color_weight') if k in fusion}
+        fus.update(origin=fusion['origin'], spacing=fusion['spacing'])
+        verts, faces = _mc_numpy(-fus['tsdf'], 0.0, _vec3(fusion['origin']), _vec3(fusion['spacing']))
+        keep, cols = _fused_filter(verts, faces, fus, min_weight, with_colors, np)
+        tv, tf, keep = torch.from_numpy(verts), torch.from_numpy(faces), torch.from_numpy(keep)
+        cols = None if cols is None else torch.from_numpy(np.ascontiguousarray(cols, dtype=F32))
+    vmask = torch.zeros(tv.shape[0], dtype=torch.bool, device=tv.device)
+    vmask[tf[keep].reshape(-1)] = True
+    v, f, extras = _compact_mesh(tv, tf, vmask, keep, [cols] if with_colors else [])
+    out = [v, f] + extras
+    if not isinstance(tsdf, torch.Tensor):
+        out = [o.numpy() for o in out]
+    return tuple(out)
 
 
 # ------------------------------------------------------------------ texture atlas

@@ -21,7 +21,11 @@ lie far apart, where the uniform grid walks every cell; the JSON then records ``
 optional rigid alignment) wraps the prediction onto the ground truth with ``geometry.nonrigid_align`` (``--fit-metric``,
 ``--fit-stiffness 50,10,2,0.5``, ``--fit-iterations``, ``--fit-normal-cos``), scores the FITTED mesh, adds a ``nonrigid`` block (rms before
 and after, the levels, inliers, the largest displacement) and, with ``--save-fitted OUT.ply``, writes the fitted mesh: the prediction's own
-faces on the ground truth's shape.  Without these flags the outputs are what they were.  Runs on the device when there is one."""
+faces on the ground truth's shape.  ``--target-depth depth.npy --target-cameras cams.npy`` (instead of ``--gt``) takes the ground truth
+from depth maps [N,H,W] with camera labels [N,25]: they are fused on a lattice of ``--target-resolution`` points along the longest axis
+(``geometry.fuse_depth``) and meshed (``geometry.fused_mesh``), and the result is scored through the mesh route like any ``--gt``; the JSON
+then carries a ``target`` block (views, lattice, truncation, triangles).  Without these flags the outputs are what they were.  Runs on
+the device when there is one."""
 import argparse
 import json
 import math
@@ -180,6 +184,19 @@ def compare_clouds(verts, faces, ref_verts, ref_faces, samples=None, seed=0, thr
     return res
 
 
+def depth_target(depth_path, cameras_path, resolution=128, device='cpu'):
+    """A ground truth given as depth maps (``depth_path``: .npy [N,H,W] or [N,1,H,W], the ray parameter per pixel, 0 / NaN where there
+    is none; ``cameras_path``: .npy [N,25]): ``(verts, faces, block)`` of ``geometry.fused_mesh(geometry.fuse_depth(...))`` on ``device``."""
+    depth = torch.from_numpy(np.ascontiguousarray(np.load(depth_path), dtype=np.float32)).to(device)
+    cams = torch.from_numpy(np.ascontiguousarray(np.load(cameras_path), dtype=np.float32)).to(device)
+    fusion = geometry.fuse_depth(depth, cams, int(resolution))
+    verts, faces = geometry.fused_mesh(fusion)
+    block = {'source': 'depth', 'views': fusion['info']['views'], 'resolution': [int(n) for n in fusion['tsdf'].shape], 'origin': list(fusion['origin']),
+             'spacing': list(fusion['spacing']), 'truncation': fusion['truncation'], 'observed': fusion['info']['observed'],
+             'vertices': int(verts.shape[0]), 'faces': int(faces.shape[0])}
+    return verts, faces, block
+
+
 def add_sign_arguments(ap):
     """``--signed``, ``--iou``, how their winding numbers are made (``--winding``, ``--winding-beta``) and how closest points are searched
     (``--search``), shared with extract_geometry."""
@@ -266,7 +283,10 @@ def summary(res):
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Chamfer distance, Hausdorff distance and F-score of two PLY meshes')
     ap.add_argument('--pred', required=True)
-    ap.add_argument('--gt', required=True)
+    ap.add_argument('--gt', default=None, help='the ground-truth mesh or cloud (PLY); or give --target-depth and --target-cameras')
+    ap.add_argument('--target-depth', default=None, metavar='depth.npy', help='ground truth as depth maps [N,H,W]: fused and meshed, then scored as a mesh')
+    ap.add_argument('--target-cameras', default=None, metavar='cams.npy', help='with --target-depth: the camera labels [N,25]')
+    ap.add_argument('--target-resolution', type=int, default=128, help='with --target-depth: lattice points along the longest axis')
     ap.add_argument('--samples', type=int, default=None, help='area-weighted samples per mesh; default: the vertices')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--thresholds', type=float, nargs='+', default=None, help='F-score thresholds (at most 8); default 0.5, 1, 2 %% of the diagonal')
@@ -279,8 +299,17 @@ def main(argv=None):
     ap.add_argument('--save-fitted', default=None, metavar='OUT.ply', help='with --fit-nonrigid: write the fitted predicted mesh')
     ap.add_argument('--device', default='cuda' if torch.cuda.is_available() else 'cpu')
     args = ap.parse_args(argv)
-    meshes = []
+    if (args.gt is None) == (args.target_depth is None) or (args.target_depth is None) != (args.target_cameras is None):
+        ap.error('give --gt, or --target-depth together with --target-cameras')
+    meshes, target = [], None
     for path in (args.pred, args.gt):
+        if path is None:
+            tv, tf, target = depth_target(args.target_depth, args.target_cameras, args.target_resolution, args.device)
+            if not tf.shape[0]:
+                ap.error(f'{args.target_depth}: the fused depth maps have no surface')
+            args.gt = args.target_depth
+            meshes += [tv, tf]
+            continue
         v, f, _ = geometry.read_ply(path)
         meshes += [torch.from_numpy(v).to(args.device), torch.from_numpy(f).to(args.device)]
     if args.save_aligned and not args.align:
@@ -306,6 +335,9 @@ def main(argv=None):
     if args.fit_nonrigid:
         extra.update(fit=fit_options_of(args), save_fitted=args.save_fitted)
     res = compare_meshes(*meshes, samples=args.samples, seed=args.seed, thresholds=args.thresholds, error_ply=args.error_ply, **extra)
+    if target is not None:
+        res['target'] = target
+        print(f'target: {target["views"]} depth maps fused on {target["resolution"]}, {target["faces"]} triangles')
     with open(args.out, 'w') as fh:
         json.dump(res, fh, indent=1)
     if args.align:

@@ -2652,6 +2652,55 @@ def rasterize_mesh(verts, faces, cams, h, w, normals=None, attributes=None, cull
     return out
 
 
+# ------------------------------------------------------------------ TSDF integration (csrc/tsdf.hip)
+
+TSDF_MAX_CHANNELS = 8        # csrc/tsdf.hip kMaxChannels
+TSDF_VIEW_ROW = 18           # csrc/tsdf.hip kViewRow
+
+
+def tsdf_integrate(depth, views, dims, lo, step, truncation, near=1e-6, mask=None, weights=None, colors=None, state=None):
+    """Depth maps fused into a lattice (see ia_tsdf_integrate): depth float32 [N,H,W], views float32 [N,18] (rotation, origin, rows 0 and
+    1 of K_res), mask bool [N,H,W], weights float32 [N,H,W], colors float32 [N,C,H,W] -> dict of 'sum', 'weight', 'tsdf' [nx,ny,nz] and,
+    with colours, 'color_sum' [nx,ny,nz,C] and 'color_weight'.  ``state``: such a dict, whose sums the call goes on from (it is not
+    modified)."""
+    _f32c(depth, 'depth'), _f32c(views, 'views')
+    if depth.dim() != 3 or views.dim() != 2 or tuple(views.shape) != (depth.shape[0], TSDF_VIEW_ROW) or views.device != depth.device:
+        raise RuntimeError(f'depth must be [N,H,W] and views [N,{TSDF_VIEW_ROW}] on one device, got {tuple(depth.shape)} and {tuple(views.shape)}')
+    n, h, w = depth.shape
+    dev = depth.device
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3:
+        raise RuntimeError(f'dims must be (nx, ny, nz), got {dims}')
+    if mask is not None and not (mask.is_cuda and mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (n, h, w)):
+        raise RuntimeError(f'mask must be a contiguous bool device tensor {(n, h, w)}')
+    if weights is not None and tuple(_f32c(weights, 'weights').shape) != (n, h, w):
+        raise RuntimeError(f'weights must be {(n, h, w)}, got {tuple(weights.shape)}')
+    c = 0
+    if colors is not None:
+        _f32c(colors, 'colors')
+        if colors.dim() != 4 or colors.shape[0] != n or tuple(colors.shape[2:]) != (h, w):
+            raise RuntimeError(f'colors must be [{n},C,{h},{w}], got {tuple(colors.shape)}')
+        c = int(colors.shape[1])
+    names = ('sum', 'weight') + (('color_sum', 'color_weight') if c else ())
+    shapes = {'color_sum': dims + (c,)}
+    if state is None:
+        out = {k: torch.empty(shapes.get(k, dims), device=dev) for k in names}
+    else:
+        for k in names:
+            if tuple(_f32c(state[k], f"state['{k}']").shape) != shapes.get(k, dims) or state[k].device != dev:
+                raise RuntimeError(f"state['{k}'] must be {shapes.get(k, dims)} on the device of depth, got {tuple(state[k].shape)}")
+        out = {k: state[k].clone() for k in names}
+    out['tsdf'] = torch.empty(dims, device=dev)
+    points = dims[0] * dims[1] * dims[2]
+    nbytes = 4.0 * points * (3 + (c + 1 if c else 0)) * (2 if state is not None else 1)
+    with torch.cuda.device(dev), _Timed('tsdf_integrate', 40.0 * points * n, nbytes, f'{dims} N={n} {h}x{w} C={c}'):
+        st = _lib.load().ia_tsdf_integrate(_p(depth), _p(mask), _p(weights), _p(colors), _p(views), n, c, h, w, *dims, _f3(lo), _f3(step),
+                                           float(truncation), float(near), int(state is not None), _p(out['sum']), _p(out['weight']),
+                                           _p(out['tsdf']), _p(out.get('color_sum')), _p(out.get('color_weight')), _lib.stream_ptr(dev))
+    _lib.check(st, 'ia_tsdf_integrate')
+    return out
+
+
 # ------------------------------------------------------------------ texture atlas (csrc/texture.hip)
 
 TEXTURE_TIMES = None         # a dict collects seconds per stage, as SMOOTH_TIMES does: tools/bench_texture.py

@@ -378,6 +378,7 @@ __global__ __launch_bounds__(512) void torgb_wide_kernel(TParams p) {
             h8* s_hi = reinterpret_cast<h8*>(s_w);
             h8* s_lo = s_hi + (p.I >> 3) * OP;
             const int total = (p.I >> 3) * OP;
+            unsigned w_bad = 0u;                                  // a staged weight outside the fp16 range (or NaN) is clamped below: the range watch hears of it
             for (int e = tid; e < total; e += 512) {
                 const int oct = e / OP, o = e - oct * OP;
                 float w8[8];
@@ -386,6 +387,7 @@ __global__ __launch_bounds__(512) void torgb_wide_kernel(TParams p) {
                     const int k = oct * 8 + j;
                     const float w = o < p.O ? p.wk[(int64_t)k * p.O + o] : 0.f;
                     w8[j] = (w * (sp ? sp[k] : 1.f)) * kWideWScale;
+                    w_bad |= (fabsf(w8[j]) <= 65504.f) ? 0u : 1u;
                     w8[j] = fminf(fmaxf(w8[j], -65504.f), 65504.f);
                 }
                 h8 hi, lo;
@@ -393,6 +395,7 @@ __global__ __launch_bounds__(512) void torgb_wide_kernel(TParams p) {
                 s_hi[e] = hi;
                 s_lo[e] = lo;
             }
+            if (w_bad) atomicOr(&ia_tu_saturated, 1u);
         }
     }
 

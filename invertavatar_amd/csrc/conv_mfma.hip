@@ -586,7 +586,9 @@ extern "C" int ia_conv2d_sx_supported(int I, int O, int H, int W, int ksize, int
     const int side = 8;                                      // smallest image: kSplitMinPoints = 8^2 (9^2 points transposed)
     if ((H < W ? H : W) < side) return 0;
     if (transposed) return npts >= (side + 1) * (side + 1) ? 1 : 0;
-    return (O >= 128 && npts >= kSplitMinPoints && W <= 512) ? 1 : 0;
+    // (the 256-point windows must fit the patch, as tile_dims asks before it gives the 8-wave tile: W = 255, 257, 300 do not, and the
+    // dispatcher refuses what falls off the two-stage tiles)
+    return (O >= 128 && npts >= kSplitMinPoints && W <= 512 && worst_patch(npts, W, 256, 3, false) <= kPatchFloats) ? 1 : 0;
 }
 
 static size_t scratch_bytes_for(int B, int G, int slab_floats) { return (size_t)B * G * 2 * slab_floats * sizeof(float); }

@@ -673,8 +673,9 @@ def test_conv_sx_with_fused_torgb(res, planes):
 def test_row_phase_upconv_equals_the_four_phase_form_and_fp64(b, i, o, h, w):
     """r04: ia_upconv2d_rows_sx -- the transposed 3x3 convolution per output row phase on the stride-1 tile (two accumulator sets, no
     zero k-step) -- forms the same products as ia_conv2d_mfma_sx(transposed): equal to summation-order level, as close to the fp64
-    convolution of the operands the kernel sees, every pixel of the (2H+1) x (2W+1) image written (interior tiles, bottom row, last
-    column; whole tiles and K-split edge tiles), run-to-run identical."""
+    convolution of the operands the kernel sees (interior tiles, bottom row, last column; whole tiles and K-split edge tiles), run-to-run
+    identical.  (That every pixel is written, and nothing outside the image or the scratch, is checked on NaN-filled buffers with guard
+    bands in tests/test_conv_edges_gpu.py.)"""
     assert hipops.upconv_rows_supported(b, i, o, h, w)
     g = torch.Generator(device='cuda').manual_seed(23 + i + h)
     x = torch.randn(b, i, h, w, device='cuda', generator=g) * 2
@@ -685,7 +686,6 @@ def test_row_phase_upconv_equals_the_four_phase_form_and_fp64(b, i, o, h, w):
     wk = hipops.pack_conv_weight_split(wt)
     ref = torch.nn.functional.conv_transpose2d(xs.float().double(), wt.double().transpose(0, 1), stride=2) * d.double()[:, :, None, None]
     scale = ref.abs().max().item()
-    poison = torch.full_like(ref, float('nan'), dtype=torch.float32)
     got = hipops.upconv2d_rows_sx(xs, wk, demod=d)
     assert got.shape == ref.shape and torch.isfinite(got).all()
     err = (got.double() - ref).abs().max().item()
@@ -699,7 +699,6 @@ def test_row_phase_upconv_equals_the_four_phase_form_and_fp64(b, i, o, h, w):
     none = hipops.upconv2d_rows_sx(xs, wk)                      # without demodulation
     ref1 = torch.nn.functional.conv_transpose2d(xs.float().double(), wt.double().transpose(0, 1), stride=2)
     assert (none.double() - ref1).abs().max().item() <= 3e-6 * ref1.abs().max().item()
-    del poison
 
 
 def test_row_phase_upconv_refuses_what_it_does_not_cover():
